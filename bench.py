@@ -2,7 +2,7 @@
 """Headline benchmark: reconstructed frames/s (+ Mevents/s voxelized) of the E2VID hot path at 346x260,
 5 bins, 15k events/window on MI355X (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n-seq S] [--sensor WxH] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n-seq S] [--sensor WxH] [--config NAME] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -31,8 +31,11 @@ gate 1e-5); EVR_ARITH=mx6 the opt-in fast mode (f16 + MX-fp6 cross terms; the `f
 fp32 MFMA.  `config.arithmetic_mode` / `dtype` report what the model actually ran (evr_model_arith).
 
 Rank 0 prints ONE JSON line < 4 KB as the LAST stdout line (compact_line: every key of the task's contract + `roofline` (dominant kernel)
-+ `cpu_baseline`, scalars only for the side blocks); the full object is written to gpurun_out/bench_full.json.  `--sub` runs (the side
-blocks' sub-processes) print the full object.  Blocks of the full object, all measured OUTSIDE the timed region of the same run:
++ `cpu_baseline`, scalars only for the side blocks).  A plain run does only what the headline needs: set-up, warm-up, the K timed steps
+(the same timed region in every mode, dominant-kernel brackets included, so e2vid's `roofline` comes free), `--dump-outputs` and the
+line; `cpu_baseline` is null there.  `--full` adds everything below and also writes the full object to a JSON file (`--full-json`).  `--sub`
+runs (the side blocks' sub-processes) measure like `--full` without sub-runs of their own and print the full object.  Blocks of the
+full object (`--full` / `--sub`), all measured OUTSIDE the timed region of the same run:
   roofline_voxelizer  HIP-event time of the tensorizer launches (in the step and standalone at S and 512 windows)
   score_parity        the first frames of sequences 0 and 37 replayed on the GPU and through the CPU oracle: per-frame image
                       error, mean MSE/SSIM/LPIPS of both, relative error, agreement to 3 significant figures
@@ -45,6 +48,11 @@ blocks' sub-processes) print the full object.  Blocks of the full object, all me
   large_batch / small_batch   128 and 1, 4, 8, 16, 32 sequences per GPU
   steady_state        >= 2 s of back-to-back steps
   per_rank            (N > 1) slowest / fastest rank's own frames/s
+
+`--dump-outputs DIR` (rank 0): what the timed path handed its caller in the LAST timed step, as DIR/<name>.npy in float32 / float64 --
+`image` [S, 1, H, W] (the reconstructions after post-processing) and `scores` [S, 3] (MSE, SSIM, LPIPS) of rank 0's sequences; colour:
+`image` (BGR, as float32), `planes`, `gray`.  Above 64 MB in all, a fixed seeded sample of the sequences (leading axis) is written.  The
+inputs are seeded: the same arguments give the same inputs on every run, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -354,6 +362,26 @@ def score_parity(gpu_frames, cpu_frames, names, gate=1e-4, sequences=(0,)):
 
 
 # ------------------------------------------------------------------------------------------------ helpers
+OUTPUT_LIMIT = 64 << 20       # bytes of --dump-outputs in all
+
+
+def write_outputs(dirpath, arrays, limit=OUTPUT_LIMIT):
+    """--dump-outputs: arrays {name: array with the sequences on its leading axis} -> dirpath/<name>.npy in float32 / float64.  Above
+    `limit` bytes in all, the same fixed seeded sample of the leading axis is taken from every array."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    n = min(v.shape[0] for v in arrays.values())
+    if total > limit:
+        keep = max(1, int(n * limit // total))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: np.ascontiguousarray(v[rows]) for k, v in arrays.items()}
+    os.makedirs(dirpath, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirpath, k + '.npy'), v)
+    return sorted(arrays)
+
+
 def sub_run(extra_args, env_extra, steps, warmup, timeout=420):
     """The same bench in a sub-process (outside this process's timed region); returns its parsed JSON line."""
     env = dict(os.environ); env.update(env_extra)
@@ -582,19 +610,13 @@ def run_color(args, wl, device):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for s in range(Wm, Wm + K):
-        step(s)
+        last = step(s)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    net.model.profile(''); net.half.profile('')          # the fully bracketed pass, outside the timed region
-    for s in range(Wm, Wm + min(K, 4)):
-        step(s)
-    torch.cuda.synchronize()
-    prof = [dict(p, name='full.' + p['name']) for p in net.model.profile_read()] + [dict(p, name='half.' + p['name']) for p in net.half.profile_read()]
-    net.model.profile(None); net.half.profile(None)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {k: last[k].cpu().numpy() for k in ('image', 'planes', 'gray')})
     flops = net.model.flops_per_step() + net.half.flops_per_step()
     an = arith_name(net)
-    peak = PEAK_F32_MFMA_TFLOPS if an == 'fp32' else PEAK_BF16_MFMA_TFLOPS
-    dom = dominant_group(prof)
     out = {"metric": "reconstructed frames/sec + Mevents/sec voxelized, ColorNet (E2VID+ layout) %dx%d B=5" % (W_, H_),
            "value": round(n_seq * K / elapsed, 2), "unit": "frames/s", "n_gpus": 1, "steps": K, "warmup": Wm,
            "ms_per_step": round(1e3 * elapsed / K, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -606,6 +628,16 @@ def run_color(args, wl, device):
                                   "them in colour mode, utils/eval_metrics.py:272)" % (wl.title, W_, H_, k, n_seq, 5 * n_seq),
                       "sequences_per_gpu": n_seq, "events_per_window": k, "sensor": [W_, H_], "bins": BINS,
                       "gflop_per_frame": round(flops / n_seq / 1e9, 3)}}
+    if not (args.full or args.sub):
+        return out
+    net.model.profile(''); net.half.profile('')          # the fully bracketed pass, outside the timed region
+    for s in range(Wm, Wm + min(K, 4)):
+        step(s)
+    torch.cuda.synchronize()
+    prof = [dict(p, name='full.' + p['name']) for p in net.model.profile_read()] + [dict(p, name='half.' + p['name']) for p in net.half.profile_read()]
+    net.model.profile(None); net.half.profile(None)
+    peak = PEAK_F32_MFMA_TFLOPS if an == 'fp32' else PEAK_BF16_MFMA_TFLOPS
+    dom = dominant_group(prof)
     if dom:
         name, g, total = dom
         ach = g['flops'] / (g['ms'] * 1e-3) / 1e12
@@ -740,7 +772,14 @@ def main():
     ap.add_argument('--unique-steps', type=int, default=40, help='distinct windows per sequence resident in HBM; later steps reuse them in order '
                     '(windows do not depend on the recurrence, the recurrent state keeps evolving: every step does all of its work)')
     ap.add_argument('--side-steps', type=int, default=20, help='timed steps of every side block (sub-processes)')
+    ap.add_argument('--full', action='store_true', help='also the CPU baseline, oracle parity, roofline passes, steady state, small batches and '
+                    'the side blocks (other precisions, sizes and configurations); off: the headline alone')
+    ap.add_argument('--full-json', default=None, metavar='PATH', help='--full: write the full object to PATH instead of the default place')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config == 'eval_cli':
+        raise SystemExit("bench.py: --dump-outputs has no timed step to dump under --config eval_cli")
+    extras = args.full or args.sub      # everything beyond the headline figure
     if not args.parity_frames:
         args.parity_frames = 4 if args.sub else 12
 
@@ -750,7 +789,8 @@ def main():
             raise SystemExit(f"bench.py: --gpus {args.gpus} but only {torch.cuda.device_count()} GPUs are visible")
         cmd = launch_command(args.gpus, sys.argv[1:])
         sys.stdout.flush()
-        os.execvpe(cmd[0], cmd, dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0')))
+        # a child process, not an exec: this process may already have opened the GPU (torch.cuda.device_count above)
+        sys.exit(subprocess.call(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0'))))
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     if not torch.cuda.is_available():
@@ -765,6 +805,14 @@ def main():
         ctypes.CDLL(None).fflush(None)      # RCCL prints a version banner through C stdio: keep the JSON the LAST stdout line
         if args.sub:
             print(json.dumps(out), flush=True)
+            return
+        if not args.full:                   # a plain run: the line alone
+            print(json.dumps(compact_line(out, None)), flush=True)
+            return
+        if args.full_json:
+            with open(args.full_json, 'w') as f:
+                json.dump(out, f, indent=1)
+            print(json.dumps(compact_line(out, args.full_json)), flush=True)
             return
         path = None
         try:
@@ -791,7 +839,7 @@ def main():
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         os.environ.setdefault('MASTER_PORT', '29533')
         dist.init_process_group('nccl', rank=rank, world_size=world, device_id=device)
-    side = (world == 1) and not args.sub and args.config == 'e2vid' and sensor is None   # the side blocks run on the default run only
+    side = args.full and (world == 1) and args.config == 'e2vid' and sensor is None   # the side blocks run on the default --full run only
 
     from evreal_amd import weights
     from evreal_amd.pipeline import HotPath
@@ -835,41 +883,46 @@ def main():
     offs_flat = torch.arange(U * n_seq + 1, dtype=torch.int64, device=device) * K_EVENTS
 
     def run_steps(h, s_begin, s_end, ref, out_rows, ns=None):
+        """-> what the last step returned: (images [ns, 1, H, W], scores), complete once the streams are synchronised."""
         ns = ns or n_seq
+        last = None
         if AHEAD == 1 or ns != n_seq:
             for s in range(s_begin, s_end):
                 u = s % U
-                h.step_raw(xy, ts, pol, offs[u][:ns + 1] if ns != n_seq else offs[u], ref, out_rows(s), n_window_events=ns * K_EVENTS)
+                last = h.step_raw(xy, ts, pol, offs[u][:ns + 1] if ns != n_seq else offs[u], ref, out_rows(s), n_window_events=ns * K_EVENTS)
             h.flush()
-            return
+            return last
         s0 = s_begin
         while s0 < s_end:
             u0 = s0 % U
             a = min(AHEAD, s_end - s0, U - u0)
             h.prefetch_raw(xy, ts, pol, offs_flat[u0 * n_seq:(u0 + a) * n_seq + 1], a, n_window_events=a * n_seq * K_EVENTS, capacity=AHEAD)
             for s in range(s0, s0 + a):
-                h.step_ahead(ref, out_rows(s))
+                last = h.step_ahead(ref, out_rows(s))
             s0 += a
         h.flush()
+        return last
 
     run_steps(hp, 0, Wm, refs, lambda s: scores[s])
     net.profile(pf_timed)
     hp.time_voxelizer(True)
     barrier()
     t0 = time.perf_counter()
-    run_steps(hp, Wm, Wm + K, refs, lambda s: scores[s])
+    last_img, _ = run_steps(hp, Wm, Wm + K, refs, lambda s: scores[s])
     barrier()
     elapsed = time.perf_counter() - t0
     prof = net.profile_read() if pf_timed is not None else []
     net.profile(None)
     vox_ms_in_step = hp.time_voxelizer(False)
     sc = scores[Wm:].cpu().numpy()                       # [K, n_seq, 3] before anything below rewrites the buffer
+    if args.dump_outputs and rank == 0:                  # (the image buffer is reused by the passes below)
+        write_outputs(args.dump_outputs, {'image': last_img.cpu().numpy(), 'scores': sc[-1]})
     hp.check_dropped()                                   # out-of-sensor events would have been dropped silently: raise instead
     sat_runs, sat_layer = net.saturation()
 
     # ---- everything below is outside the timed region ----
     scratch = torch.zeros((n_seq, 3), dtype=torch.float64, device=device)
-    if pf_timed is None:                                 # the fully bracketed pass (same two-stream step)
+    if pf_timed is None and extras:                      # the fully bracketed pass (same two-stream step)
         net.profile(pf)
         run_steps(hp, Wm, Wm + min(K, 6), refs, lambda s: scratch)
         barrier()
@@ -878,7 +931,7 @@ def main():
     # the same layers once more with the evaluation kernels on the SAME stream, so the dominant kernel's duration is
     # also known without the second stream's kernels sharing the chip with it
     prof_single = None
-    if hp.overlap:
+    if hp.overlap and extras:
         hp.overlap = False
         net.profile(pf)
         run_steps(hp, Wm, min(Wm + 3, Wm + K), refs, lambda s: scratch)
@@ -888,7 +941,7 @@ def main():
         hp.overlap = True
 
     steady = None
-    if side or args.sub or world > 1:
+    if extras and (side or args.sub or world > 1):
         cycles = max(1, int(np.ceil(2.2 / max(elapsed, 1e-3))))
         barrier()
         t1 = time.perf_counter()
@@ -926,11 +979,13 @@ def main():
                         "channels; 256 x 256 tiles above)" if an != 'fp32' else ("wino_f32_kernel<LSTM=true> (ConvLSTM gate convolutions, Winograd F(2x2,3x3) in fp32: persistent blocks of 64 tiles x 64 columns)"
                         if wino_on else "conv_igemm_kernel<32,4,4,LSTM=true,REGSTAGE,X3=0> (ConvLSTM gate convolutions)"))
             share = None
-        else:
+        elif prof:
             name, g, total_ms = dominant_group(prof)
             lstm = [p for p in prof if p['name'] in g['layers']]
             dom_name = name + " (" + ", ".join(g['layers']) + ")"
             share = round(g['ms'] / total_ms, 3)
+        else:                                            # (a plain run of the other configurations brackets nothing)
+            lstm, dom_name, share = [], None, None
         rl_flops = sum(p['flops_per_launch'] * p['launches'] for p in lstm)
         rl_ms = sum(p['ms'] for p in lstm)
         rl_launches = sum(p['launches'] for p in lstm)
@@ -976,7 +1031,7 @@ def main():
                          "mfma_issue_frac": round(achieved * issue / peak, 4),
                          "streams": ("2: reconstruction | evaluation (robust norm, MSE/SSIM, LPIPS of the previous frame) -- "
                                      "the timed launches share the chip with the evaluation kernels"
-                                     if prof_single is not None else "1"),
+                                     if hp.overlap else "1"),
                          "single_stream": (None if prof_single is None else (lambda l: {
                              "avg_launch_us": round(1e3 * sum(p['ms'] for p in l) / max(sum(p['launches'] for p in l), 1), 2),
                              "achieved": round(sum(p['flops_per_launch'] * p['launches'] for p in l) / max(sum(p['ms'] for p in l) * 1e-3, 1e-12) / 1e12, 2)})(
@@ -987,6 +1042,8 @@ def main():
             "steady_state": steady,
             "per_rank": per_rank,
         }
+        if not prof:
+            out["roofline"] = None
         df = [p_ for p_ in prof if p_['name'] == 'dynamic_filter' and p_['launches']]
         if df:      # HyperE2VID's per-pixel dynamic filtering (hyper_dynamic.py:50-57,83-88) is a VALU kernel bound by its tensors: x [n,h,w,256] and
             # coeff [n,h,w,72] read once, out [n,h,w,1536] written once, 4 B per channel, at the first decoder's output grid (hp/4 x wp/4)
@@ -1017,7 +1074,7 @@ def main():
                              "frac": round(g / PEAK_HBM_GBS, 4), "us_per_step": round(1e3 * vox_ms_in_step * n_launch / K, 2),
                              "note": "inside the timed region, sharing the chip with the evaluation stream"}
         n_win_avail = U * n_seq
-        for nw in sorted({n_seq, min(512, n_win_avail)}):
+        for nw in (sorted({n_seq, min(512, n_win_avail)}) if extras else ()):
             o_ = torch.arange(nw + 1, dtype=torch.int64, device=device) * K_EVENTS
             buf = torch.empty((nw, BINS, H_, W_), dtype=torch.float32, device=device)
             st = torch.zeros((nw, 3), dtype=torch.float64, device=device)
@@ -1026,9 +1083,10 @@ def main():
             rv[f"standalone_{nw}"] = {"windows": nw, "us": round(1e3 * ms, 2), "achieved": round(g, 1), "frac": round(g / PEAK_HBM_GBS, 4),
                                       "mevents_per_s": round(nw * K_EVENTS / (ms * 1e-3) / 1e6, 1)}
             del buf, st
-        best = max((v for k, v in rv.items() if isinstance(v, dict)), key=lambda v: v["frac"])
-        rv["achieved"], rv["frac"] = best["achieved"], best["frac"]
-        out["roofline_voxelizer"] = rv
+        if any(isinstance(v, dict) for v in rv.values()):
+            best = max((v for k, v in rv.items() if isinstance(v, dict)), key=lambda v: v["frac"])
+            rv["achieved"], rv["frac"] = best["achieved"], best["frac"]
+            out["roofline_voxelizer"] = rv
 
         if side:
             # ---- small batches (the reference's regime is one sequence at a time) ----
@@ -1094,7 +1152,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
 
-    if rank == 0:
+    if rank == 0 and extras:
         # ---- score parity: the first frames of two sequences, GPU replay (THIS dispatch: same n_seq, same kernels) vs the CPU oracle;
         # ---- cpu_baseline: the oracle timed on sequence 0 (bounded: ~25 s on the default run, ~10 s beside other ranks, parity frames only in sub-runs)
         F = min(args.parity_frames, U)

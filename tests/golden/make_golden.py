@@ -460,6 +460,14 @@ def e2vid_eval_checkpoints(root, config_parser_cls):
     return out
 
 
+def make_firenetplus_ckpt():
+    """The FireNet+ checkpoint's pickle layout (legacy torch format, the reference's parse_config.ConfigParser under 'config') with its
+    tensors dropped: tests/test_dist_cpu.py checks the loader's ConfigParser shim against it."""
+    ck = torch.load(f'{REF}/pretrained/FireNet+/model.pth', map_location='cpu', weights_only=False)
+    ck = dict(ck, state_dict={}, optimizer={})
+    torch.save(ck, os.path.join(HERE, 'firenetplus_ckpt_layout.pth'), _use_new_zipfile_serialization=False)
+
+
 def make_eval_e2vid():
     import contextlib
     import utils.eval_metrics as em
@@ -655,7 +663,9 @@ def make_spade():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['voxel', 'dataset', 'helpers', 'firenet', 'e2vid', 'eval', 'eval_e2vid', 'color', 'spade', 'metrics', 'etnet']
+    which = sys.argv[1:] or ['voxel', 'dataset', 'helpers', 'firenet', 'e2vid', 'eval', 'eval_e2vid', 'color', 'spade', 'metrics', 'etnet',
+                             'firenetplus_ckpt']
     for w in which:
         {'voxel': make_voxel, 'dataset': make_dataset, 'helpers': make_helpers,
-         'firenet': make_firenet, 'e2vid': make_e2vid, 'eval': make_eval, 'eval_e2vid': make_eval_e2vid, 'color': make_color, 'spade': make_spade, 'metrics': make_metrics_published, 'etnet': make_etnet}[w]()
+         'firenet': make_firenet, 'e2vid': make_e2vid, 'eval': make_eval, 'eval_e2vid': make_eval_e2vid, 'color': make_color, 'spade': make_spade, 'metrics': make_metrics_published, 'etnet': make_etnet,
+         'firenetplus_ckpt': make_firenetplus_ckpt}[w]()

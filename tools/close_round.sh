@@ -3,7 +3,7 @@
 #  on the sha of those sources, profiles/pmc_traffic.json)
 TAG=${1:-r03f}; R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O
 db() { ls $1/*.db $1/*/*.db 2>/dev/null | head -1; }
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $O/prof -o k -- python $R/bench.py --sub > $O/bench_under_rocprof.json 2> $O/rocprof.err
 cd $R

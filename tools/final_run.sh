@@ -1,5 +1,5 @@
 R=$PWD; O=$R/gpurun_out/r03f; mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python tools/voxel_bench.py --windows 64 512 2048 > $O/voxelizer_standalone.jsonl 2>/dev/null
 python tools/voxel_bench.py --windows 64 512 --sensor 640x480 >> $O/voxelizer_standalone.jsonl 2>/dev/null
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # (bench.py --sub = headline + roofline + a 4-frame oracle comparison: no sub-runs, no small-batch passes to pollute the per-kernel averages)
 TAG=${1:-r04}
 R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; cp gpurun_out/bench_full.json $O/bench_default_full.json
+python bench.py --full --full-json $O/bench_default_full.json > $O/bench_default.json 2> $O/bench_default.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $O/prof -o k -- python $R/bench.py --sub --steps 40 > $O/bench_under_rocprof.json 2> $O/rocprof.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch -o f -- python $R/bench.py --sub --steps 4 --warmup 2 --cpu-frames 0 > $O/pmc_fetch.json 2> $O/pmc_fetch.err

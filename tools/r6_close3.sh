@@ -13,5 +13,5 @@ python tools/rocpd_pmc.py $(db $O/pmc_write) > $O/pmc_write_size.md
 python tools/make_pmc_traffic.py $(db $O/pmc_fetch) $(db $O/pmc_write) "profiles/${TAG}_pmc_fetch_size.md + ${TAG}_pmc_write_size.md" > $O/pmc_traffic.log 2>&1
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
 rm -rf $O/pmc_fetch $O/pmc_write
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; cp gpurun_out/bench_full.json $O/bench_default_full.json
+python bench.py --full --full-json $O/bench_default_full.json > $O/bench_default.json 2> $O/bench_default.err
 tail -c 400 $O/bench_default.json; echo; cat $O/pmc_traffic.json | head -c 600
