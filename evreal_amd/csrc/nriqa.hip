@@ -1,0 +1,432 @@
+// NIQE (Mittal, Soundararajan, Bovik 2013) on gfx950: the no-reference score of the reference's `-qm niqe`
+// (utils/eval_metrics.py:100-156 -> pyiqa), following the published MATLAB release (computequality.m,
+// computefeature.m, estimateaggdparam.m, estimatemodelparam.m).  Conventions (tests/nriqa_ref.py restates them):
+//   input   u = rint(255 * clip(v)) in fp32 (half to even), fp64 from here on; cropped to whole 96 x 96 blocks
+//   scale s mu = G*I, sigma = sqrt(|G*(I.I) - mu^2|), MSCN = (I - mu)/(sigma + 1); G: 7x7 Gaussian, sigma 7/6, sum 1,
+//           correlation with replicate padding, the 49 taps accumulated row by row; blocks of 96/s
+//   resize  MATLAB imresize(I, 0.5): bicubic (a = -0.5) with antialiasing = 8 taps of 0.5 * cubic(0.5 d), symmetric
+//           borders, rows first.  The taps are multiples of 2^-8 and the inputs integers <= 255: both passes are exact.
+//   fit     AGGD per block on the MSCN values and on four in-block circular pair products (shifts (0,1) (1,0) (1,1)
+//           (1,-1)); alpha = the grid point 0.2 + 0.001 k minimising (r(alpha) - r_hat_norm)^2, first on ties (NaN ->
+//           k = 0, as numpy's argmin).  Gamma is never evaluated here: the handle's table (built on the host) holds
+//           r(alpha), sqrt(G(1/a)/G(3/a)) and G(2/a)/G(1/a).
+//   score   sqrt(d' ((Sp + Sd)/2)^-1 d), d = mu_p - nanmean(rows), Sd = unbiased covariance of the NaN-free rows,
+//           by a Cholesky solve (Sp is SPD: checked at creation).
+// Launches per batch, whatever n: resize, block kernel at scale 1, block kernel at scale 2, score (features: three).
+// Every frame's arithmetic runs in work-groups of its own, each sum in a fixed order, no atomics: the results are
+// bitwise independent of the batch size and of a frame's position in the batch.
+#include "common.h"
+#include <cmath>
+#include <new>
+#include <vector>
+
+namespace {
+
+constexpr int BLK = 96;
+constexpr int NF = 36;                 // features per block: 18 per scale
+constexpr int NGRID = 9801;            // alpha = 0.2 + 0.001 k, k = 0 .. 9800
+constexpr int MAX_BLOCKS = 8192;       // blocks per frame the score kernel takes (its NaN-row flags live in LDS)
+constexpr int NT = 256;
+
+struct Taps { double g[49]; };         // the 7x7 Gaussian, row-major
+
+__device__ __forceinline__ int clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+__device__ __forceinline__ int mirror(int i, int n) { return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i); }
+
+__device__ __forceinline__ float quant(float v, int clip) {
+    if (clip) v = fminf(fmaxf(v, 0.f), 1.f);
+    return rintf(255.f * v);
+}
+
+// imresize(u, 0.5) of the cropped, quantised frame: out [n, Hc/2, Wc/2]
+__global__ __launch_bounds__(NT) void niqe_resize_kernel(const float* __restrict__ img, int H, int W, int Hc, int Wc,
+                                                         int clip, double* __restrict__ out) {
+    // 0.5 * cubic(0.5 * d) at d = 3.5, 2.5, 1.5, 0.5, -0.5, ... (they sum to 1 exactly: the per-output normalisation is a no-op)
+    const double w[8] = {-0.01171875, -0.03515625, 0.11328125, 0.43359375, 0.43359375, 0.11328125, -0.03515625, -0.01171875};
+    const int Hh = Hc / 2, Wh = Wc / 2, f = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (i >= (int64_t)Hh * Wh) return;
+    const int y = (int)(i / Wh), x = (int)(i % Wh);
+    const float* src = img + (int64_t)f * H * W;
+    int rows[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) rows[t] = mirror(2 * y - 3 + t, Hc);
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int c = mirror(2 * x - 3 + j, Wc);
+        double col = 0.0;                       // the row pass at column c
+#pragma unroll
+        for (int t = 0; t < 8; ++t) col = col + w[t] * (double)quant(src[(int64_t)rows[t] * W + c], clip);
+        acc = acc + w[j] * col;
+    }
+    out[(int64_t)f * Hh * Wh + i] = acc;
+}
+
+__device__ __forceinline__ bool better(double d, int k, double bd, int bk) { return d < bd || (d == bd && k < bk); }
+
+// One work-group per (block, frame) at one scale: MSCN on chip, the 26 block sums (5 vectors x {sum x^2 | x<0, n<0,
+// sum x^2 | x>0, n>0, sum |x|} + the sigma sum), then the five AGGD fits -> feat[f][b][scale*18 .. +18].
+// S = 96 reads the fp32 frame (quantised on load, exact in fp32); S = 48 reads the fp64 half-size image.
+template <int S, typename T>
+__global__ __launch_bounds__(NT) void niqe_block_kernel(const float* __restrict__ img, const double* __restrict__ half, int H,
+                                                        int W, int Hs, int Ws, int clip, int nbx, Taps taps,
+                                                        const double* __restrict__ table, double* __restrict__ feat,
+                                                        double* __restrict__ sharp) {
+    constexpr int TS = S + 6;
+    constexpr int NS = 26;
+    __shared__ T tile[TS][TS + 1];
+    __shared__ double m[S][S + 1];
+    __shared__ double red[NT / 64][NS];
+    __shared__ double st[NS];
+    const int b = blockIdx.x, f = blockIdx.y, nb = gridDim.x, tid = threadIdx.x;
+    const int y0 = (b / nbx) * S, x0 = (b % nbx) * S;
+
+    for (int i = tid; i < TS * TS; i += NT) {
+        const int r = i / TS, c = i % TS;
+        const int yy = clampi(y0 + r - 3, Hs), xx = clampi(x0 + c - 3, Ws);
+        if constexpr (S == BLK) tile[r][c] = quant(img[(int64_t)f * H * W + (int64_t)yy * W + xx], clip);
+        else tile[r][c] = half[(int64_t)f * Hs * Ws + (int64_t)yy * Ws + xx];
+    }
+    __syncthreads();
+
+    double ssig = 0.0;
+    for (int i = tid; i < S * S; i += NT) {
+        const int r = i / S, c = i % S;
+        double mu = 0.0, s2 = 0.0;
+#pragma unroll
+        for (int dy = 0; dy < 7; ++dy) {
+#pragma unroll
+            for (int dx = 0; dx < 7; ++dx) {
+                const double v = (double)tile[r + dy][c + dx], g = taps.g[dy * 7 + dx];
+                mu = mu + g * v;
+                s2 = s2 + g * (v * v);
+            }
+        }
+        const double sigma = sqrt(fabs(s2 - mu * mu));
+        m[r][c] = ((double)tile[r + 3][c + 3] - mu) / (sigma + 1.0);
+        ssig += sigma;
+    }
+    __syncthreads();
+
+    double a[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) a[k] = 0.0;
+    a[25] = ssig;
+    for (int i = tid; i < S * S; i += NT) {
+        const int r = i / S, c = i % S;
+        const double x = m[r][c];
+        double v[5];
+        v[0] = x;
+        v[1] = x * m[r][(c + S - 1) % S];                      // np.roll by (0, 1): m[r][c - 1]
+        v[2] = x * m[(r + S - 1) % S][c];                      // (1, 0)
+        v[3] = x * m[(r + S - 1) % S][(c + S - 1) % S];        // (1, 1)
+        v[4] = x * m[(r + S - 1) % S][(c + 1) % S];            // (1, -1)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const double q = v[k] * v[k];
+            if (v[k] < 0.0) { a[k * 5 + 0] += q; a[k * 5 + 1] += 1.0; }
+            if (v[k] > 0.0) { a[k * 5 + 2] += q; a[k * 5 + 3] += 1.0; }
+            a[k * 5 + 4] += fabs(v[k]);
+        }
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const double s = evr_wave_sum(a[k]);
+        if (lane == 0) red[wave][k] = s;
+    }
+    __syncthreads();
+    if (tid < NS) st[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    __syncthreads();
+
+    const double* R = table;
+    const double* ALPHA = table + NGRID;
+    const double* F1 = table + 2 * NGRID;
+    const double* F2 = table + 3 * NGRID;
+    const double N = (double)(S * S);
+    double* out = feat + ((int64_t)f * nb + b) * NF + (S == BLK ? 0 : 18);
+    for (int v = wave; v < 5; v += NT / 64) {      // one wave per fit
+        const double* s = st + v * 5;
+        const double ls = sqrt(s[0] / s[1]), rs = sqrt(s[2] / s[3]);     // an empty side: 0/0 = NaN
+        const double g = ls / rs;
+        const double ma = s[4] / N;
+        const double rhat = (ma * ma) / ((s[0] + s[2]) / N);
+        const double rn = (rhat * (g * g * g + 1.0) * (g + 1.0)) / ((g * g + 1.0) * (g * g + 1.0));
+        int bk = 0;
+        if (!isnan(rn)) {
+            double bd = (R[lane] - rn) * (R[lane] - rn);
+            bk = lane;
+            for (int k = lane + 64; k < NGRID; k += 64) {
+                const double d = (R[k] - rn) * (R[k] - rn);
+                if (d < bd) { bd = d; bk = k; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double od = __shfl_xor(bd, o, 64);
+                const int ok = __shfl_xor(bk, o, 64);
+                if (better(od, ok, bd, bk)) { bd = od; bk = ok; }
+            }
+        }
+        if (lane == 0) {
+            const double bl = ls * F1[bk], br = rs * F1[bk];
+            if (v == 0) {
+                out[0] = ALPHA[bk];
+                out[1] = (bl + br) / 2.0;
+            } else {
+                double* o = out + 2 + 4 * (v - 1);
+                o[0] = ALPHA[bk];
+                o[1] = (br - bl) * F2[bk];
+                o[2] = bl;
+                o[3] = br;
+            }
+        }
+    }
+    if (S == BLK && tid == 0 && sharp) sharp[(int64_t)f * nb + b] = st[25] / N;
+}
+
+// One work-group per frame: NaN-aware mean, covariance of the NaN-free rows, Cholesky of (Sp + Sd)/2, solve, sqrt.
+__global__ __launch_bounds__(NT) void niqe_score_kernel(const double* __restrict__ feat, int nb, const double* __restrict__ model,
+                                                        double* __restrict__ scores) {
+    __shared__ double A[NF][NF + 1];
+    __shared__ double mud[NF], muc[NF], y[NF];
+    __shared__ unsigned char ok[MAX_BLOCKS];
+    __shared__ int cnt[NT / 64];
+    __shared__ int bad;
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const double* F = feat + (int64_t)f * nb * NF;
+    const double* mup = model;
+    const double* covp = model + NF;
+    int c = 0;
+    for (int r = tid; r < nb; r += NT) {
+        bool full = true;
+        for (int k = 0; k < NF; ++k) full = full && !isnan(F[(int64_t)r * NF + k]);
+        ok[r] = full ? 1 : 0;
+        c += full ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((tid & 63) == 0) cnt[tid >> 6] = c;
+    if (tid == 0) bad = 0;
+    __syncthreads();
+    const int m = ((cnt[0] + cnt[1]) + cnt[2]) + cnt[3];
+    if (tid < NF) {
+        double s = 0.0, sc = 0.0;
+        int k = 0;
+        for (int r = 0; r < nb; ++r) {
+            const double v = F[(int64_t)r * NF + tid];
+            if (!isnan(v)) { s += v; ++k; }
+            if (ok[r]) sc += v;
+        }
+        mud[tid] = s / (double)k;               // no value: 0/0 = NaN
+        muc[tid] = sc / (double)m;
+    }
+    __syncthreads();
+    for (int e = tid; e < NF * NF; e += NT) {
+        const int i = e / NF, j = e % NF;
+        if (j > i) continue;
+        double s = 0.0;
+        for (int r = 0; r < nb; ++r)
+            if (ok[r]) s += (F[(int64_t)r * NF + i] - muc[i]) * (F[(int64_t)r * NF + j] - muc[j]);
+        A[i][j] = (covp[i * NF + j] + s / (double)(m - 1)) / 2.0;
+    }
+    __syncthreads();
+    // right-looking Cholesky of the lower triangle, in place
+    for (int k = 0; k < NF; ++k) {
+        if (tid == 0) {
+            const double d = A[k][k];
+            if (!(d > 0.0)) bad = 1;
+            A[k][k] = sqrt(d);
+        }
+        __syncthreads();
+        if (tid > k && tid < NF) A[tid][k] = A[tid][k] / A[k][k];
+        __syncthreads();
+        for (int e = tid; e < NF * NF; e += NT) {
+            const int i = e / NF, j = e % NF;
+            if (j > k && j <= i) A[i][j] = A[i][j] - A[i][k] * A[j][k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double q = 0.0;
+        for (int i = 0; i < NF; ++i) {
+            double s = mup[i] - mud[i];
+            for (int j = 0; j < i; ++j) s = s - A[i][j] * y[j];
+            y[i] = s / A[i][i];
+            q += y[i] * y[i];
+        }
+        scores[f] = (m < 2 || bad) ? (double)NAN : sqrt(q);
+    }
+}
+
+__global__ void niqe_nan_kernel(double* __restrict__ scores, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) scores[i] = (double)NAN;
+}
+
+Taps gaussian_taps() {
+    // fspecial('gaussian', 7, 7/6); tests/nriqa_ref.py gaussian_window() evaluates the same expressions in the same order
+    Taps t;
+    const double sig = 7.0 / 6.0;
+    for (int i = 0; i < 7; ++i)
+        for (int j = 0; j < 7; ++j) {
+            const int y = i - 3, x = j - 3;
+            t.g[i * 7 + j] = std::exp(-(double)(x * x + y * y) / (2.0 * sig * sig));
+        }
+    double s = 0.0;
+    for (int k = 0; k < 49; ++k) s += t.g[k];
+    for (int k = 0; k < 49; ++k) t.g[k] = t.g[k] / s;
+    return t;
+}
+
+struct Dims {
+    int Hc, Wc, nb, nbx;
+    size_t half_bytes, feat_bytes, sharp_bytes;
+};
+
+Dims dims(int n, int H, int W) {
+    Dims d;
+    d.Hc = (H / BLK) * BLK; d.Wc = (W / BLK) * BLK;
+    d.nbx = d.Wc / BLK;
+    d.nb = (d.Hc / BLK) * d.nbx;
+    d.half_bytes = evr::align_up((size_t)n * (d.Hc / 2) * (d.Wc / 2) * sizeof(double), 256);
+    d.feat_bytes = evr::align_up((size_t)n * d.nb * NF * sizeof(double), 256);
+    d.sharp_bytes = evr::align_up((size_t)n * d.nb * sizeof(double), 256);
+    return d;
+}
+
+}  // namespace
+
+struct evr_niqe {
+    double* d_model = nullptr;   // mu [36], cov [36*36]
+    double* d_table = nullptr;   // r(alpha), alpha, sqrt(G(1/a)/G(3/a)), G(2/a)/G(1/a): [4][9801]
+    Taps taps;
+};
+
+extern "C" int evr_niqe_create(const double* mu, const double* cov, evr_niqe** out) {
+    EVR_REQUIRE(mu && cov && out, "evr_niqe_create: null pointer");
+    *out = nullptr;
+    for (int i = 0; i < NF; ++i) EVR_REQUIRE(std::isfinite(mu[i]), "evr_niqe_create: mu[%d] is not finite", i);
+    // symmetric positive definite: a Cholesky factorisation on the host
+    std::vector<double> L(cov, cov + NF * NF);
+    for (int i = 0; i < NF; ++i)
+        for (int j = 0; j < NF; ++j)
+            EVR_REQUIRE(std::isfinite(L[i * NF + j]) && L[i * NF + j] == cov[j * NF + i], "evr_niqe_create: cov is not a finite symmetric matrix");
+    for (int k = 0; k < NF; ++k) {
+        double d = L[k * NF + k];
+        for (int p = 0; p < k; ++p) d -= L[k * NF + p] * L[k * NF + p];
+        EVR_REQUIRE(d > 0.0, "evr_niqe_create: cov is not positive definite");
+        L[k * NF + k] = std::sqrt(d);
+        for (int i = k + 1; i < NF; ++i) {
+            double s = L[i * NF + k];
+            for (int p = 0; p < k; ++p) s -= L[i * NF + p] * L[k * NF + p];
+            L[i * NF + k] = s / L[k * NF + k];
+        }
+    }
+    std::vector<double> model(NF + NF * NF), table(4 * NGRID);
+    for (int i = 0; i < NF; ++i) model[i] = mu[i];
+    for (int i = 0; i < NF * NF; ++i) model[NF + i] = cov[i];
+    for (int k = 0; k < NGRID; ++k) {
+        const double a = 0.2 + 0.001 * (double)k;
+        const double g1 = std::tgamma(1.0 / a), g2 = std::tgamma(2.0 / a), g3 = std::tgamma(3.0 / a);
+        table[k] = (g2 * g2) / (g1 * g3);
+        table[NGRID + k] = a;
+        table[2 * NGRID + k] = std::sqrt(g1 / g3);
+        table[3 * NGRID + k] = g2 / g1;
+    }
+    evr_niqe* h = new (std::nothrow) evr_niqe();
+    EVR_REQUIRE(h, "evr_niqe_create: out of host memory");
+    h->taps = gaussian_taps();
+    hipError_t e = hipMalloc((void**)&h->d_model, model.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_table, table.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(h->d_model, model.data(), model.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h->d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (h->d_model) (void)hipFree(h->d_model);
+        if (h->d_table) (void)hipFree(h->d_table);
+        delete h;
+        return evr::hip_fail(e, "evr_niqe_create", __FILE__, __LINE__);
+    }
+    *out = h;
+    return EVR_OK;
+}
+
+extern "C" int evr_niqe_destroy(evr_niqe* h) {
+    if (!h) return EVR_OK;
+    hipError_t e1 = h->d_model ? hipFree(h->d_model) : hipSuccess;
+    hipError_t e2 = h->d_table ? hipFree(h->d_table) : hipSuccess;
+    delete h;
+    EVR_HIP(e1);
+    EVR_HIP(e2);
+    return EVR_OK;
+}
+
+extern "C" size_t evr_niqe_workspace_bytes(int n, int H, int W) {
+    if (n < 0 || H < 1 || W < 1) return 0;
+    const Dims d = dims(n, H, W);
+    return d.half_bytes + d.feat_bytes + d.sharp_bytes + 256;
+}
+
+static int niqe_run(evr_niqe* h, const float* img, int n, int H, int W, int clip, double* scores, double* feat,
+                    double* sharp, void* ws, size_t ws_bytes, evr_stream_t stream_, const char* what) {
+    hipStream_t stream = (hipStream_t)stream_;
+    EVR_REQUIRE(h, "%s: null handle", what);
+    EVR_REQUIRE(n >= 0 && H >= 1 && W >= 1, "%s: bad shape", what);
+    if (n == 0) return EVR_OK;
+    EVR_REQUIRE(img && (scores || (feat && sharp)), "%s: null pointer", what);
+    const Dims d = dims(n, H, W);
+    EVR_REQUIRE(d.nb <= MAX_BLOCKS, "%s: %d blocks per frame > %d", what, d.nb, MAX_BLOCKS);
+    const size_t need = evr_niqe_workspace_bytes(n, H, W);
+    if (!ws || ws_bytes < need) {
+        evr::set_error("%s: workspace %zu B < required %zu B", what, ws_bytes, need);
+        return EVR_ERR_WORKSPACE;
+    }
+    if (d.nb == 0) {              // no whole 96 x 96 block: NaN scores, no features
+        if (scores) {
+            hipLaunchKernelGGL(niqe_nan_kernel, dim3((n + NT - 1) / NT), dim3(NT), 0, stream, scores, n);
+            EVR_LAUNCH_CHECK();
+        }
+        return EVR_OK;
+    }
+    char* p = (char*)ws;
+    double* half = (double*)p; p += d.half_bytes;
+    double* wfeat = (double*)p; p += d.feat_bytes;
+    double* wsharp = (double*)p;
+    if (!feat) feat = wfeat;
+    if (!sharp) sharp = wsharp;
+    const int Hh = d.Hc / 2, Wh = d.Wc / 2;
+    hipLaunchKernelGGL(niqe_resize_kernel, dim3((unsigned)(((int64_t)Hh * Wh + NT - 1) / NT), n), dim3(NT), 0, stream, img, H, W,
+                       d.Hc, d.Wc, clip, half);
+    EVR_LAUNCH_CHECK();
+    hipLaunchKernelGGL((niqe_block_kernel<BLK, float>), dim3(d.nb, n), dim3(NT), 0, stream, img, (const double*)nullptr, H, W,
+                       d.Hc, d.Wc, clip, d.nbx, h->taps, (const double*)h->d_table, feat, sharp);
+    EVR_LAUNCH_CHECK();
+    hipLaunchKernelGGL((niqe_block_kernel<BLK / 2, double>), dim3(d.nb, n), dim3(NT), 0, stream, (const float*)nullptr,
+                       (const double*)half, H, W, Hh, Wh, clip, d.nbx, h->taps, (const double*)h->d_table, feat, (double*)nullptr);
+    EVR_LAUNCH_CHECK();
+    if (scores) {
+        hipLaunchKernelGGL(niqe_score_kernel, dim3(n), dim3(NT), 0, stream, (const double*)feat, d.nb, (const double*)h->d_model,
+                           scores);
+        EVR_LAUNCH_CHECK();
+    }
+    return EVR_OK;
+}
+
+extern "C" int evr_niqe_score(evr_niqe* h, const float* img, int n, int H, int W, int clip, double* out_scores,
+                              void* workspace, size_t workspace_bytes, evr_stream_t stream) {
+    if (!out_scores && n > 0) {
+        evr::set_error("evr_niqe_score: null pointer");
+        return EVR_ERR_INVALID;
+    }
+    return niqe_run(h, img, n, H, W, clip, out_scores, nullptr, nullptr, workspace, workspace_bytes, stream, "evr_niqe_score");
+}
+
+extern "C" int evr_niqe_features(evr_niqe* h, const float* img, int n, int H, int W, int clip, double* out_feat,
+                                 double* out_sharpness, void* workspace, size_t workspace_bytes, evr_stream_t stream) {
+    if ((!out_feat || !out_sharpness) && n > 0) {
+        evr::set_error("evr_niqe_features: null pointer");
+        return EVR_ERR_INVALID;
+    }
+    return niqe_run(h, img, n, H, W, clip, nullptr, out_feat, out_sharpness, workspace, workspace_bytes, stream,
+                    "evr_niqe_features");
+}

@@ -8,6 +8,8 @@ Frames arrive in batches; gating (start/end time, |ref_ts-img_ts| <= ts_tol_ms, 
 Metric plug-ins keep the reference's contract (utils/eval_metrics.py:18-75): a `BaseMetric` subclass with `name`,
 `no_ref`, `calculate(img, ref) -> float | list`, `finish_queue()`, `reset()`.  Three kinds live side by side:
   * 'mse', 'ssim' and -- when a weights file is available -- 'lpips' run batched on the GPU (evr_metrics / evr_lpips_*);
+  * 'niqe' (no-reference) runs batched on the GPU (evr_niqe_*) when a pristine model file is available, and its scores are
+    booked through the four-frame queue of the reference's pyiqa metrics, so its file holds the same lines;
   * anything registered with `register_metric(name, factory)` runs per frame on host arrays, exactly like the reference's
     MseMetric / SsimMetric (clipped float32 [H,W] images in, a float or a list of floats out);
   * any other name is looked up in pyiqa.list_models() when pyiqa is importable (queued in batches of 4 as
@@ -27,6 +29,8 @@ from .prepost import Metrics, histogram_equalization
 
 GPU_METRICS = ('mse', 'ssim')
 LPIPS_WEIGHTS_ENV = 'EVREAL_LPIPS_WEIGHTS'      # path to a pyiqa/lpips AlexNet-v0.1 state_dict (torch.save'd)
+NIQE_MODEL_ENV = 'EVREAL_NIQE_MODEL'            # path to a NIQE pristine model (.mat of the MATLAB release, or .npz)
+NIQE_MODEL_FILES = (os.path.join('pretrained', 'niqe_modelparameters.mat'), os.path.join('pretrained', 'niqe_model.npz'))
 
 
 def _load_lpips():
@@ -36,6 +40,24 @@ def _load_lpips():
         return None
     from .lpips import LPIPS
     return LPIPS(torch.load(path, map_location='cpu', weights_only=False))
+
+
+def niqe_model_path():
+    """The first of $EVREAL_NIQE_MODEL, pretrained/niqe_modelparameters.mat, pretrained/niqe_model.npz that exists, or None."""
+    for path in (os.environ.get(NIQE_MODEL_ENV),) + NIQE_MODEL_FILES:
+        if path and os.path.exists(path):
+            return path
+    return None
+
+
+def _load_niqe():
+    path = niqe_model_path()
+    if path is None:
+        return None
+    from .nriqa import NIQE, load_niqe_model
+    model = load_niqe_model(path)
+    print(f"niqe: model {path} ({model['source']})")
+    return NIQE(model)
 
 
 class BaseMetric:
@@ -101,6 +123,35 @@ class GpuMetric(BaseMetric):
 
     def calculate(self, img, ref):
         raise RuntimeError(f"{self.name} is computed in batches by EvalMetricsTracker.update_batch")
+
+
+class QueuedGpuMetric(GpuMetric):
+    """A GPU metric booked as the reference books its queued pyiqa metrics (utils/eval_metrics.py:119-147, 217-223): the
+    scores of every `batch_size` evaluated frames leave together, their finite ones against the last evaluated indices; the
+    tail leaves at finalize() as it is (a non-finite tail score is kept, as the reference's finish_queue keeps it)."""
+
+    def reset(self):
+        super().reset()
+        self.pending = []
+
+    def book(self, history, indices, scores):
+        """history: the evaluated indices before this batch; -> the (index, score) lines this batch's frames release."""
+        hist, lines = list(history[-self.batch_size:]), []
+        for i, s in zip(indices, scores):
+            hist.append(i)
+            self.pending.append(float(s))
+            if len(self.pending) == self.batch_size:
+                self.add(self.pending)
+                self.pending = []
+                if self.updated:
+                    lines += zip(hist[-self.updated:], self.get_last_scores(self.updated))
+        self.updated = 0
+        return lines
+
+    def finish_queue(self):
+        self.updated = len(self.pending)
+        self.scores.extend(self.pending)
+        self.pending = []
 
 
 _REGISTRY = {}
@@ -208,6 +259,8 @@ class EvalMetricsTracker:
                 self.metrics.append(GpuMetric(name))
             elif name == 'lpips' and self._lpips_model() is not None:
                 self.metrics.append(GpuMetric(name))
+            elif name == 'niqe' and self._niqe_model() is not None:
+                self.metrics.append(QueuedGpuMetric(name, no_ref=True))
             elif name in _REGISTRY:
                 self.metrics.append(_REGISTRY[name]())
             elif name in pyiqa_metric_factory().list_of_metrics:
@@ -230,6 +283,15 @@ class EvalMetricsTracker:
                 print(f"lpips: no weights at ${LPIPS_WEIGHTS_ENV} or pretrained/lpips_alex.pth (pyiqa downloads them; "
                       "offline they must be provided) -> falling back to pyiqa if it is installed")
         return cls._lpips_cache[1]
+
+    _niqe_cache = [False, None]
+
+    @classmethod
+    def _niqe_model(cls):
+        """One NIQE model per process; None without a model file (then `niqe` goes to pyiqa, or is unknown)."""
+        if not cls._niqe_cache[0]:
+            cls._niqe_cache = [True, _load_niqe()]
+        return cls._niqe_cache[1]
 
     # -- files --------------------------------------------------------------------------------
     def reset(self):
@@ -282,8 +344,10 @@ class EvalMetricsTracker:
     def wants_precomputed(self):
         """Names of the GPU metrics a frame loop may compute for a whole chunk itself and hand to update_batch(scores=...):
         only when no histogram equalisation stands between the frames and the scores."""
-        if self.hist_eq != 'none' or self.color or not self.has_reference_frames:
+        if self.hist_eq != 'none' or self.color:
             return []
+        if not self.has_reference_frames:       # (only no-reference metrics are left: they need no reference frames)
+            return [m.name for m in self.metrics if getattr(m, 'on_gpu', False) and m.no_ref]
         return [m.name for m in self.metrics if getattr(m, 'on_gpu', False)]
 
     def update_batch(self, indices, imgs, refs, img_ts, ref_ts, scores=None, u8=None):
@@ -332,16 +396,20 @@ class EvalMetricsTracker:
             rsel = refs[js].contiguous() if refs is not None else None
         if gpu:
             want = {m.name for m in gpu}
-            scores = lp = None
+            scores = lp = nq = None
             if not have_pre:
                 if want & set(GPU_METRICS):
                     scores = self._gpu(isel, rsel, mse='mse' in want, ssim='ssim' in want, clip=True).cpu().numpy()
                 lp = self._lpips_model()(isel, rsel, clip=True).cpu().numpy() if 'lpips' in want else None
+                nq = self._niqe_model()(isel, clip=True).cpu().numpy() if 'niqe' in want else None
             for m in gpu:
                 if have_pre:
                     col = np.asarray(pre[m.name])[sel]
                 else:
-                    col = scores[:, 0] if m.name == 'mse' else scores[:, 1] if m.name == 'ssim' else lp
+                    col = scores[:, 0] if m.name == 'mse' else scores[:, 1] if m.name == 'ssim' else nq if m.name == 'niqe' else lp
+                if isinstance(m, QueuedGpuMetric):
+                    self._append(join(self.output_dir, m.name + '.txt'), m.book(self.quan_eval_indices, idxs, col))
+                    continue
                 m.add(col)
                 self._append(join(self.output_dir, m.name + '.txt'),
                              [(i, float(s)) for i, s in zip(idxs, col) if math.isfinite(s)])
@@ -460,6 +528,11 @@ class EvalMetricsTracker:
         sequence loops): the native writers keep working on this tracker's last frames while the next sequence starts; the caller
         owes a wait_all_pngs() before it reports the dataset (evreal_amd.eval does it per dataset) -- 3 ms per 160-frame sequence."""
         for m in self.metrics:
+            if isinstance(m, QueuedGpuMetric):
+                m.finish_queue()
+                self.save_new_scores(m)
+                m.updated = 0
+                continue
             if getattr(m, 'on_gpu', False):
                 m.updated = 0
                 continue

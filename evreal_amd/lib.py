@@ -77,6 +77,12 @@ SYMBOLS = {
     'evr_lpips_destroy': (c_int, [c_void_p]),
     'evr_lpips_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'evr_lpips_flops': (c_double, [c_void_p]),
+    'evr_niqe_create': (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
+    'evr_niqe_destroy': (c_int, [c_void_p]),
+    'evr_niqe_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'evr_niqe_score': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'evr_niqe_features': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
     'evr_bayer_split': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'evr_color_merge': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'evr_split_pack': (c_int, [c_void_p, c_void_p, c_int64]),

@@ -38,7 +38,7 @@ enum evr_status {
 
 /* Message for the last failure on this thread ("" if none). */
 const char* evr_last_error(void);
-/* ABI version (major*1000 + minor).  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
+/* ABI version (major*1000 + minor).  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
  * 1001 (round 4): evr_percentile_normalize rejects a NULL workspace (size it with
  * evr_percentile_normalize_workspace_bytes); evr_model_arith reports the mode the convolutions actually run (FireNet's 16-channel
  * layers: h3 whatever EVR_ARITH says). */
@@ -265,6 +265,32 @@ int evr_lpips_destroy(evr_lpips* m);
 int evr_lpips_forward(evr_lpips* m, const float* img, const float* ref, int n, int H, int W, int clip,
                       double* out, evr_stream_t stream);
 double evr_lpips_flops(const evr_lpips* m);
+
+/* ----------------------------------------------------------------------------------------------
+ * NIQE (Mittal, Soundararajan, Bovik 2013), the no-reference score of `-qm niqe` for datasets without frames
+ * (utils/eval_metrics.py:100-156 -> pyiqa), after the published MATLAB release.  Conventions (tests/nriqa_ref.py):
+ * u = rint(255 * v) in fp32 (v clamped to [0,1] first when clip != 0), fp64 from there on; the frame is cropped to whole
+ * 96 x 96 blocks from the top-left; 18 AGGD features per block at full and half size (MATLAB imresize bicubic with
+ * antialiasing); score = sqrt(d' ((Sp + Sd)/2)^-1 d).  A frame with no whole block, or fewer than 2 NaN-free block
+ * rows, scores NaN.
+ * evr_niqe_create: the pristine model, mu [36] and cov [36*36] (row-major, symmetric positive definite: refused
+ *   otherwise).  The handle owns the model and the alpha table on the device (Gamma is evaluated once, on the host).
+ * evr_niqe_score: img [n,H,W] fp32 -> out_scores double [n].
+ * evr_niqe_features: img [n,H,W] fp32 -> out_feat double [n, nb, 36] (block k in raster order of the (H/96) x (W/96)
+ *   blocks: its 18 full-size features, then its 18 half-size ones) and out_sharpness double [n, nb] (the block's mean
+ *   full-size sigma: estimatemodelparam.m's sharpness).
+ * Four launches per call whatever n (three for features), no host synchronisation; results are bitwise independent
+ * of n and of a frame's position in the batch.  workspace: evr_niqe_workspace_bytes(n, H, W); at most 8192 blocks
+ * per frame.  One handle may serve several streams at once (it holds no per-call state).
+ */
+typedef struct evr_niqe evr_niqe;
+int evr_niqe_create(const double* mu, const double* cov, evr_niqe** out);
+int evr_niqe_destroy(evr_niqe* h);
+size_t evr_niqe_workspace_bytes(int n, int H, int W);
+int evr_niqe_score(evr_niqe* h, const float* img, int n, int H, int W, int clip, double* out_scores,
+                   void* workspace, size_t workspace_bytes, evr_stream_t stream);
+int evr_niqe_features(evr_niqe* h, const float* img, int n, int H, int W, int clip, double* out_feat,
+                      double* out_sharpness, void* workspace, size_t workspace_bytes, evr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Colour reconstruction (ColorNet, model/model.py:46-105; merge utils/color_utils.py:53-88).
