@@ -95,7 +95,8 @@ bool wino_eligible(const ConvArgs& a) {
     if (a.epi == EPI_LSTM) return !tconv && a.hidden % 16 == 0 && a.cout == 4 * a.hidden;
     // (a fused 1x1 prediction layer: only where a wave's 32 columns are ALL of a pixel's channels -- the last transposed decoder; its skip
     // term is the whole skip tensor (post_add: the exact-fp32 head kernel writes no per-pixel dot product) or one float per pixel)
-    if (a.pred_w) return tconv && a.cout_total == 32 && (a.epi == EPI_BIAS || a.epi == EPI_BIAS_RELU);
+    // (the fused epilogue stores the image only: a debug copy of the decoder's own output -- a.out, debug taps -- takes the direct form)
+    if (a.pred_w) return tconv && a.cout_total == 32 && !a.out && (a.epi == EPI_BIAS || a.epi == EPI_BIAS_RELU);
     if (!a.out) return false;
     if (tconv) return a.epi == EPI_BIAS || a.epi == EPI_BIAS_RELU;
     return (a.epi == EPI_BIAS || a.epi == EPI_BIAS_RELU || a.epi == EPI_RESIDUAL_RELU) && a.cout_total == a.cout;
@@ -162,14 +163,24 @@ __global__ __launch_bounds__(256) void wino_f32_kernel(const ConvArgs* __restric
     // range of the (tile block, column block) items, column block fastest, and its blocks walk it with the stride of their count --
     // at any time the CUs of an XCD work on neighbouring tile blocks x all column blocks (shared input lines in the XCD's L2).
     // A new work-group per item cost ~10 us of launch, cold-start latency and drain per 27-us item at 128 input channels.
+    // (fewer than 8 blocks -- EVR_WINO_BLOCKS < 8 -- split the items into as many ranges as there are blocks: with 8 ranges the
+    // ranges of the XCDs that have no block were never computed)
     int item, item_end, stride;
     {
-        const int nblk = gridDim.x, bid = blockIdx.x, xcd = bid & 7;
-        const int q = total >> 3, r = total & 7;
-        const int start = xcd * q + (xcd < r ? xcd : r);
-        item_end = start + q + (xcd < r ? 1 : 0);
-        stride = (nblk - xcd + 7) >> 3;
-        item = start + (bid >> 3);
+        const int nblk = gridDim.x, bid = blockIdx.x;
+        if (nblk >= 8) {
+            const int xcd = bid & 7;
+            const int q = total >> 3, r = total & 7;
+            const int start = xcd * q + (xcd < r ? xcd : r);
+            item_end = start + q + (xcd < r ? 1 : 0);
+            stride = (nblk - xcd + 7) >> 3;
+            item = start + (bid >> 3);
+        } else {
+            const int q = total / nblk, r = total - q * nblk;
+            item = bid * q + (bid < r ? bid : r);
+            item_end = item + q + (bid < r ? 1 : 0);
+            stride = 1;
+        }
     }
     if (item >= item_end) return;
     const int c0 = a.c0;
@@ -233,7 +244,7 @@ __global__ __launch_bounds__(256) void wino_f32_kernel(const ConvArgs* __restric
         *(f2*)(vimg + (xi * 4 + 2) * 512) = R[2];
         *(f2*)(vimg + (xi * 4 + 3) * 512) = R[3];
     };
-    auto row_pass_store = [&](int xi, float4* vimg4) { row_pass_a(xi); row_pass_b(xi); row_store(xi, vimg4); };
+    auto row_pass_then_store = [&](int xi, float4* vimg4) { row_pass_a(xi); row_pass_b(xi); row_store(xi, vimg4); };
     // the 32-KB weight image of (column block cbx, chunk c): 32 lane-linear 1-KB pieces, 8 per wave (piece j of this wave)
     const unsigned u_voff = (unsigned)(lane * 16 + wv * 8192);
     auto issue_u = [&](int cbx, int c, int j, float4* ubuf) {
@@ -434,7 +445,7 @@ __global__ __launch_bounds__(256) void wino_f32_kernel(const ConvArgs* __restric
             for (int i = 0; i < 16; ++i) S[i] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rs1, poff[i], 0, 0));
         }
 #pragma unroll
-        for (int xi = 0; xi < 4; ++xi) row_pass_store(xi, ldsV0);
+        for (int xi = 0; xi < 4; ++xi) row_pass_then_store(xi, ldsV0);
         {
             const int nxt = item + stride;
             has_next = nxt < item_end;
@@ -602,7 +613,7 @@ int launch_conv_wino(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stre
     const int64_t total = ((Mt + 63) / 64) * (a.cout / 64);
     EVR_REQUIRE(total < (1LL << 31), "conv_wino: too many work items");
     // persistent blocks, one per CU (EVR_WINO_BLOCKS overrides the count); libm-grade gate activations with EVR_WINO_FASTACT=0
-    static const int nblocks = getenv("EVR_WINO_BLOCKS") ? atoi(getenv("EVR_WINO_BLOCKS")) : 256;
+    static const int nblocks = getenv("EVR_WINO_BLOCKS") && atoi(getenv("EVR_WINO_BLOCKS")) > 0 ? atoi(getenv("EVR_WINO_BLOCKS")) : 256;
     static const bool fast_act = getenv("EVR_WINO_FASTACT") ? atoi(getenv("EVR_WINO_FASTACT")) != 0 : true;
     const unsigned grid = (unsigned)(total < nblocks ? total : nblocks);
     static const int var = getenv("EVR_WINO_VAR") ? atoi(getenv("EVR_WINO_VAR")) : 0;

@@ -229,7 +229,8 @@ def _rerun_exact(model, trackers, names):
     """Saturation must not change results (the reference computes in fp32 throughout, model/submodules.py:227-245, and has no range
     limit): drain the GPU, drop what the first pass produced -- its trackers are closed, and the re-run's trackers truncate every
     file they own when they are created -- say so, and hand back the model's exact-fp32 twin (the library's fp32-MFMA HIP kernels
-    on PLAIN tensors; never the oracle, never a CPU path)."""
+    on PLAIN tensors, Winograd F(2x2, 3x3) for its 3x3, transposed and k5 stride-2 layers; held to 8x the reference's own fp32 error
+    against a float64 oracle, _HipModel.exact_twin; never the oracle, never a CPU path)."""
     torch.cuda.synchronize()
     n, layer = model.saturation(clear=True)
     for t in trackers:

@@ -97,9 +97,13 @@ class _HipModel:
         self._shape, self._needs_reset = None, True
 
     def exact_twin(self):
-        """The same network on the library's exact-fp32 HIP kernels (fp32 MFMA, PLAIN tensors: the reference's arithmetic,
-        model/submodules.py:227-245, and no range limit) -- what a sequence is re-run on when its activations left the split
-        format's range (saturation()).  Built once from the weights this model was loaded with; `self` if it already is exact."""
+        """The same network on the library's exact-fp32 HIP kernels, PLAIN tensors and no range limit -- what a sequence is re-run
+        on when its activations left the split format's range (saturation()).  fp32 MFMA throughout; the 3x3 stride-1 layers, the
+        transposed decoders and the k5 stride-2 encoders as Winograd F(2x2, 3x3) (weights transformed in fp64), the ConvLSTM gates
+        with v_exp / v_rcp activations (EVR_WINO_FASTACT=0: libm).  Not the reference's summation order: every tensor is held to
+        max(8 x the reference's own fp32 error, 2^-20 x its magnitude) against a float64 oracle (tests/test_gpu_wino.py), at unit
+        scale and with an intermediate 65536 times larger.  Built once from the weights this model was loaded with; `self` if it
+        already is exact."""
         if self.arith == 'fp32':
             return self
         if self._exact is None:

@@ -150,7 +150,9 @@ typedef struct evr_model_desc {
     int reserved[5];         /* reserved[2]: arithmetic of THIS model's convolutions, as mode + 1 (1 exact fp32, 3 "mx", 4 "h3", 5 "mx6");
                               *   0 = what EVR_ARITH / EVR_FP32 select for the process.  The reference computes in fp32
                               *   (model/submodules.py:227-245): the exact-fp32 twin is what a sequence is re-run on when its
-                              *   activations leave a split format's range (evr_model_saturation);
+                              *   activations leave a split format's range (evr_model_saturation).  It runs fp32 MFMA, Winograd
+                              *   F(2x2, 3x3) where the layer allows and v_exp / v_rcp gate activations, and is held to 8x the
+                              *   reference's own fp32 error against a float64 oracle (tests/test_gpu_wino.py);
                               * reserved[1] bit 0: use_dynamic_decoder (HyperE2VID, model/submodules.py:100-127);
                               * reserved[0] bit 0: debug -- keep every intermediate readable by
                               * evr_model_read_tensor (otherwise the last decoder's NHWC output is never

@@ -1,4 +1,4 @@
-"""Oracle: recurrent-network forward passes on torch-CPU fp32.  TEST INFRASTRUCTURE ONLY.
+"""Oracle: recurrent-network forward passes on torch-CPU fp32 (UNetRecurrentOracle also in float64: dtype=).  TEST INFRASTRUCTURE ONLY.
 
 Functional restatement (state_dict in, tensors out) of the reference's nn.Modules, NCHW:
   UNetRecurrentOracle   model/unet.py:9-143 (BaseUNet/UNetRecurrent) +
@@ -129,8 +129,11 @@ class UNetRecurrentOracle:
 
     def __init__(self, sd, num_bins=5, base_num_channels=32, num_encoders=3, num_residual_blocks=2,
                  kernel_size=5, norm=None, use_upsample_conv=False, recurrent_block_type='convlstm',
-                 final_activation='none', prefix='unetrecurrent.', use_dynamic_decoder=False):
-        self.sd = {k: v.detach().float() for k, v in sd.items()}
+                 final_activation='none', prefix='unetrecurrent.', use_dynamic_decoder=False, dtype=torch.float32):
+        # dtype=torch.float64: weights, states, prev_recs and inputs in float64 -- the high-precision reference the fp32 paths are
+        # measured against (the default float32 is the reference's own arithmetic)
+        self.dtype = dtype
+        self.sd = {k: v.detach().to(dtype) for k, v in sd.items()}
         self.pre, self.k, self.norm = prefix, kernel_size, norm
         self.num_encoders, self.num_res = num_encoders, num_residual_blocks
         self.up, self.rec = use_upsample_conv, recurrent_block_type
@@ -144,9 +147,10 @@ class UNetRecurrentOracle:
 
     def __call__(self, x, taps=None):
         sd, pre, k = self.sd, self.pre, self.k
+        x = x.to(self.dtype)
         ev_tensor = x
         if self.prev_recs is None:                 # model/model.py:139-141
-            self.prev_recs = torch.zeros(x.shape[0], 1, x.shape[2], x.shape[3])
+            self.prev_recs = torch.zeros(x.shape[0], 1, x.shape[2], x.shape[3], dtype=self.dtype)
         x = conv_layer(sd, pre + 'head', x, 1, k // 2, 'relu', None)   # head has norm=None (unet.py:77-82)
         head = x
         if taps is not None: taps['head'] = x

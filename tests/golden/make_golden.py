@@ -351,6 +351,34 @@ def make_e2vid():
                  **{'tap.' + k: (v[:, ::4].copy() if v.shape[1] >= 32 else v) for k, v in taps.items()}, **extra)
 
 
+def make_e2vid_ref64():
+    """The reference class in float64 on the e2vid_bn sequence (same seed, weights and voxels as e2vid_bn_seq.npz): pins the float64
+    mode of oracle.model.UNetRecurrentOracle, the high-precision reference of tests/test_gpu_wino.py.  Images of every frame in full;
+    the final ConvLSTM states as a [:, ::8, ::4, ::4] subsample (the whole fixture stays near 200 KB)."""
+    import copy
+    kw = weights.E2VID_KWARGS
+    schema = weights.unet_recurrent_schema(**kw)
+    m = ref_model.E2VIDRecurrent(dict(kw))
+    sd = weights.synth_state_dict(schema, seed=7)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+    m.eval()
+    m64 = copy.deepcopy(m).double()
+    m64.reset_states()
+    H, W = 64, 96
+    vox = voxel_sequence(61, 4, 5, H, W)
+    with torch.no_grad():
+        imgs = [m64(torch.from_numpy(vox[f:f + 1]).double())['image'].numpy() for f in range(len(vox))]
+    st = m64.unetrecurrent.states
+    out = {}
+    for i, (h, c) in enumerate(st):
+        assert h.dtype == torch.float64 and c.dtype == torch.float64
+        out[f'h{i}_sub'] = h.numpy()[:, ::8, ::4, ::4].copy(); out[f'c{i}_sub'] = c.numpy()[:, ::8, ::4, ::4].copy()
+    images = np.concatenate(imgs)
+    assert images.dtype == np.float64
+    save_npz('e2vid_bn_ref64.npz', voxel_sha=np.array(sha(vox)), voxel_args=np.array([61, 4, 5, H, W]), seed=np.array(7),
+             weights_sha=np.array(weights.state_dict_digest(sd)), images=images, **out)
+
+
 # ---------------------------------------------------------------- 9. the evaluation loop itself
 EVAL_SEQS = {   # name: (seed, n_events, rate_hz, W, H, fps, start_time_s, end_time_s)
     'seqA': (71, 40000, 2.0e5, 64, 48, 50.0, None, None),
@@ -663,9 +691,9 @@ def make_spade():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['voxel', 'dataset', 'helpers', 'firenet', 'e2vid', 'eval', 'eval_e2vid', 'color', 'spade', 'metrics', 'etnet',
+    which = sys.argv[1:] or ['voxel', 'dataset', 'helpers', 'firenet', 'e2vid', 'e2vid_ref64', 'eval', 'eval_e2vid', 'color', 'spade', 'metrics', 'etnet',
                              'firenetplus_ckpt']
     for w in which:
         {'voxel': make_voxel, 'dataset': make_dataset, 'helpers': make_helpers,
-         'firenet': make_firenet, 'e2vid': make_e2vid, 'eval': make_eval, 'eval_e2vid': make_eval_e2vid, 'color': make_color, 'spade': make_spade, 'metrics': make_metrics_published, 'etnet': make_etnet,
+         'firenet': make_firenet, 'e2vid': make_e2vid, 'e2vid_ref64': make_e2vid_ref64, 'eval': make_eval, 'eval_e2vid': make_eval_e2vid, 'color': make_color, 'spade': make_spade, 'metrics': make_metrics_published, 'etnet': make_etnet,
          'firenetplus_ckpt': make_firenetplus_ckpt}[w]()

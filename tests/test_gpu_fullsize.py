@@ -50,8 +50,10 @@ def _d(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _run(m, o, H, W, num_encoders, frames, n_seq, n_events, seed0, normalize=True, check_states=False, oracle_seqs=None):
-    """oracle_seqs: the sequences replayed through the CPU oracle (default: all; the GPU always advances all n_seq together)."""
+def _run(m, o, H, W, num_encoders, frames, n_seq, n_events, seed0, normalize=True, check_states=False, oracle_seqs=None, o64=None):
+    """oracle_seqs: the sequences replayed through the CPU oracle (default: all; the GPU always advances all n_seq together).
+    o64: the same oracle in float64, replayed on the first of them; then the return value is (worst, report) where report lists, per
+    compared tensor, (name, e_gpu, e_32, max|T_64|) with e_gpu = max|T_gpu - T_64| and e_32 = max|T_32 - T_64| (tests/test_gpu_wino.py)."""
     from evreal_amd.voxel import Voxelizer
     from oracle import prepost as op, voxel as ov
     crop = op.CropParams(W, H, num_encoders)
@@ -60,6 +62,13 @@ def _run(m, o, H, W, num_encoders, frames, n_seq, n_events, seed0, normalize=Tru
     m.reset_states(); o.reset_states()
     sel = list(range(n_seq)) if oracle_seqs is None else list(oracle_seqs)
     worst = 0.0
+    report = []
+    if o64 is not None:
+        o64.reset_states()
+
+    def cmp64(name, got, t32, t64):
+        report.append((name, float(np.abs(got.astype(np.float64) - t64).max()), float(np.abs(t32.astype(np.float64) - t64).max()),
+                       float(np.abs(t64).max())))
     for f in range(frames):
         ev, cat, offs = _windows([seed0 + 1000 * f + s for s in range(n_seq)], n_events, W, H)
         g = vz.voxelize(_d(cat[0]), _d(cat[1]), _d(cat[2]), _d(cat[3]), _d(offs), 5, (H, W), stats=st)
@@ -72,6 +81,10 @@ def _run(m, o, H, W, num_encoders, frames, n_seq, n_events, seed0, normalize=Tru
         err = float(np.abs(img[sel] - want).max())
         worst = max(worst, err)
         assert err < IMG_ATOL, (f, err)
+        if o64 is not None:
+            with torch.no_grad():
+                want64 = crop.crop(o64(torch.from_numpy(crop.pad(v[:1]))).numpy())
+            cmp64(f'img{f}', img[sel[0]:sel[0] + 1], want[:1], want64)
     if check_states:
         for i in range(num_encoders):
             shp = (n_seq,) + tuple(o.states[i][0].shape[1:])
@@ -79,7 +92,10 @@ def _run(m, o, H, W, num_encoders, frames, n_seq, n_events, seed0, normalize=Tru
             c = m.read_tensor(f'c{i}').cpu().numpy().reshape(shp)[sel]
             np.testing.assert_allclose(h, o.states[i][0].numpy(), rtol=2e-4, atol=5e-5, err_msg=f'h{i}')
             np.testing.assert_allclose(c, o.states[i][1].numpy(), rtol=2e-4, atol=5e-5, err_msg=f'c{i}')
-    return worst
+            if o64 is not None:
+                cmp64(f'h{i}', h[:1], o.states[i][0].numpy()[:1], o64.states[i][0].numpy())
+                cmp64(f'c{i}', c[:1], o.states[i][1].numpy()[:1], o64.states[i][1].numpy())
+    return worst if o64 is None else (worst, report)
 
 
 def test_drift_100_frames_346x260_8_sequences():
@@ -104,14 +120,23 @@ def test_exact_fp32_twin_winograd_346x260():
     m, o = _pair(dict(weights.E2VID_KWARGS), seed=23)
     twin = m.exact_twin()
     assert twin.arith == 'fp32'
+    from oracle import model as omod
+    o64 = omod.UNetRecurrentOracle(dict(o.sd), **{k: dict(weights.E2VID_KWARGS)[k] for k in OKEYS}, dtype=torch.float64)
     global IMG_ATOL
     keep, IMG_ATOL = IMG_ATOL, 1e-4
     try:
-        worst = _run(twin, o, 260, 346, 3, frames=20, n_seq=3, n_events=15000, seed0=70000, check_states=True)
+        worst, report = _run(twin, o, 260, 346, 3, frames=20, n_seq=3, n_events=15000, seed0=70000, check_states=True, o64=o64)
     finally:
         IMG_ATOL = keep
     print(f'exact-fp32 twin (Winograd {os.environ.get("EVR_WINO", "on")}), 20 frames x 3 sequences: worst per-pixel error {worst:.2e}')
     assert worst < 2e-5, worst      # measured 1e-6-class; a wrong tile or weight position is 1e-1
+    # sequence 0 against the float64 oracle: e_gpu <= max(8 e_32, 2^-20 max|T_64|), the bound of tests/test_gpu_wino.py
+    bad = []
+    for name, e_gpu, e_32, s in report:
+        print(f'  float64 oracle, sequence 0, {name:6s}: e_gpu {e_gpu:.3e}  e_32 {e_32:.3e}  ratio {e_gpu / max(e_32, 1e-300):.2f}')
+        if not e_gpu <= max(8.0 * e_32, 2.0 ** -20 * s):
+            bad.append((name, e_gpu, e_32, s))
+    assert len(report) == 20 + 6 and not bad, bad
 
 
 def test_one_sequence_split_k_100_frames_346x260():

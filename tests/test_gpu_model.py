@@ -335,7 +335,9 @@ def test_large_activations_are_reported_not_silent():
     from |x| ~ 256 on (the value then keeps only its f16 half, 2^-12 relative), H2 (EVR_ARITH=h3) clamps at +-4094, P6 (the default for
     this layout) scales every 16-channel group by its own maximum and only clamps beyond the half-precision range.  Inputs 30x the
     usual magnitude stay inside and pass the gate with a zero counter; at 300x and beyond every frame EITHER still passes
-    1e-4 OR evr_model_saturation reports the excursion (so the degradation is never silent); results stay finite."""
+    1e-4 OR evr_model_saturation reports the excursion (so the degradation is never silent); results stay finite.  The exact-fp32 twin
+    (what evaluate() re-runs such sequences on; the model itself under EVR_FP32=1) also holds the float64 bound of tests/test_gpu_wino.py
+    at every scale: e_twin <= max(8 e_32, 2^-20 max|img_64|), e_32 = the fp32 oracle's own distance to the float64 oracle."""
     from evreal_amd import model, weights
     from oracle import model as omod
     kw = dict(weights.E2VID_KWARGS)
@@ -344,12 +346,16 @@ def test_large_activations_are_reported_not_silent():
     okeys = ['num_bins', 'base_num_channels', 'num_encoders', 'num_residual_blocks', 'kernel_size', 'norm', 'use_upsample_conv',
              'recurrent_block_type', 'final_activation']
     o = omod.UNetRecurrentOracle({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, **{k: kw[k] for k in okeys})
+    o64 = omod.UNetRecurrentOracle({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, **{k: kw[k] for k in okeys},
+                                   dtype=torch.float64)
+    twin = m.exact_twin()
     rng = np.random.default_rng(0)
     exact = bool(os.environ.get('EVR_FP32')) or os.environ.get('EVR_ARITH') == 'fp32'
     for scale in (30.0, 300.0, 1e5):
-        m.reset_states(); o.reset_states()
-        m.saturation(clear=True)
+        m.reset_states(); o.reset_states(); o64.reset_states(); twin.reset_states()
+        m.saturation(clear=True); twin.saturation(clear=True)
         worst = 0.0
+        e_twin = e_32 = s64 = 0.0
         for f in range(3):
             v = np.zeros((1, 5, 64, 96), np.float32)
             mk = rng.random(v.shape) < 0.2
@@ -359,6 +365,15 @@ def test_large_activations_are_reported_not_silent():
                 want = o(torch.from_numpy(v)).numpy()
             assert np.isfinite(img).all()
             worst = max(worst, float(np.abs(img - want).max()))
+            with torch.no_grad():
+                want64 = o64(torch.from_numpy(v)).numpy()
+            timg = img if twin is m else twin(torch.from_numpy(v).cuda())['image'].cpu().numpy()
+            e_twin = max(e_twin, float(np.abs(timg.astype(np.float64) - want64).max()))
+            e_32 = max(e_32, float(np.abs(want.astype(np.float64) - want64).max()))
+            s64 = max(s64, float(np.abs(want64).max()))
+        print(f'scale {scale:g}: exact twin vs float64 {e_twin:.3e}, fp32 oracle vs float64 {e_32:.3e}, ratio {e_twin / max(e_32, 1e-300):.2f}')
+        assert e_twin <= max(8.0 * e_32, 2.0 ** -20 * s64), (scale, e_twin, e_32, s64)
+        assert twin.saturation()[0] == 0, scale
         runs, layer = m.saturation()
         loose = {30.0: 1e-4, 300.0: 1e-3, 1e5: 5e-2}[scale]      # fp32 itself: summation-order differences grow with the magnitude
         if exact:

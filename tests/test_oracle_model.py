@@ -149,3 +149,45 @@ def test_etnet_oracle_golden(norm, tag):
     for i, (h, c) in enumerate(m.states):
         np.testing.assert_allclose(h.numpy()[:, ::4], z[f'h{i}_sub'], rtol=1e-4, atol=1e-5, err_msg=f'h{i}')
         np.testing.assert_allclose(c.numpy()[:, ::4], z[f'c{i}_sub'], rtol=1e-4, atol=1e-5, err_msg=f'c{i}')
+
+
+def test_e2vid_bn_float64_oracle_matches_the_reference_in_float64():
+    """UNetRecurrentOracle(dtype=torch.float64) against the reference class run in float64 (copy.deepcopy(m).double(),
+    tests/golden/make_golden.py make_e2vid_ref64) on the e2vid_bn sequence: images of every frame and the final ConvLSTM states
+    to float64 level.  tests/test_gpu_wino.py measures the exact-fp32 kernels against this oracle without the reference."""
+    z = load_npz('e2vid_bn_ref64.npz')
+    kw = weights.E2VID_KWARGS
+    sd = weights.synth_state_dict(weights.unet_recurrent_schema(**kw), seed=int(z['seed']))
+    assert weights.state_dict_digest(sd) == str(z['weights_sha'])
+    okw = {k: kw[k] for k in ['num_bins', 'base_num_channels', 'num_encoders', 'num_residual_blocks', 'kernel_size',
+                              'norm', 'use_upsample_conv', 'recurrent_block_type', 'final_activation']}
+    m = omod.UNetRecurrentOracle({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, **okw, dtype=torch.float64)
+    seed, F, B, H, W = [int(v) for v in z['voxel_args']]
+    vox = synth.sparse_voxels(seed, F, B, H, W)
+    assert sha(vox) == str(z['voxel_sha'])
+    m32 = omod.UNetRecurrentOracle({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, **okw)
+    spread = 0.0
+    for f in range(F):
+        x = torch.from_numpy(vox[f:f + 1])
+        img = m(x)
+        assert img.dtype == torch.float64 and m.prev_recs.dtype == torch.float64
+        np.testing.assert_allclose(img.numpy(), z['images'][f:f + 1], rtol=0, atol=1e-12, err_msg=f'frame {f}')
+        spread = max(spread, float(np.abs(m32(x).numpy() - z['images'][f:f + 1]).max()))
+    for i, (h, c) in enumerate(m.states):
+        assert h.dtype == torch.float64 and c.dtype == torch.float64
+        np.testing.assert_allclose(h.numpy()[:, ::8, ::4, ::4], z[f'h{i}_sub'], rtol=0, atol=1e-12, err_msg=f'h{i}')
+        np.testing.assert_allclose(c.numpy()[:, ::8, ::4, ::4], z[f'c{i}_sub'], rtol=0, atol=1e-12, err_msg=f'c{i}')
+    # the fixture is float64 and not a copy of the fp32 golden: the fp32 oracle differs from it by its own rounding
+    assert 0.0 < spread < 1e-5, spread
+
+
+def test_float64_oracle_default_is_the_fp32_oracle():
+    """dtype defaults to float32: the oracle every other test uses is unchanged (weights, zero states and prev_recs fp32)."""
+    kw = weights.E2VID_KWARGS
+    sd = weights.synth_state_dict(weights.unet_recurrent_schema(**kw), seed=3)
+    okw = {k: kw[k] for k in ['num_bins', 'base_num_channels', 'num_encoders', 'num_residual_blocks', 'kernel_size',
+                              'norm', 'use_upsample_conv', 'recurrent_block_type', 'final_activation']}
+    m = omod.UNetRecurrentOracle({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, **okw)
+    assert m.dtype == torch.float32 and all(v.dtype == torch.float32 for v in m.sd.values())
+    out = m(torch.from_numpy(synth.sparse_voxels(4, 1, 5, 16, 24)))
+    assert out.dtype == torch.float32 and m.prev_recs.dtype == torch.float32 and m.states[0][1].dtype == torch.float32
