@@ -31,19 +31,24 @@ constexpr int NT = 256;
 struct Taps { double g[49]; };         // the 7x7 Gaussian, row-major
 
 __device__ __forceinline__ int clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-__device__ __forceinline__ int mirror(int i, int n) { return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i); }
+// symmetric (half-sample) reflection, repeated for an index more than one length outside (a side shorter than 4)
+__device__ __forceinline__ int mirror(int i, int n) {
+    i %= 2 * n;
+    if (i < 0) i += 2 * n;
+    return i < n ? i : 2 * n - 1 - i;
+}
 
 __device__ __forceinline__ float quant(float v, int clip) {
     if (clip) v = fminf(fmaxf(v, 0.f), 1.f);
     return rintf(255.f * v);
 }
 
-// imresize(u, 0.5) of the cropped, quantised frame: out [n, Hc/2, Wc/2]
+// imresize(u, 0.5) of the cropped (NIQE) or whole (BRISQUE) quantised frame: out [n, ceil(Hc/2), ceil(Wc/2)]
 __global__ __launch_bounds__(NT) void niqe_resize_kernel(const float* __restrict__ img, int H, int W, int Hc, int Wc,
                                                          int clip, double* __restrict__ out) {
     // 0.5 * cubic(0.5 * d) at d = 3.5, 2.5, 1.5, 0.5, -0.5, ... (they sum to 1 exactly: the per-output normalisation is a no-op)
     const double w[8] = {-0.01171875, -0.03515625, 0.11328125, 0.43359375, 0.43359375, 0.11328125, -0.03515625, -0.01171875};
-    const int Hh = Hc / 2, Wh = Wc / 2, f = blockIdx.y;
+    const int Hh = (Hc + 1) / 2, Wh = (Wc + 1) / 2, f = blockIdx.y;
     const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
     if (i >= (int64_t)Hh * Wh) return;
     const int y = (int)(i / Wh), x = (int)(i % Wh);
@@ -279,6 +284,22 @@ Taps gaussian_taps() {
     return t;
 }
 
+// The alpha grid's columns, Gamma evaluated once on the host: r(alpha) = G(2/a)^2/(G(1/a)G(3/a)) (the AGGD ratio), alpha,
+// sqrt(G(1/a)/G(3/a)), G(2/a)/G(1/a), and with cols = 5 the GGD ratio G(1/a)G(3/a)/G(2/a)^2.  [cols][NGRID]
+std::vector<double> alpha_table(int cols) {
+    std::vector<double> table((size_t)cols * NGRID);
+    for (int k = 0; k < NGRID; ++k) {
+        const double a = 0.2 + 0.001 * (double)k;
+        const double g1 = std::tgamma(1.0 / a), g2 = std::tgamma(2.0 / a), g3 = std::tgamma(3.0 / a);
+        table[k] = (g2 * g2) / (g1 * g3);
+        table[NGRID + k] = a;
+        table[2 * NGRID + k] = std::sqrt(g1 / g3);
+        table[3 * NGRID + k] = g2 / g1;
+        if (cols > 4) table[4 * NGRID + k] = (g1 * g3) / (g2 * g2);
+    }
+    return table;
+}
+
 struct Dims {
     int Hc, Wc, nb, nbx;
     size_t half_bytes, feat_bytes, sharp_bytes;
@@ -323,17 +344,10 @@ extern "C" int evr_niqe_create(const double* mu, const double* cov, evr_niqe** o
             L[i * NF + k] = s / L[k * NF + k];
         }
     }
-    std::vector<double> model(NF + NF * NF), table(4 * NGRID);
+    std::vector<double> model(NF + NF * NF);
     for (int i = 0; i < NF; ++i) model[i] = mu[i];
     for (int i = 0; i < NF * NF; ++i) model[NF + i] = cov[i];
-    for (int k = 0; k < NGRID; ++k) {
-        const double a = 0.2 + 0.001 * (double)k;
-        const double g1 = std::tgamma(1.0 / a), g2 = std::tgamma(2.0 / a), g3 = std::tgamma(3.0 / a);
-        table[k] = (g2 * g2) / (g1 * g3);
-        table[NGRID + k] = a;
-        table[2 * NGRID + k] = std::sqrt(g1 / g3);
-        table[3 * NGRID + k] = g2 / g1;
-    }
+    const std::vector<double> table = alpha_table(4);
     evr_niqe* h = new (std::nothrow) evr_niqe();
     EVR_REQUIRE(h, "evr_niqe_create: out of host memory");
     h->taps = gaussian_taps();
@@ -429,4 +443,376 @@ extern "C" int evr_niqe_features(evr_niqe* h, const float* img, int n, int H, in
     }
     return niqe_run(h, img, n, H, W, clip, nullptr, out_feat, out_sharpness, workspace, workspace_bytes, stream,
                     "evr_niqe_features");
+}
+
+// =====================================================================================================================
+// BRISQUE (Mittal, Moorthy, Bovik 2012): the no-reference score of the reference's `-qm brisque` (-> pyiqa), following the
+// published MATLAB release (brisquescore.m, brisque_feature.m, estimateggdparam.m, estimateaggdparam.m) and libsvm's
+// svm-scale -r / svm-predict.  Conventions (tests/brisque_ref.py states them in the same words):
+//   input     u = rint(255 * clip(v)) in fp32 (half to even), fp64 from here on; no crop: the whole frame is used
+//   MSCN      at each of two scales: mu = filter2(w, I, 'same'), sigma = sqrt(|filter2(w, I.*I) - mu^2|),
+//             M = (I - mu)/(sigma + 1); w: 7x7 Gaussian, sigma 7/6, sum 1; ZERO padding; the 49 taps accumulated row by row
+//   resize    MATLAB imresize(I, 0.5), bicubic, antialiased, symmetric borders: ceil(H/2) x ceil(W/2)
+//   features  18 per scale, 36 in all, scale 1 first.  GGD fit of all of M: rho = mean(M^2)/mean(|M|)^2, alpha = the grid
+//             point 0.2 + 0.001 k minimising |rho - G(1/a)G(3/a)/G(2/a)^2| -> [alpha, mean(M^2)].  For each circshift
+//             (0,1) (1,0) (1,1) (-1,1) of the whole frame (wrapping at its edges), the AGGD fit of P = M . circshift(M, s)
+//             (NIQE's estimateaggdparam) -> [alpha, (sr - sl) G(2/a)/G(1/a) sqrt(G(1/a)/G(3/a)), sl^2, sr^2].  Every grid
+//             search takes the first point on ties; a NaN ratio takes k = 0 (numpy's argmin); an empty AGGD side is NaN.
+//   scaling   svm-scale: x' = lower + (upper - lower)(x - min)/(max - min); x == min -> lower, x == max -> upper; a feature
+//             whose range has min == max is dropped (0 in the sparse vector)
+//   score     RBF SVR: sum_i coef_i exp(-gamma |x' - sv_i|^2) - rho, |.|^2 a sum of squared differences in feature order.
+//             A frame with any NaN feature scores NaN (a flat frame is one).  Nothing goes through the release's %f / %g
+//             text round trips: fp64 throughout.
+// Launches per batch, whatever n: resize, statistics kernel at scale 1, statistics kernel at scale 2, finisher.  The
+// statistics kernels run one work-group per (32 x 32 tile, frame) and write the tile's 26 partial sums; the finisher runs
+// one work-group per frame and adds them in tile order.  No atomics: results are bitwise independent of the batch.
+
+namespace {
+
+constexpr int BT = 32;                 // statistics tile: BT x BT pixels per work-group
+constexpr int BNS = 26;                // partial sums per tile: sum M^2, sum |M|, then per shift the six below
+
+__device__ __forceinline__ float load_px(const float* p, int64_t i, int clip) { return quant(p[i], clip); }
+__device__ __forceinline__ double load_px(const double* p, int64_t i, int) { return p[i]; }
+__device__ __forceinline__ int wrap(int i, int n) { i %= n; return i < 0 ? i + n : i; }
+
+// M at one pixel from its 7x7 neighbourhood get(dy, dx), taps accumulated row by row (the oracle's order)
+template <typename Get>
+__device__ __forceinline__ double mscn_at(const Taps& taps, double centre, Get get) {
+    double mu = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int dy = 0; dy < 7; ++dy) {
+#pragma unroll
+        for (int dx = 0; dx < 7; ++dx) {
+            const double v = get(dy, dx), g = taps.g[dy * 7 + dx];
+            mu = mu + g * v;
+            s2 = s2 + g * (v * v);
+        }
+    }
+    const double sigma = sqrt(fabs(s2 - mu * mu));
+    return (centre - mu) / (sigma + 1.0);
+}
+
+// One work-group per (tile, frame) at one scale.  The tile's input and a 4-pixel zero-padded halo are staged in LDS; M is
+// computed on chip for the tile plus the row above, the row below and the column to the left (the pairs' neighbours).
+// Where one of those lies outside the frame it is the wrapped row or column at the other edge, whose neighbourhood is
+// read from memory.  -> part[f][t][26]: sum M^2, sum |M|, then for the shifts (0,1) (1,0) (1,1) (-1,1):
+// sum P^2 | P<0, n<0, sum P^2 | P>0, n>0, sum |P|, sum P^2.
+// T = float reads the fp32 frame (quantised on load, exact in fp32); T = double reads the fp64 half-size image.
+template <typename T>
+__global__ __launch_bounds__(NT) void brisque_stats_kernel(const T* __restrict__ src, int Hs, int Ws, int clip, int ntx,
+                                                           Taps taps, double* __restrict__ part) {
+    constexpr int TR = BT + 8, TC = BT + 7;     // input rows y0-4 .. y0+BT+3, columns x0-4 .. x0+BT+2
+    constexpr int MR = BT + 2, MC = BT + 1;     // M rows y0-1 .. y0+BT, columns x0-1 .. x0+BT-1
+    __shared__ T tile[TR][TC + 1];
+    __shared__ double m[MR][MC];
+    __shared__ double red[NT / 64][BNS];
+    const int t = blockIdx.x, f = blockIdx.y, nt = gridDim.x, tid = threadIdx.x;
+    const int y0 = (t / ntx) * BT, x0 = (t % ntx) * BT;
+    const T* img = src + (int64_t)f * Hs * Ws;
+
+    for (int i = tid; i < TR * TC; i += NT) {
+        const int r = i / TC, c = i % TC;
+        const int yy = y0 + r - 4, xx = x0 + c - 4;
+        tile[r][c] = (yy >= 0 && yy < Hs && xx >= 0 && xx < Ws) ? load_px(img, (int64_t)yy * Ws + xx, clip) : (T)0;
+    }
+    __syncthreads();
+
+    for (int i = tid; i < MR * MC; i += NT) {
+        const int r = i / MC, c = i % MC;
+        const int gy = y0 + r - 1, gx = x0 + c - 1;
+        double v = 0.0;
+        if (gy >= 0 && gy < Hs && gx >= 0 && gx < Ws) {
+            // tile[r + dy][c + dx] holds the input at (gy + dy - 3, gx + dx - 3), zero outside the frame
+            v = mscn_at(taps, (double)tile[r + 3][c + 3], [&](int dy, int dx) { return (double)tile[r + dy][c + dx]; });
+        } else if (gy >= -1 && gy <= Hs && gx >= -1 && gx < Ws) {
+            // a neighbour across the frame's edge: the pixel at the other side, its zero-padded neighbourhood from memory
+            const int wy = wrap(gy, Hs), wx = wrap(gx, Ws);
+            auto get = [&](int dy, int dx) {
+                const int yy = wy + dy - 3, xx = wx + dx - 3;
+                return (yy >= 0 && yy < Hs && xx >= 0 && xx < Ws) ? (double)load_px(img, (int64_t)yy * Ws + xx, clip) : 0.0;
+            };
+            v = mscn_at(taps, get(3, 3), get);
+        }
+        m[r][c] = v;
+    }
+    __syncthreads();
+
+    double a[BNS];
+#pragma unroll
+    for (int k = 0; k < BNS; ++k) a[k] = 0.0;
+    for (int i = tid; i < BT * BT; i += NT) {
+        const int r = i / BT + 1, c = i % BT + 1;              // (r, c) in m: the pixel (y0 + r - 1, x0 + c - 1)
+        if (y0 + r - 1 >= Hs || x0 + c - 1 >= Ws) continue;
+        const double x = m[r][c];
+        a[0] += x * x;
+        a[1] += fabs(x);
+        double v[4];
+        v[0] = x * m[r][c - 1];                                 // circshift by (0, 1): M(y, x - 1)
+        v[1] = x * m[r - 1][c];                                 // (1, 0): M(y - 1, x)
+        v[2] = x * m[r - 1][c - 1];                             // (1, 1): M(y - 1, x - 1)
+        v[3] = x * m[r + 1][c - 1];                             // (-1, 1): M(y + 1, x - 1)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double q = v[k] * v[k];
+            if (v[k] < 0.0) { a[2 + 6 * k + 0] += q; a[2 + 6 * k + 1] += 1.0; }
+            if (v[k] > 0.0) { a[2 + 6 * k + 2] += q; a[2 + 6 * k + 3] += 1.0; }
+            a[2 + 6 * k + 4] += fabs(v[k]);
+            a[2 + 6 * k + 5] += q;
+        }
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < BNS; ++k) {
+        const double s = evr_wave_sum(a[k]);
+        if (lane == 0) red[wave][k] = s;
+    }
+    __syncthreads();
+    if (tid < BNS) part[((int64_t)f * nt + t) * BNS + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+struct SvrParams { int nsv; double gamma, rho, lower, upper; };
+
+// One work-group per frame: the tile sums in tile order, the 2 x (1 GGD + 4 AGGD) fits (one wave per fit), the 36
+// features, svm-scale and the SVR.  model: fmin [36], fmax [36], coef [nsv], sv [nsv][36].
+__global__ __launch_bounds__(NT) void brisque_finish_kernel(const double* __restrict__ part1, int nt1, int N1,
+                                                            const double* __restrict__ part2, int nt2, int N2,
+                                                            const double* __restrict__ table, const double* __restrict__ model,
+                                                            SvrParams svr, double* __restrict__ feat, double* __restrict__ scores) {
+    __shared__ double st[2][BNS];
+    __shared__ double fe[NF], xs[NF];
+    __shared__ double red[NT / 64];
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 2 * BNS) {
+        const int s = tid / BNS, k = tid % BNS, nt = s ? nt2 : nt1;
+        const double* p = (s ? part2 : part1) + (int64_t)f * nt * BNS + k;
+        double sum = 0.0;
+        for (int t = 0; t < nt; ++t) sum += p[(int64_t)t * BNS];
+        st[s][k] = sum;
+    }
+    __syncthreads();
+
+    const double* R = table;
+    const double* ALPHA = table + NGRID;
+    const double* F1 = table + 2 * NGRID;
+    const double* F2 = table + 3 * NGRID;
+    const double* RG = table + 4 * NGRID;
+    for (int v = wave; v < 10; v += NT / 64) {                 // one wave per fit
+        const int sc = v / 5, j = v % 5;
+        const double* S = st[sc];
+        const double N = (double)(sc ? N2 : N1);
+        double rn, ls = 0.0, rs = 0.0, msq = 0.0;
+        if (j == 0) {
+            msq = S[0] / N;
+            const double ma = S[1] / N;
+            rn = msq / (ma * ma);
+        } else {
+            const double* s = S + 2 + 6 * (j - 1);
+            ls = sqrt(s[0] / s[1]);                             // an empty side: 0/0 = NaN
+            rs = sqrt(s[2] / s[3]);
+            const double g = ls / rs;
+            const double ma = s[4] / N;
+            const double rhat = (ma * ma) / (s[5] / N);
+            rn = (rhat * (g * g * g + 1.0) * (g + 1.0)) / ((g * g + 1.0) * (g * g + 1.0));
+        }
+        int bk = 0;
+        if (!isnan(rn)) {
+            auto dist = [&](int k) { return j == 0 ? fabs(rn - RG[k]) : (R[k] - rn) * (R[k] - rn); };
+            double bd = dist(lane);
+            bk = lane;
+            for (int k = lane + 64; k < NGRID; k += 64) {
+                const double d = dist(k);
+                if (d < bd) { bd = d; bk = k; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double od = __shfl_xor(bd, o, 64);
+                const int ok = __shfl_xor(bk, o, 64);
+                if (better(od, ok, bd, bk)) { bd = od; bk = ok; }
+            }
+        }
+        if (lane == 0) {
+            double* o = fe + 18 * sc;
+            if (j == 0) {
+                o[0] = ALPHA[bk];
+                o[1] = msq;
+            } else {
+                o += 2 + 4 * (j - 1);
+                o[0] = ALPHA[bk];
+                o[1] = ((rs - ls) * F2[bk]) * F1[bk];
+                o[2] = ls * ls;
+                o[3] = rs * rs;
+            }
+        }
+    }
+    __syncthreads();
+    if (feat && tid < NF) feat[(int64_t)f * NF + tid] = fe[tid];
+    if (!scores) return;
+
+    if (tid < NF) {                                             // svm-scale
+        const double x = fe[tid], lo = model[tid], hi = model[NF + tid];
+        double y;
+        if (lo == hi) y = 0.0;
+        else if (x == lo) y = svr.lower;
+        else if (x == hi) y = svr.upper;
+        else y = svr.lower + ((svr.upper - svr.lower) * (x - lo)) / (hi - lo);
+        xs[tid] = y;
+    }
+    __syncthreads();
+    const double* coef = model + 2 * NF;
+    const double* sv = coef + svr.nsv;
+    double acc = 0.0;
+    for (int i = tid; i < svr.nsv; i += NT) {
+        double d = 0.0;
+        for (int k = 0; k < NF; ++k) {
+            const double e = xs[k] - sv[(int64_t)i * NF + k];
+            d = d + e * e;
+        }
+        acc = acc + coef[i] * exp(-svr.gamma * d);
+    }
+    acc = evr_wave_sum(acc);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        bool nan = false;
+        for (int k = 0; k < NF; ++k) nan = nan || isnan(fe[k]);
+        scores[f] = nan ? (double)NAN : (((red[0] + red[1]) + red[2]) + red[3]) - svr.rho;
+    }
+}
+
+struct BDims {
+    int Hh, Wh, ntx1, nt1, ntx2, nt2;
+    size_t half_bytes, part1_bytes, part2_bytes;
+};
+
+BDims bdims(int n, int H, int W) {
+    BDims d;
+    d.Hh = (H + 1) / 2; d.Wh = (W + 1) / 2;
+    d.ntx1 = (W + BT - 1) / BT;
+    d.nt1 = ((H + BT - 1) / BT) * d.ntx1;
+    d.ntx2 = (d.Wh + BT - 1) / BT;
+    d.nt2 = ((d.Hh + BT - 1) / BT) * d.ntx2;
+    d.half_bytes = evr::align_up((size_t)n * d.Hh * d.Wh * sizeof(double), 256);
+    d.part1_bytes = evr::align_up((size_t)n * d.nt1 * BNS * sizeof(double), 256);
+    d.part2_bytes = evr::align_up((size_t)n * d.nt2 * BNS * sizeof(double), 256);
+    return d;
+}
+
+}  // namespace
+
+struct evr_brisque {
+    double* d_model = nullptr;   // fmin [36], fmax [36], coef [nsv], sv [nsv*36]
+    double* d_table = nullptr;   // r(alpha), alpha, sqrt(G(1/a)/G(3/a)), G(2/a)/G(1/a), GGD ratio: [5][9801]
+    SvrParams svr;
+    Taps taps;
+};
+
+extern "C" int evr_brisque_create(const double* sv, const double* coef, int nsv, double gamma, double rho, const double* fmin,
+                                  const double* fmax, double lower, double upper, evr_brisque** out) {
+    EVR_REQUIRE(out && fmin && fmax, "evr_brisque_create: null pointer");
+    *out = nullptr;
+    EVR_REQUIRE(nsv >= 0, "evr_brisque_create: nsv = %d < 0", nsv);
+    EVR_REQUIRE(nsv == 0 || (sv && coef), "evr_brisque_create: null support vectors");
+    EVR_REQUIRE(std::isfinite(gamma) && std::isfinite(rho) && std::isfinite(lower) && std::isfinite(upper),
+                "evr_brisque_create: gamma, rho, lower and upper must be finite");
+    EVR_REQUIRE(lower < upper, "evr_brisque_create: lower %g >= upper %g", lower, upper);
+    for (int k = 0; k < NF; ++k) {
+        EVR_REQUIRE(std::isfinite(fmin[k]) && std::isfinite(fmax[k]), "evr_brisque_create: range of feature %d is not finite", k + 1);
+        EVR_REQUIRE(fmin[k] <= fmax[k], "evr_brisque_create: feature %d has min %g > max %g", k + 1, fmin[k], fmax[k]);
+    }
+    for (int i = 0; i < nsv; ++i) {
+        EVR_REQUIRE(std::isfinite(coef[i]), "evr_brisque_create: coef[%d] is not finite", i);
+        for (int k = 0; k < NF; ++k)
+            EVR_REQUIRE(std::isfinite(sv[(size_t)i * NF + k]), "evr_brisque_create: sv[%d][%d] is not finite", i, k);
+    }
+    std::vector<double> model(2 * NF + (size_t)nsv * (NF + 1));
+    for (int k = 0; k < NF; ++k) { model[k] = fmin[k]; model[NF + k] = fmax[k]; }
+    for (int i = 0; i < nsv; ++i) model[2 * NF + i] = coef[i];
+    for (size_t i = 0; i < (size_t)nsv * NF; ++i) model[2 * NF + nsv + i] = sv[i];
+    const std::vector<double> table = alpha_table(5);
+    evr_brisque* h = new (std::nothrow) evr_brisque();
+    EVR_REQUIRE(h, "evr_brisque_create: out of host memory");
+    h->taps = gaussian_taps();
+    h->svr = SvrParams{nsv, gamma, rho, lower, upper};
+    hipError_t e = hipMalloc((void**)&h->d_model, model.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_table, table.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(h->d_model, model.data(), model.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h->d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (h->d_model) (void)hipFree(h->d_model);
+        if (h->d_table) (void)hipFree(h->d_table);
+        delete h;
+        return evr::hip_fail(e, "evr_brisque_create", __FILE__, __LINE__);
+    }
+    *out = h;
+    return EVR_OK;
+}
+
+extern "C" int evr_brisque_destroy(evr_brisque* h) {
+    if (!h) return EVR_OK;
+    hipError_t e1 = h->d_model ? hipFree(h->d_model) : hipSuccess;
+    hipError_t e2 = h->d_table ? hipFree(h->d_table) : hipSuccess;
+    delete h;
+    EVR_HIP(e1);
+    EVR_HIP(e2);
+    return EVR_OK;
+}
+
+extern "C" size_t evr_brisque_workspace_bytes(int n, int H, int W) {
+    if (n < 0 || H < 1 || W < 1) return 0;
+    const BDims d = bdims(n, H, W);
+    return d.half_bytes + d.part1_bytes + d.part2_bytes + 256;
+}
+
+static int brisque_run(evr_brisque* h, const float* img, int n, int H, int W, int clip, double* scores, double* feat, void* ws,
+                       size_t ws_bytes, evr_stream_t stream_, const char* what) {
+    hipStream_t stream = (hipStream_t)stream_;
+    EVR_REQUIRE(h, "%s: null handle", what);
+    EVR_REQUIRE(n >= 0 && n <= 65535 && H >= 1 && W >= 1, "%s: bad shape n=%d H=%d W=%d", what, n, H, W);
+    EVR_REQUIRE((int64_t)H * W <= (int64_t)1 << 30, "%s: %d x %d frame is too large", what, H, W);
+    if (n == 0) return EVR_OK;
+    EVR_REQUIRE(img, "%s: null pointer", what);
+    const size_t need = evr_brisque_workspace_bytes(n, H, W);
+    if (!ws || ws_bytes < need) {
+        evr::set_error("%s: workspace %zu B < required %zu B", what, ws_bytes, need);
+        return EVR_ERR_WORKSPACE;
+    }
+    const BDims d = bdims(n, H, W);
+    char* p = (char*)ws;
+    double* half = (double*)p; p += d.half_bytes;
+    double* part1 = (double*)p; p += d.part1_bytes;
+    double* part2 = (double*)p;
+    hipLaunchKernelGGL(niqe_resize_kernel, dim3((unsigned)(((int64_t)d.Hh * d.Wh + NT - 1) / NT), n), dim3(NT), 0, stream, img, H,
+                       W, H, W, clip, half);
+    EVR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(brisque_stats_kernel<float>, dim3(d.nt1, n), dim3(NT), 0, stream, img, H, W, clip, d.ntx1, h->taps, part1);
+    EVR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(brisque_stats_kernel<double>, dim3(d.nt2, n), dim3(NT), 0, stream, (const double*)half, d.Hh, d.Wh, clip,
+                       d.ntx2, h->taps, part2);
+    EVR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(brisque_finish_kernel, dim3(n), dim3(NT), 0, stream, (const double*)part1, d.nt1, H * W,
+                       (const double*)part2, d.nt2, d.Hh * d.Wh, (const double*)h->d_table, (const double*)h->d_model, h->svr,
+                       feat, scores);
+    EVR_LAUNCH_CHECK();
+    return EVR_OK;
+}
+
+extern "C" int evr_brisque_score(evr_brisque* h, const float* img, int n, int H, int W, int clip, double* out_scores,
+                                 void* workspace, size_t workspace_bytes, evr_stream_t stream) {
+    EVR_REQUIRE(h, "evr_brisque_score: null handle");
+    EVR_REQUIRE(h->svr.nsv > 0, "evr_brisque_score: a features-only handle (no support vectors) gives no score");
+    if (!out_scores && n > 0) {
+        evr::set_error("evr_brisque_score: null pointer");
+        return EVR_ERR_INVALID;
+    }
+    return brisque_run(h, img, n, H, W, clip, out_scores, nullptr, workspace, workspace_bytes, stream, "evr_brisque_score");
+}
+
+extern "C" int evr_brisque_features(evr_brisque* h, const float* img, int n, int H, int W, int clip, double* out_feat,
+                                    void* workspace, size_t workspace_bytes, evr_stream_t stream) {
+    if (!out_feat && n > 0) {
+        evr::set_error("evr_brisque_features: null pointer");
+        return EVR_ERR_INVALID;
+    }
+    return brisque_run(h, img, n, H, W, clip, nullptr, out_feat, workspace, workspace_bytes, stream, "evr_brisque_features");
 }

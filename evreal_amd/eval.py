@@ -301,7 +301,7 @@ class _ChunkBuffers:
     """Device + pinned host buffers of one in-flight chunk (the frame loop keeps two: while the host books chunk c, the
     GPU already works on chunk c + 1)."""
 
-    def __init__(self, S, B, H, W, dev, want_scores, want_lpips, want_u8, with_refs, want_niqe=False):
+    def __init__(self, S, B, H, W, dev, want_scores, want_lpips, want_u8, with_refs, want_niqe=False, want_brisque=False):
         f32 = dict(dtype=torch.float32, device=dev)
         self.grid = torch.empty((CHUNK, S, B, H, W), **f32)
         self.stats = torch.zeros((CHUNK, S, 3), dtype=torch.float64, device=dev)
@@ -313,6 +313,8 @@ class _ChunkBuffers:
         self.h_lp = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_lpips else None
         self.nq = torch.zeros((CHUNK * S,), dtype=torch.float64, device=dev) if want_niqe else None
         self.h_nq = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_niqe else None
+        self.bq = torch.zeros((CHUNK * S,), dtype=torch.float64, device=dev) if want_brisque else None
+        self.h_bq = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_brisque else None
         self.u8 = torch.empty((CHUNK, S, H, W), dtype=torch.uint8, device=dev) if want_u8 else None
         self.h_u8 = torch.empty((CHUNK, S, H, W), dtype=torch.uint8).pin_memory() if want_u8 else None
         self.ev_model = torch.cuda.Event()
@@ -370,9 +372,10 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
     want_u8 = trackers[0].save_images
     lp_model = EvalMetricsTracker._lpips_model() if 'lpips' in pre else None
     nq_model = EvalMetricsTracker._niqe_model() if 'niqe' in pre else None
+    bq_model = EvalMetricsTracker._brisque_model() if 'brisque' in pre else None
     gpu_metrics = trackers[0]._gpu
     bufs = [_ChunkBuffers(S, batch.num_bins, H, W, dev, bool(set(pre) & {'mse', 'ssim'}), lp_model is not None, want_u8,
-                          all(ds.has_images for ds in dss), nq_model is not None) for _ in range(2)]
+                          all(ds.has_images for ds in dss), nq_model is not None, bq_model is not None) for _ in range(2)]
     main = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(device=dev)
     policy = _range_guard_policy(eval_config)
@@ -413,6 +416,9 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
             if b.nq is not None:
                 nq_model(im, clip=True, out=b.nq[:n * S])
                 b.h_nq[:n * S].copy_(b.nq[:n * S], non_blocking=True)
+            if b.bq is not None:
+                bq_model(im, clip=True, out=b.bq[:n * S])
+                b.h_bq[:n * S].copy_(b.bq[:n * S], non_blocking=True)
             if b.u8 is not None:
                 b.u8[:n].copy_(torch.round(torch.clamp(b.imgs[:n, :, 0], 0.0, 1.0) * 255))     # eval_utils.py:83
                 b.h_u8[:n].copy_(b.u8[:n], non_blocking=True)
@@ -430,6 +436,7 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
         sc = b.h_scores[:n * S].numpy().reshape(n, S, 2) if b.h_scores is not None else None
         lp = b.h_lp[:n * S].numpy().reshape(n, S) if b.h_lp is not None else None
         nq = b.h_nq[:n * S].numpy().reshape(n, S) if b.h_nq is not None else None
+        bq = b.h_bq[:n * S].numpy().reshape(n, S) if b.h_bq is not None else None
         for j in range(S):
             it = b.items[j]
             if not it:
@@ -442,6 +449,7 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
                 if 'ssim' in pre: scores['ssim'] = sc[:k, j, 1].copy()
                 if 'lpips' in pre and lp is not None: scores['lpips'] = lp[:k, j].copy()
                 if 'niqe' in pre and nq is not None: scores['niqe'] = nq[:k, j].copy()
+                if 'brisque' in pre and bq is not None: scores['brisque'] = bq[:k, j].copy()
             u8 = b.h_u8[:k, j] if b.h_u8 is not None else None      # (a strided view of the pinned buffer: the native writers copy it inside the call)
             if ds.has_images:
                 refs = b.refs[:k, j] if b.refs is not None else ds.frames(tb['frame_index'][it])[:, 0]

@@ -8,8 +8,9 @@ Frames arrive in batches; gating (start/end time, |ref_ts-img_ts| <= ts_tol_ms, 
 Metric plug-ins keep the reference's contract (utils/eval_metrics.py:18-75): a `BaseMetric` subclass with `name`,
 `no_ref`, `calculate(img, ref) -> float | list`, `finish_queue()`, `reset()`.  Three kinds live side by side:
   * 'mse', 'ssim' and -- when a weights file is available -- 'lpips' run batched on the GPU (evr_metrics / evr_lpips_*);
-  * 'niqe' (no-reference) runs batched on the GPU (evr_niqe_*) when a pristine model file is available, and its scores are
-    booked through the four-frame queue of the reference's pyiqa metrics, so its file holds the same lines;
+  * 'niqe' and 'brisque' (no-reference) run batched on the GPU (evr_niqe_* / evr_brisque_*) when a model file is available,
+    and their scores are booked through the four-frame queue of the reference's pyiqa metrics, so their files hold the
+    same lines;
   * anything registered with `register_metric(name, factory)` runs per frame on host arrays, exactly like the reference's
     MseMetric / SsimMetric (clipped float32 [H,W] images in, a float or a list of floats out);
   * any other name is looked up in pyiqa.list_models() when pyiqa is importable (queued in batches of 4 as
@@ -31,6 +32,8 @@ GPU_METRICS = ('mse', 'ssim')
 LPIPS_WEIGHTS_ENV = 'EVREAL_LPIPS_WEIGHTS'      # path to a pyiqa/lpips AlexNet-v0.1 state_dict (torch.save'd)
 NIQE_MODEL_ENV = 'EVREAL_NIQE_MODEL'            # path to a NIQE pristine model (.mat of the MATLAB release, or .npz)
 NIQE_MODEL_FILES = (os.path.join('pretrained', 'niqe_modelparameters.mat'), os.path.join('pretrained', 'niqe_model.npz'))
+BRISQUE_MODEL_ENV = 'EVREAL_BRISQUE_MODEL'      # path to a BRISQUE model (.npz, or a libsvm text model such as allmodel)
+BRISQUE_RANGE_ENV = 'EVREAL_BRISQUE_RANGE'      # the svm-scale range file of a libsvm model (default: allrange beside it)
 
 
 def _load_lpips():
@@ -58,6 +61,34 @@ def _load_niqe():
     model = load_niqe_model(path)
     print(f"niqe: model {path} ({model['source']})")
     return NIQE(model)
+
+
+def brisque_model_path():
+    """-> (model path, range path or None) for the first that exists of: $EVREAL_BRISQUE_MODEL (an .npz, or a libsvm model
+    with $EVREAL_BRISQUE_RANGE, else `allrange` beside it), pretrained/brisque_model.npz, pretrained/allmodel with
+    pretrained/allrange; None without one."""
+    path = os.environ.get(BRISQUE_MODEL_ENV)
+    if path and os.path.exists(path):
+        if path.lower().endswith('.npz'):
+            return path, None
+        return path, os.environ.get(BRISQUE_RANGE_ENV) or os.path.join(os.path.dirname(path), 'allrange')
+    npz = os.path.join('pretrained', 'brisque_model.npz')
+    if os.path.exists(npz):
+        return npz, None
+    model, rng = os.path.join('pretrained', 'allmodel'), os.path.join('pretrained', 'allrange')
+    if os.path.exists(model) and os.path.exists(rng):
+        return model, rng
+    return None
+
+
+def _load_brisque():
+    found = brisque_model_path()
+    if found is None:
+        return None
+    from .nriqa import BRISQUE, load_brisque_model
+    model = load_brisque_model(*found)
+    print(f"brisque: model {found[0]} ({model['source']})")
+    return BRISQUE(model)
 
 
 class BaseMetric:
@@ -261,6 +292,8 @@ class EvalMetricsTracker:
                 self.metrics.append(GpuMetric(name))
             elif name == 'niqe' and self._niqe_model() is not None:
                 self.metrics.append(QueuedGpuMetric(name, no_ref=True))
+            elif name == 'brisque' and self._brisque_model() is not None:
+                self.metrics.append(QueuedGpuMetric(name, no_ref=True))
             elif name in _REGISTRY:
                 self.metrics.append(_REGISTRY[name]())
             elif name in pyiqa_metric_factory().list_of_metrics:
@@ -292,6 +325,15 @@ class EvalMetricsTracker:
         if not cls._niqe_cache[0]:
             cls._niqe_cache = [True, _load_niqe()]
         return cls._niqe_cache[1]
+
+    _brisque_cache = [False, None]
+
+    @classmethod
+    def _brisque_model(cls):
+        """One BRISQUE model per process; None without a model file (then `brisque` goes to pyiqa, or is unknown)."""
+        if not cls._brisque_cache[0]:
+            cls._brisque_cache = [True, _load_brisque()]
+        return cls._brisque_cache[1]
 
     # -- files --------------------------------------------------------------------------------
     def reset(self):
@@ -396,17 +438,19 @@ class EvalMetricsTracker:
             rsel = refs[js].contiguous() if refs is not None else None
         if gpu:
             want = {m.name for m in gpu}
-            scores = lp = nq = None
+            scores = lp = nq = bq = None
             if not have_pre:
                 if want & set(GPU_METRICS):
                     scores = self._gpu(isel, rsel, mse='mse' in want, ssim='ssim' in want, clip=True).cpu().numpy()
                 lp = self._lpips_model()(isel, rsel, clip=True).cpu().numpy() if 'lpips' in want else None
                 nq = self._niqe_model()(isel, clip=True).cpu().numpy() if 'niqe' in want else None
+                bq = self._brisque_model()(isel, clip=True).cpu().numpy() if 'brisque' in want else None
             for m in gpu:
                 if have_pre:
                     col = np.asarray(pre[m.name])[sel]
                 else:
-                    col = scores[:, 0] if m.name == 'mse' else scores[:, 1] if m.name == 'ssim' else nq if m.name == 'niqe' else lp
+                    col = (scores[:, 0] if m.name == 'mse' else scores[:, 1] if m.name == 'ssim' else nq if m.name == 'niqe'
+                           else bq if m.name == 'brisque' else lp)
                 if isinstance(m, QueuedGpuMetric):
                     self._append(join(self.output_dir, m.name + '.txt'), m.book(self.quan_eval_indices, idxs, col))
                     continue

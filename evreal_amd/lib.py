@@ -83,6 +83,12 @@ SYMBOLS = {
     'evr_niqe_score': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'evr_niqe_features': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                   c_void_p]),
+    'evr_brisque_create': (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_double, c_double,
+                                   ctypes.POINTER(c_void_p)]),
+    'evr_brisque_destroy': (c_int, [c_void_p]),
+    'evr_brisque_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'evr_brisque_score': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'evr_brisque_features': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'evr_bayer_split': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'evr_color_merge': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'evr_split_pack': (c_int, [c_void_p, c_void_p, c_int64]),

@@ -1,5 +1,6 @@
-"""No-reference image quality on the GPU: NIQE (Mittal, Soundararajan, Bovik 2013), the `-qm niqe` of the reference's
-no-reference datasets (utils/eval_metrics.py:100-156, 205-208 -> pyiqa), through evr_niqe_* (csrc/nriqa.hip).
+"""No-reference image quality on the GPU: NIQE (Mittal, Soundararajan, Bovik 2013) and BRISQUE (Mittal, Moorthy, Bovik
+2012), the `-qm niqe` / `-qm brisque` of the reference's no-reference datasets (utils/eval_metrics.py:100-156, 205-208 ->
+pyiqa), through evr_niqe_* and evr_brisque_* (csrc/nriqa.hip).
 
 The pristine model is a 36-vector and a 36x36 covariance.  Offline it comes from a file:
   * the published MATLAB release's (or pyiqa's cached) `niqe_modelparameters.mat`: keys mu_prisparam, cov_prisparam;
@@ -9,6 +10,15 @@ The pristine model is a 36-vector and a 36x36 covariance.  Offline it comes from
 
     (estimatemodelparam.m on the sequences' images.npy frames).  Scores from a self-fitted model are NOT comparable with
     published NIQE figures.
+
+The BRISQUE model is an RBF support-vector regression plus the svm-scale ranges of its 36 features.  It comes from:
+  * a libsvm text model (e.g. the MATLAB release's `allmodel`) with its svm-scale range file (`allrange`), or
+  * an `.npz` with sv, coef, gamma, rho, fmin, fmax, lower, upper and source, e.g. one converted by
+
+        python -m evreal_amd.nriqa brisque-convert --model allmodel --range allrange --out brisque_model.npz
+
+pyiqa's `brisque_svm_weights.pth` holds the support vectors but not the feature ranges (those live in pyiqa's source), so
+that file alone is refused.
 """
 import argparse
 import ctypes
@@ -164,6 +174,199 @@ def fit_niqe_model(frames, clip=True, threshold=SHARPNESS_THRESHOLD, source='fit
     return dict(mu=mu, cov=cov, source=source)
 
 
+BRISQUE_SVM_TYPES = ('epsilon_svr', 'nu_svr')
+# libsvm model header lines a BRISQUE model may carry without needing them
+_LIBSVM_IGNORED = ('nr_class', 'total_sv', 'probA', 'probB', 'label', 'nr_sv', 'degree', 'coef0')
+
+
+def check_brisque_model(sv, coef, gamma, rho, fmin, fmax, lower, upper):
+    """-> dict of fp64 arrays / floats; raises ValueError unless the model is one evr_brisque_create accepts (nsv = 0: a
+    features-only model)."""
+    sv = np.ascontiguousarray(np.asarray(sv, dtype=np.float64).reshape(-1, NUM_FEATURES))
+    coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float64).reshape(-1))
+    fmin = np.ascontiguousarray(np.asarray(fmin, dtype=np.float64).reshape(-1))
+    fmax = np.ascontiguousarray(np.asarray(fmax, dtype=np.float64).reshape(-1))
+    gamma, rho, lower, upper = float(gamma), float(rho), float(lower), float(upper)
+    if sv.shape[0] != coef.shape[0]:
+        raise ValueError(f"BRISQUE model: {sv.shape[0]} support vectors but {coef.shape[0]} coefficients")
+    if fmin.shape != (NUM_FEATURES,) or fmax.shape != (NUM_FEATURES,):
+        raise ValueError(f"BRISQUE model: feature ranges {fmin.shape} / {fmax.shape}, expected (36,) / (36,)")
+    if not all(np.all(np.isfinite(a)) for a in (sv, coef, fmin, fmax, [gamma, rho, lower, upper])):
+        raise ValueError("BRISQUE model: non-finite values")
+    if not lower < upper:
+        raise ValueError(f"BRISQUE model: scaling interval lower {lower} >= upper {upper}")
+    if np.any(fmin > fmax):
+        raise ValueError(f"BRISQUE model: feature {int(np.argmax(fmin > fmax)) + 1} has min > max")
+    return dict(sv=sv, coef=coef, gamma=gamma, rho=rho, fmin=fmin, fmax=fmax, lower=lower, upper=upper)
+
+
+def _libsvm_index(tok, what, path):
+    i, _, v = tok.partition(':')
+    try:
+        i, v = int(i), float(v)
+    except ValueError:
+        raise ValueError(f"{path}: cannot read '{tok}' in {what}") from None
+    if not 1 <= i <= NUM_FEATURES:
+        raise ValueError(f"{path}: feature index {i} in {what} is outside 1..{NUM_FEATURES}")
+    return i, v
+
+
+def read_libsvm_model(path):
+    """A libsvm text model (svm-train's output) of an epsilon- or nu-SVR with an RBF kernel over at most 36 features ->
+    (sv [nsv, 36], coef [nsv], gamma, rho).  Sparse `index:value` lines; a missing index is 0."""
+    head, sv, coef = {}, [], []
+    with open(path) as f:
+        lines = iter(f.read().splitlines())
+    for line in lines:
+        tok = line.split()
+        if not tok:
+            continue
+        if tok[0] == 'SV':
+            break
+        if tok[0] in ('svm_type', 'kernel_type', 'gamma', 'rho'):
+            head[tok[0]] = tok[1:]
+        elif tok[0] not in _LIBSVM_IGNORED:
+            raise ValueError(f"{path}: unknown libsvm model line '{line.strip()}'")
+    else:
+        raise ValueError(f"{path}: no SV section (not a libsvm model)")
+    svm_type = (head.get('svm_type') or ['?'])[0]
+    if svm_type not in BRISQUE_SVM_TYPES:
+        raise ValueError(f"{path}: svm_type {svm_type}, BRISQUE needs a regression ({' or '.join(BRISQUE_SVM_TYPES)})")
+    kernel = (head.get('kernel_type') or ['?'])[0]
+    if kernel != 'rbf':
+        raise ValueError(f"{path}: kernel_type {kernel}, only rbf is supported")
+    if 'gamma' not in head or 'rho' not in head or len(head['rho']) != 1:
+        raise ValueError(f"{path}: gamma and one rho are required")
+    for n, line in enumerate(lines):
+        tok = line.split()
+        if not tok:
+            continue
+        row = np.zeros(NUM_FEATURES)
+        for t in tok[1:]:
+            i, v = _libsvm_index(t, f'support vector {n + 1}', path)
+            row[i - 1] = v
+        coef.append(float(tok[0]))
+        sv.append(row)
+    return np.array(sv).reshape(-1, NUM_FEATURES), np.array(coef), float(head['gamma'][0]), float(head['rho'][0])
+
+
+def read_svm_scale_range(path):
+    """An svm-scale range file (`svm-scale -s`) with an x section over all 36 features -> (fmin [36], fmax [36], lower,
+    upper).  A y section (target scaling) is refused: BRISQUE's release scales features only."""
+    with open(path) as f:
+        lines = [l.split() for l in f.read().splitlines() if l.strip()]
+    if not lines or lines[0][0] == 'y':
+        raise ValueError(f"{path}: a range file with a y section is not supported" if lines else f"{path}: empty range file")
+    if lines[0] != ['x'] or len(lines) < 2 or len(lines[1]) != 2:
+        raise ValueError(f"{path}: not an svm-scale range file (expected 'x', then 'lower upper')")
+    lower, upper = float(lines[1][0]), float(lines[1][1])
+    fmin, fmax = np.full(NUM_FEATURES, np.nan), np.full(NUM_FEATURES, np.nan)
+    for tok in lines[2:]:
+        if tok[0] == 'y':
+            raise ValueError(f"{path}: a range file with a y section is not supported")
+        if len(tok) != 3:
+            raise ValueError(f"{path}: cannot read range line '{' '.join(tok)}'")
+        i = int(tok[0])
+        if not 1 <= i <= NUM_FEATURES:
+            raise ValueError(f"{path}: feature index {i} is outside 1..{NUM_FEATURES}")
+        fmin[i - 1], fmax[i - 1] = float(tok[1]), float(tok[2])
+    missing = [k + 1 for k in range(NUM_FEATURES) if np.isnan(fmin[k])]
+    if missing:
+        raise ValueError(f"{path}: no range for feature(s) {missing}; all 36 are needed")
+    return fmin, fmax, lower, upper
+
+
+def load_brisque_model(path, range_path=None):
+    """-> dict(sv, coef, gamma, rho, fmin, fmax, lower, upper, source, path) from an .npz, or from a libsvm text model and
+    its svm-scale range file (`range_path`, default `allrange` beside the model)."""
+    if path.lower().endswith('.pth'):
+        raise ValueError(f"{path}: pyiqa's BRISQUE weights hold no feature ranges (they live in pyiqa's source); give a "
+                         "libsvm model with its range file, or an .npz")
+    if path.lower().endswith('.npz'):
+        with np.load(path, allow_pickle=False) as d:
+            m = check_brisque_model(*(d[k] for k in ('sv', 'coef', 'gamma', 'rho', 'fmin', 'fmax', 'lower', 'upper')))
+            source = str(d['source']) if 'source' in d.files else 'unknown'
+    else:
+        if range_path is None:
+            range_path = os.path.join(os.path.dirname(path), 'allrange')
+        sv, coef, gamma, rho = read_libsvm_model(path)
+        fmin, fmax, lower, upper = read_svm_scale_range(range_path)
+        m = check_brisque_model(sv, coef, gamma, rho, fmin, fmax, lower, upper)
+        source = f'libsvm model {os.path.basename(path)} + range {os.path.basename(range_path)}'
+    return dict(m, source=source, path=path)
+
+
+def save_brisque_model(path, sv, coef, gamma, rho, fmin, fmax, lower, upper, source):
+    m = check_brisque_model(sv, coef, gamma, rho, fmin, fmax, lower, upper)
+    np.savez(path, **m, source=np.array(source))
+
+
+class BRISQUE:
+    """BRISQUE scores of cuda fp32 frames [n,H,W] -> cuda fp64 [n] (NaN for a frame with a NaN feature, e.g. a flat one).
+    `model`: a dict as load_brisque_model returns, or a path.  A model without support vectors gives features only.  The
+    workspace is kept between calls."""
+
+    def __init__(self, model):
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        if isinstance(model, (str, os.PathLike)):
+            model = load_brisque_model(os.fspath(model))
+        self.model = check_brisque_model(*(model[k] for k in ('sv', 'coef', 'gamma', 'rho', 'fmin', 'fmax', 'lower', 'upper')))
+        self.source, self.path = model.get('source', 'unknown'), model.get('path')
+        m = self.model
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        h = ctypes.c_void_p()
+        _lib.check(self.lib.evr_brisque_create(vp(m['sv']), vp(m['coef']), len(m['coef']), m['gamma'], m['rho'], vp(m['fmin']),
+                                               vp(m['fmax']), m['lower'], m['upper'], ctypes.byref(h)), 'evr_brisque_create')
+        self.handle = h
+        self.ws = None
+
+    def _workspace(self, n, H, W, device):
+        need = int(self.lib.evr_brisque_workspace_bytes(n, H, W))
+        if self.ws is None or self.ws.numel() < need or self.ws.device != device:
+            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
+        return self.ws
+
+    def __call__(self, img, clip=True, out=None):
+        v = _as_frames(img)
+        n, H, W = v.shape
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=v.device)
+        ws = self._workspace(n, H, W, v.device)
+        _lib.check(self.lib.evr_brisque_score(self.handle, _lib.ptr(v), n, H, W, 1 if clip else 0, _lib.ptr(out), _lib.ptr(ws),
+                                              ws.numel(), _lib.stream_ptr()), 'evr_brisque_score')
+        return out
+
+    def features(self, img, clip=True):
+        """-> cuda fp64 [n, 36]: the 18 full-size features, then the 18 half-size ones (unscaled)."""
+        v = _as_frames(img)
+        n, H, W = v.shape
+        feat = torch.empty((n, NUM_FEATURES), dtype=torch.float64, device=v.device)
+        ws = self._workspace(n, H, W, v.device)
+        _lib.check(self.lib.evr_brisque_features(self.handle, _lib.ptr(v), n, H, W, 1 if clip else 0, _lib.ptr(feat),
+                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), 'evr_brisque_features')
+        return feat
+
+    def __del__(self):
+        try:
+            if self.handle is not None:
+                self.lib.evr_brisque_destroy(self.handle); self.handle = None
+        except Exception:
+            pass
+
+
+_brisque_feature_handle = []
+
+
+def brisque_features(img, clip=True):
+    """BRISQUE features of cuda fp32 frames [n,H,W] -> [n, 36] on the device (a features-only handle)."""
+    if not _brisque_feature_handle:
+        _brisque_feature_handle.append(BRISQUE(dict(sv=np.zeros((0, NUM_FEATURES)), coef=np.zeros(0), gamma=1.0, rho=0.0,
+                                                    fmin=np.zeros(NUM_FEATURES), fmax=np.ones(NUM_FEATURES), lower=-1.0,
+                                                    upper=1.0, source='features only')))
+    return _brisque_feature_handle[0].features(img, clip)
+
+
 def _sequence_frames(path, device, chunk=64):
     """The frames of one sequence's images.npy as the frame loop reads them (images[i][:,:,0] / 255 in fp32)."""
     imgs = np.load(os.path.join(path, 'images.npy'), mmap_mode='r')
@@ -180,7 +383,16 @@ def main(argv=None):
     f = sub.add_parser('fit', help="fit a pristine NIQE model on the sequences' own images.npy frames")
     f.add_argument('--out', required=True, help='output .npz (mu, cov, source)')
     f.add_argument('sequences', nargs='+', help='sequence directories holding images.npy')
+    c = sub.add_parser('brisque-convert', help='convert a libsvm BRISQUE model and its svm-scale range file to an .npz')
+    c.add_argument('--model', required=True, help='libsvm text model (e.g. allmodel)')
+    c.add_argument('--range', default=None, help="svm-scale range file (default: allrange beside the model)")
+    c.add_argument('--out', required=True, help='output .npz')
     a = ap.parse_args(argv)
+    if a.cmd == 'brisque-convert':
+        m = load_brisque_model(a.model, a.range)
+        save_brisque_model(a.out, *(m[k] for k in ('sv', 'coef', 'gamma', 'rho', 'fmin', 'fmax', 'lower', 'upper')), m['source'])
+        print(f"wrote {a.out}: {len(m['coef'])} support vectors, {m['source']}")
+        return 0
     _lib.require_gpu()
     seqs = [os.path.abspath(s) for s in a.sequences]
     source = 'self-fitted (estimatemodelparam, sharpness > 0.75 max) on images.npy of: ' + ', '.join(os.path.basename(s) for s in seqs)

@@ -38,7 +38,7 @@ enum evr_status {
 
 /* Message for the last failure on this thread ("" if none). */
 const char* evr_last_error(void);
-/* ABI version (major*1000 + minor).  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
+/* ABI version (major*1000 + minor).  1005: evr_brisque_*.  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
  * 1001 (round 4): evr_percentile_normalize rejects a NULL workspace (size it with
  * evr_percentile_normalize_workspace_bytes); evr_model_arith reports the mode the convolutions actually run (FireNet's 16-channel
  * layers: h3 whatever EVR_ARITH says). */
@@ -293,6 +293,33 @@ int evr_niqe_score(evr_niqe* h, const float* img, int n, int H, int W, int clip,
                    void* workspace, size_t workspace_bytes, evr_stream_t stream);
 int evr_niqe_features(evr_niqe* h, const float* img, int n, int H, int W, int clip, double* out_feat,
                       double* out_sharpness, void* workspace, size_t workspace_bytes, evr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * BRISQUE (Mittal, Moorthy, Bovik 2012), the no-reference score of `-qm brisque` for datasets without frames
+ * (-> pyiqa in the reference), after the published MATLAB release and libsvm's svm-scale / svm-predict.  Conventions
+ * (csrc/nriqa.hip, tests/brisque_ref.py): u = rint(255 * v) in fp32 (v clamped to [0,1] first when clip != 0), fp64 from
+ * there on, the whole frame (no crop); MSCN with a zero-padded 7x7 Gaussian at full and half size (MATLAB imresize,
+ * ceil(H/2) x ceil(W/2)); 18 features per scale (GGD of the MSCN map, AGGD of four whole-frame circular pair
+ * products); svm-scale to [lower, upper] (a feature with fmin == fmax is dropped); score = sum_i coef_i
+ * exp(-gamma |x' - sv_i|^2) - rho.  A frame with a NaN feature (e.g. a flat one) scores NaN.
+ * evr_brisque_create: sv [nsv*36] (row-major), coef [nsv], the RBF gamma, rho, the per-feature range fmin/fmax [36]
+ *   and the scaled interval lower < upper.  Non-finite values, nsv < 0 and fmin > fmax are refused.  nsv == 0 makes a
+ *   features-only handle (sv and coef may be NULL); evr_brisque_score refuses it.
+ * evr_brisque_score: img [n,H,W] fp32 -> out_scores double [n].
+ * evr_brisque_features: img [n,H,W] fp32 -> out_feat double [n, 36] (the 18 full-size features, then the 18 half-size).
+ * Four launches per call whatever n, no host synchronisation; results are bitwise independent of n and of a frame's
+ * position in the batch.  workspace: evr_brisque_workspace_bytes(n, H, W); n <= 65535.  One handle may serve several
+ * streams at once.
+ */
+typedef struct evr_brisque evr_brisque;
+int evr_brisque_create(const double* sv, const double* coef, int nsv, double gamma, double rho, const double* fmin,
+                       const double* fmax, double lower, double upper, evr_brisque** out);
+int evr_brisque_destroy(evr_brisque* h);
+size_t evr_brisque_workspace_bytes(int n, int H, int W);
+int evr_brisque_score(evr_brisque* h, const float* img, int n, int H, int W, int clip, double* out_scores,
+                      void* workspace, size_t workspace_bytes, evr_stream_t stream);
+int evr_brisque_features(evr_brisque* h, const float* img, int n, int H, int W, int clip, double* out_feat,
+                         void* workspace, size_t workspace_bytes, evr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Colour reconstruction (ColorNet, model/model.py:46-105; merge utils/color_utils.py:53-88).
