@@ -2235,6 +2235,243 @@ static int launch_wide(const ConvArgs& a, const ConvArgs* d_args, hipStream_t st
     return EVR_OK;
 }
 
+#if EVR_ARITH == 3
+// ---------------------------------------------------------------------------------------------------
+// conv3x3_wide_kernel<true, WN> -- the ConvLSTM gate launches -- on v_mfma_f32_16x16x32_f16 (h3 build only; EVR_MFMA16=0 restores the
+// 32x32x16 form above).  Under the h3 mix the chip holds a higher clock on this shape at equal matrix cycles per FLOP
+// (tools/mfma_shape_probe.hip, profiles/r07_mfma_shape_probe.txt).  Block tile, wave tile (64 px x 128 columns), LDS layout, band /
+// weight-ring DMA, counted waits and the XCD remap are the kernel's above; what changes is the fragment addressing and the epilogue.
+//   operands   lane l = (p = l & 15, o = l >> 4) holds row / column p and k = 8o .. 8o + 7 of the 32-channel chunk: of an H2 row's
+//              eight 16-B slots (hi k 0-15 | lo k 0-15 | hi k 16-31 | lo k 16-31) its hi operand is slot 4*(o >> 1) + (o & 1), its
+//              lo operand that slot | 2 -- two ds_read_b128 per 16-row fragment, three MFMAs (lo.hi, hi.lo, hi.hi: small terms first)
+//   fragments  weights (first operand): f = 0..7 = tile rows 16f .. 16f + 15, i.e. gate f >> 1, half s = f & 1 of the wave's 32
+//              hidden channels; pixels: b = 0..3 = the wave's pixels 16b .. 16b + 15.  Per step 8 + 16 reads and 96 MFMAs; the
+//              next weight fragment is requested before the 12 MFMAs of the current one
+//   acc        register j of (b, f) = pixel 16b + p, tile row 16f + 4o + j: a lane holds all four gates of hidden channels
+//              n0/4 + 16s + 4o + 0..3 for 4 pixels -> the cell update is a register epilogue on 16-B runs of c, and h leaves as
+//              4-channel pieces (H2: 8 B hi + 8 B lo; the four lanes o of a pixel cover one whole group)
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ f4 mma16_h3(f4 acc, f16x8 wh, f16x8 wl, f16x8 xh, f16x8 xl) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, acc, 0, 0, 0);
+    return acc;
+}
+#endif
+
+template <int WN>
+__global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvArgs* __restrict__ ap) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const ConvArgs& a = *ap;
+    constexpr int WM = 4, NW = WM * WN, SP = 8, NF = 8;
+    constexpr bool SINGLE = (WN == 1);
+    constexpr int NBUF = SINGLE ? 1 : 2;
+    constexpr int TM = 256, TN = 128 * WN;
+    constexpr int A_ROWS = TM + 8;
+    constexpr int A_PIECES = A_ROWS / 8;
+    constexpr int A_F4 = A_ROWS * SP, B_F4 = TN * SP;
+    constexpr int NA_MAX = (A_PIECES + NW - 1) / NW, NA_MIN = A_PIECES / NW;
+    constexpr int NBW = (B_F4 / 64) / NW;
+    static_assert(NBW == 4 && (SINGLE || NA_MIN == 4), "update the counted waits");
+    __shared__ __attribute__((aligned(16))) float4 lds[NBUF * A_F4 + 2 * B_F4 + SP];   // [band 0 | band 1 | weight slot 0 | 1 | a zero row]
+    constexpr int ZROW = (NBUF * A_F4 + 2 * B_F4) / SP;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wmi = wv & 3, wni = (WN == 1) ? 0 : (wv >> 2);
+    const int W = a.win, H = a.hin;
+    const int hw = H * W;
+    const int M = a.n * hw;
+    const int ntiles = a.cout / TN;
+    int lin;
+    {   // XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8)
+        const int total = gridDim.x, bid = blockIdx.x;
+        const int q = total >> 3, rr = total & 7, xcd = bid & 7, idx = bid >> 3;
+        lin = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
+    }
+    const int ntile = lin % ntiles, mtile = lin / ntiles;
+    const int m0 = mtile * TM, n0 = ntile * TN;
+    const int n0w = n0 + wni * 128;
+    const int c0 = a.c0, c1 = a.c1;
+    const int nchunks = (c0 + (a.in_mode == IN_CAT ? c1 : 0)) / 32;
+    const int ktot = 9 * nchunks * 32;
+    const unsigned in_pix = (unsigned)M;
+    const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(a.in0, in_pix * (unsigned)c0 * 4u);
+    const __amdgpu_buffer_rsrc_t rs1 = make_rsrc(a.in1 ? a.in1 : a.in0, in_pix * (unsigned)(a.in1 ? c1 : c0) * 4u);
+    const __amdgpu_buffer_rsrc_t rsw = make_rsrc(a.wgt, (unsigned)a.cout * ktot * 4u);
+
+    // DMA pieces: conv3x3_wide_kernel's
+    const int row0 = 8 * wv + (lane >> 3);
+    const int a_pix0 = m0 - 1 + row0;
+    const unsigned a_q0 = (unsigned)((((lane & 7) ^ swz<32>(row0)) * 4));
+    const unsigned b_off0 = (unsigned)((n0 + row0) * ktot) + a_q0;
+    const unsigned a_v0 = ((unsigned)(a_pix0 * c0) + a_q0) * 4u, a_v1 = ((unsigned)(a_pix0 * c1) + a_q0) * 4u;
+    auto issue_band = [&](int cc, int dyi, int buf) {
+        int coff = cc * 32;
+        const bool second = coff >= c0;
+        const int csrc = second ? c1 : c0;
+        if (second) coff -= c0;
+        const int shift = (dyi - 1) * W;
+#pragma unroll
+        for (int jj = 0; jj < NA_MAX; ++jj) {
+            if (jj < NA_MIN || wv + jj * NW < A_PIECES) {      // wave-uniform
+                const int pix = a_pix0 + 8 * NW * jj + shift;
+                unsigned voff = OOB_OFFSET;
+                if ((unsigned)pix < in_pix) voff = (second ? a_v1 : a_v0) + (unsigned)(((8 * NW * jj + shift) * csrc + coff) * 4);
+                lds_ptr_t dst = (lds_ptr_t)&lds[buf * A_F4 + (wv + jj * NW) * 64];
+                if (second) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, dst, 16, voff, 0, 0, 0);
+                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, dst, 16, voff, 0, 0, 0);
+            }
+        }
+    };
+    auto issue_w = [&](int t, int cc, int slot) {
+        const unsigned kofs = (unsigned)((t * nchunks + cc) * 32);
+#pragma unroll
+        for (int jj = 0; jj < NBW; ++jj) {
+            lds_ptr_t dst = (lds_ptr_t)&lds[NBUF * A_F4 + slot * B_F4 + (wv + jj * NW) * 64];
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, dst, 16, b_off0 * 4u, (kofs + (unsigned)(8 * NW * jj * ktot)) * 4u, 0, 0);
+        }
+    };
+
+    const int p = lane & 15, o = lane >> 4;
+    const int hs = 4 * (o >> 1) + (o & 1);                     // the lane's hi slot; its lo slot is hs | 2
+    const int wq_h = hs ^ (p >> 1), wq_l = (hs | 2) ^ (p >> 1);     // weight rows 16f + p: swz<32> = p >> 1 for every f
+    // (four named accumulator sets, one per 16-pixel block, as conv3x3_wide_kernel keeps two)
+    f4 accA[NF], accB[NF], accC[NF], accD[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const f4 b4 = *(const f4*)(a.bias + n0w + 16 * f + 4 * o);
+        accA[f] = b4; accB[f] = b4; accC[f] = b4; accD[f] = b4;
+    }
+    const int mP = m0 + wmi * 64 + p;                          // the lane's pixel of block 0; block b: + 16b
+    auto neighbours = [&](int m) -> unsigned {   // validity of the pixel's 9 neighbours (bit t = tap (t/3 - 1, t%3 - 1))
+        unsigned vm = 0;
+        if (m < M) {
+            const int img = fdiv(m, a.div_hw_mul, a.div_hw_sh), rem = m - img * hw;
+            const int py = fdiv(rem, a.div_w_mul, a.div_w_sh), px = rem - py * W;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
+                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) vm |= 1u << t;
+            }
+        }
+        return vm;
+    };
+    const unsigned vmA = neighbours(mP), vmB = neighbours(mP + 16), vmC = neighbours(mP + 32), vmD = neighbours(mP + 48);
+
+    if (tid < SP) lds[NBUF * A_F4 + 2 * B_F4 + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+    issue_band(0, 0, 0);
+    issue_w(0, 0, 0);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+
+    for (int c = 0; c < nchunks; ++c) {
+        const int pa = c & 1;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int t2 = (t + 1) % 9;
+            int cw = c + (t + 1) / 9;
+            if (cw >= nchunks) cw = nchunks - 1;
+            const int d2 = (t / 3 + 1) % 3;
+            int cb = c + (t / 3 + 1) / 3;
+            if (cb >= nchunks) cb = nchunks - 1;
+            issue_w(t2, cw, pa ^ ((t + 1) & 1));
+            if (!SINGLE && t % 3 == 0) issue_band(cb, d2, pa ^ ((t / 3 + 1) & 1));
+            __builtin_amdgcn_sched_barrier(0);
+            const int ab = SINGLE ? 0 : (pa ^ ((t / 3) & 1));
+            const float4* lb = &lds[NBUF * A_F4 + (pa ^ (t & 1)) * B_F4 + (wni * 128 + p) * SP];
+            int l0 = wmi * 64 + p + (t % 3);                           // band row of block 0; block b: + 16b, the same swizzle
+            asm volatile("" : "+v"(l0));
+            const int xs = swz<32>(l0);
+            int iA = ab * A_ROWS + l0, iB = iA + 16, iC = iA + 32, iD = iA + 48;
+            if (t != 4) {
+                iA = ((vmA >> t) & 1u) ? iA : ZROW; iB = ((vmB >> t) & 1u) ? iB : ZROW;
+                iC = ((vmC >> t) & 1u) ? iC : ZROW; iD = ((vmD >> t) & 1u) ? iD : ZROW;
+            }
+            auto ld = [&](const float4* q) { return __builtin_bit_cast(f16x8, *q); };
+            const f16x8 xhA = ld(&lds[iA * SP + (hs ^ xs)]), xlA = ld(&lds[iA * SP + ((hs | 2) ^ xs)]);
+            const f16x8 xhB = ld(&lds[iB * SP + (hs ^ xs)]), xlB = ld(&lds[iB * SP + ((hs | 2) ^ xs)]);
+            const f16x8 xhC = ld(&lds[iC * SP + (hs ^ xs)]), xlC = ld(&lds[iC * SP + ((hs | 2) ^ xs)]);
+            const f16x8 xhD = ld(&lds[iD * SP + (hs ^ xs)]), xlD = ld(&lds[iD * SP + ((hs | 2) ^ xs)]);
+            f16x8 wh = ld(lb + wq_h), wl = ld(lb + wq_l);
+#pragma unroll
+            for (int f = 0; f < NF; ++f) {
+                f16x8 whn = wh, wln = wl;
+                if (f + 1 < NF) { whn = ld(lb + (f + 1) * 16 * SP + wq_h); wln = ld(lb + (f + 1) * 16 * SP + wq_l); }
+                accA[f] = mma16_h3(accA[f], wh, wl, xhA, xlA);
+                accB[f] = mma16_h3(accB[f], wh, wl, xhB, xlB);
+                accC[f] = mma16_h3(accC[f], wh, wl, xhC, xlC);
+                accD[f] = mma16_h3(accD[f], wh, wl, xhD, xlD);
+                __builtin_amdgcn_sched_barrier(0);
+                wh = whn; wl = wln;
+            }
+            if constexpr (SINGLE) {
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                if (t % 3 == 2 && !(t == 8 && c == nchunks - 1)) {
+                    issue_band(cb, d2, 0);
+                    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                }
+            } else {
+                if (t % 3 == 0) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            }
+        }
+    }
+
+    // ConvLSTM cell update (submodules.py:227-245; the operation order per value is epi_finish's).  The cell states of all four
+    // pixel blocks are requested before the first gate arithmetic.
+    const float sc = a.acc_scale;
+    const unsigned hid = (unsigned)a.hidden;
+    const int ch0 = (n0w >> 2) + 4 * o;
+    const bool okA = mP < M, okB = mP + 16 < M, okC = mP + 32 < M, okD = mP + 48 < M;
+    const unsigned rA = (unsigned)(okA ? mP : 0) * hid, rB = (unsigned)(okB ? mP + 16 : 0) * hid;
+    const unsigned rC = (unsigned)(okC ? mP + 32 : 0) * hid, rD = (unsigned)(okD ? mP + 48 : 0) * hid;
+    f4 cpA[2], cpB[2], cpC[2], cpD[2];
+    const bool lds_c = !(a.debug_ablate & 16) && !(EPI_ABLATE & 16);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const f4 z = {0.f, 0.f, 0.f, 0.f};
+        cpA[s] = lds_c ? *(const f4*)(a.state + rA + ch0 + 16 * s) : z;
+        cpB[s] = lds_c ? *(const f4*)(a.state + rB + ch0 + 16 * s) : z;
+        cpC[s] = lds_c ? *(const f4*)(a.state + rC + ch0 + 16 * s) : z;
+        cpD[s] = lds_c ? *(const f4*)(a.state + rD + ch0 + 16 * s) : z;
+    }
+    auto finish = [&](const f4 (&acc)[NF], const f4 (&cp)[2], unsigned row, bool ok) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            f4 cn, hn;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float gi = sigmoid_t<true>(acc[s][j] * sc);
+                const float gf = sigmoid_t<true>(acc[2 + s][j] * sc);
+                const float go = sigmoid_t<true>(acc[4 + s][j] * sc);
+                const float gc = tanh_t<true>(acc[6 + s][j] * sc);
+                cn[j] = __fadd_rn(__fmul_rn(gf, cp[s][j]), __fmul_rn(gi, gc));
+                hn[j] = go * tanh_t<true>(cn[j]);
+            }
+            if (ok && (!(EPI_ABLATE & 64) || cn[0] == 123.456f)) {
+                *(f4*)(a.state + row + ch0 + 16 * s) = cn;                      // the cell state stays fp32
+                if (!a.out_packed) *(f4*)(a.out + row + ch0 + 16 * s) = hn;
+                else store4_fmt<FMT>(a.out, row, ch0 + 16 * s, hn);
+            }
+        }
+    };
+    finish(accA, cpA, rA, okA);
+    finish(accB, cpB, rB, okB);
+    finish(accC, cpC, rC, okC);
+    finish(accD, cpD, rD, okD);
+#endif
+}
+
+template <int WN>
+static int launch_wide16(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream) {
+    const int M = a.n * a.hm * a.wm;
+    const int total = ((M + 255) / 256) * (a.cout / (128 * WN));
+    hipLaunchKernelGGL((conv3x3_wide16_kernel<WN>), dim3(total), dim3(256 * WN), 0, stream, d_args);
+    EVR_LAUNCH_CHECK();
+    return EVR_OK;
+}
+#endif   // EVR_ARITH == 3
+
 // ---------------------------------------------------------------------------------------------------
 // Programmed band kernel: the k5 stride-2 encoder convolutions in split arithmetic on PACKED activations.
 //
@@ -2757,6 +2994,11 @@ int EVR_LAUNCH_NAME(const ConvArgs& a, const ConvArgs* d_args, int kc, int wm, i
         const bool wide_ok = wide && a.tp.ngroups == 1 && a.cout % 256 == 0 && !a.pred_w &&
                              (((int64_t)a.n * a.hm * a.wm + 255) / 256) * (a.cout / 256) >= (twin ? wide_min_twin : wide_min);
         if (wide_ok && a.epi == EPI_LSTM) {
+#if EVR_ARITH == 3
+            // the same tiles on 16x16x32 MFMAs (conv3x3_wide16_kernel); EVR_MFMA16=0: the 32x32x16 form
+            static const int mfma16 = getenv("EVR_MFMA16") ? atoi(getenv("EVR_MFMA16")) : 1;
+            if (mfma16) return twin ? launch_wide16<1>(a, d_args, stream) : launch_wide16<2>(a, d_args, stream);
+#endif
             return twin ? launch_wide<true, 1>(a, d_args, stream, img) : launch_wide<true, 2>(a, d_args, stream, img);
         }
         // plain 3x3 layers (residual blocks): the twin form once a launch has enough 256 x 128 tiles (not at 64 sequences of
