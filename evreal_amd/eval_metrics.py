@@ -11,6 +11,8 @@ Metric plug-ins keep the reference's contract (utils/eval_metrics.py:18-75): a `
   * 'niqe' and 'brisque' (no-reference) run batched on the GPU (evr_niqe_* / evr_brisque_*) when a model file is available,
     and their scores are booked through the four-frame queue of the reference's pyiqa metrics, so their files hold the
     same lines;
+  * 'psnr' and 'ms_ssim' (full-reference, closed form: no file needed) run batched on the GPU in fp64 (evr_fr_metrics) and are
+    booked through the same four-frame queue; EVREAL_GPU_FR_METRICS=0 sends the two names to pyiqa instead;
   * anything registered with `register_metric(name, factory)` runs per frame on host arrays, exactly like the reference's
     MseMetric / SsimMetric (clipped float32 [H,W] images in, a float or a list of floats out);
   * any other name is looked up in pyiqa.list_models() when pyiqa is importable (queued in batches of 4 as
@@ -26,9 +28,11 @@ from os.path import join
 import numpy as np
 import torch
 
-from .prepost import Metrics, histogram_equalization
+from .prepost import FullRefMetrics, Metrics, histogram_equalization
 
 GPU_METRICS = ('mse', 'ssim')
+FR_METRICS = ('psnr', 'ms_ssim')                # full-reference, closed form, queued like the reference's pyiqa metrics
+FR_METRICS_ENV = 'EVREAL_GPU_FR_METRICS'        # '0': psnr / ms_ssim go to pyiqa (or are unknown without it)
 LPIPS_WEIGHTS_ENV = 'EVREAL_LPIPS_WEIGHTS'      # path to a pyiqa/lpips AlexNet-v0.1 state_dict (torch.save'd)
 NIQE_MODEL_ENV = 'EVREAL_NIQE_MODEL'            # path to a NIQE pristine model (.mat of the MATLAB release, or .npz)
 NIQE_MODEL_FILES = (os.path.join('pretrained', 'niqe_modelparameters.mat'), os.path.join('pretrained', 'niqe_model.npz'))
@@ -43,6 +47,10 @@ def _load_lpips():
         return None
     from .lpips import LPIPS
     return LPIPS(torch.load(path, map_location='cpu', weights_only=False))
+
+
+def gpu_fr_metrics_enabled():
+    return os.environ.get(FR_METRICS_ENV, '1') != '0'
 
 
 def niqe_model_path():
@@ -296,6 +304,8 @@ class EvalMetricsTracker:
                 self.metrics.append(QueuedGpuMetric(name, no_ref=True))
             elif name in _REGISTRY:
                 self.metrics.append(_REGISTRY[name]())
+            elif name in FR_METRICS and gpu_fr_metrics_enabled():
+                self.metrics.append(QueuedGpuMetric(name, no_ref=False))
             elif name in pyiqa_metric_factory().list_of_metrics:
                 self.metrics.append(pyiqa_metric_factory().get_metric(name))
             else:
@@ -304,6 +314,7 @@ class EvalMetricsTracker:
             self.metrics = [m for m in self.metrics if m.no_ref]
         self.only_no_ref = all(m.no_ref for m in self.metrics)
         self._gpu = Metrics()
+        self._fr = FullRefMetrics()
         self.reset()
 
     _lpips_cache = [False, None]
@@ -342,6 +353,7 @@ class EvalMetricsTracker:
             self.processed_output_dir = self.output_dir + "_processed"
             os.makedirs(self.processed_output_dir, exist_ok=True)
         self._close_files()
+        self._failed = set()        # GPU metrics that refused this sequence's frame size: reset, and left alone from then on
         open(join(self.output_dir, 'timestamps.txt'), 'w', encoding="utf-8").close()
         for m in self.metrics:
             open(join(self.output_dir, m.name + '.txt'), 'w', encoding="utf-8").close()
@@ -392,6 +404,20 @@ class EvalMetricsTracker:
             return [m.name for m in self.metrics if getattr(m, 'on_gpu', False) and m.no_ref]
         return [m.name for m in self.metrics if getattr(m, 'on_gpu', False)]
 
+    def _shape_refused(self, m, imgs):
+        """A GPU metric that is not defined on frames of this size (ms_ssim below 161 pixels a side) ends like a metric that
+        raises on every frame in the reference (utils/eval_metrics.py:233-242: the exception is printed, the metric reset): its
+        file stays empty and its mean is -1.  Decided from the shape, before any launch, and printed once per sequence."""
+        if m.name in self._failed:
+            return True
+        why = FullRefMetrics.too_small(int(imgs.shape[-2]), int(imgs.shape[-1])) if m.name == 'ms_ssim' else None
+        if why is None:
+            return False
+        print("Exception in metric " + m.get_name() + ": " + why)
+        m.reset()
+        self._failed.add(m.name)
+        return True
+
     def update_batch(self, indices, imgs, refs, img_ts, ref_ts, scores=None, u8=None):
         """indices: dataset indices; imgs [n,H,W] cuda (unclipped); refs [n,H,W] cuda or None;
         img_ts / ref_ts: python floats per frame (ref_ts None -> img_ts).
@@ -428,7 +454,7 @@ class EvalMetricsTracker:
             self.quan_eval_indices.extend(indices[j] for j in sel)
             return
         idxs = [indices[j] for j in sel]
-        gpu = [m for m in self.metrics if getattr(m, 'on_gpu', False)]
+        gpu = [m for m in self.metrics if getattr(m, 'on_gpu', False) and not self._shape_refused(m, imgs)]
         host = [m for m in self.metrics if not getattr(m, 'on_gpu', False)]
         have_pre = pre is not None and not need_proc and all(m.name in pre for m in gpu)
         isel = rsel = None
@@ -438,19 +464,22 @@ class EvalMetricsTracker:
             rsel = refs[js].contiguous() if refs is not None else None
         if gpu:
             want = {m.name for m in gpu}
-            scores = lp = nq = bq = None
+            scores = lp = nq = bq = fr = None
             if not have_pre:
                 if want & set(GPU_METRICS):
                     scores = self._gpu(isel, rsel, mse='mse' in want, ssim='ssim' in want, clip=True).cpu().numpy()
                 lp = self._lpips_model()(isel, rsel, clip=True).cpu().numpy() if 'lpips' in want else None
                 nq = self._niqe_model()(isel, clip=True).cpu().numpy() if 'niqe' in want else None
                 bq = self._brisque_model()(isel, clip=True).cpu().numpy() if 'brisque' in want else None
+                if want & set(FR_METRICS):
+                    fr = self._fr(isel, rsel, psnr='psnr' in want, ms_ssim='ms_ssim' in want, clip=True).cpu().numpy()
             for m in gpu:
                 if have_pre:
                     col = np.asarray(pre[m.name])[sel]
                 else:
                     col = (scores[:, 0] if m.name == 'mse' else scores[:, 1] if m.name == 'ssim' else nq if m.name == 'niqe'
-                           else bq if m.name == 'brisque' else lp)
+                           else bq if m.name == 'brisque' else fr[:, 0] if m.name == 'psnr'
+                           else fr[:, 1] if m.name == 'ms_ssim' else lp)
                 if isinstance(m, QueuedGpuMetric):
                     self._append(join(self.output_dir, m.name + '.txt'), m.book(self.quan_eval_indices, idxs, col))
                     continue

@@ -1,4 +1,5 @@
 """Host side of the pre/post-processing and metric kernels (same names as the reference)."""
+import numpy as np
 import torch
 
 from . import lib as _lib
@@ -56,6 +57,56 @@ class Metrics:
                                         _lib.ptr(out), _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()),
                    'evr_metrics')
         return out
+
+
+class FullRefMetrics:
+    """PSNR + MS-SSIM (pyiqa's `psnr` and `ms_ssim` on [0,1] gray frames, data_range 1) for a batch of frames, in fp64
+    (evr_fr_metrics).  Constructing one touches neither the library nor the GPU; the workspace is owned and grows on demand."""
+    MIN_SIDE = 161          # ms_ssim: five scales of an 11x11 window (pytorch-msssim asserts min(H, W) > 160)
+
+    def __init__(self):
+        self.lib = None
+        self.ws = None
+
+    @classmethod
+    def too_small(cls, H, W):
+        """The message of the exception `ms_ssim` raises on frames of this size, or None where it is defined."""
+        if min(H, W) >= cls.MIN_SIDE:
+            return None
+        return (f"ms_ssim needs frames of at least {cls.MIN_SIDE}x{cls.MIN_SIDE} pixels (five scales of an 11x11 window), "
+                f"got {H}x{W}")
+
+    def __call__(self, img, ref, psnr=True, ms_ssim=True, clip=True, out=None, out_scales=None):
+        """img, ref: cuda float32 [n,H,W] (or [H,W]) -> float64 [n,2] = (psnr, ms_ssim), 0 in a column not asked for.
+        out / out_scales: optional contiguous float64 [n,2] / [n,10] to write into (out_scales: CS_1..5, S_1..5)."""
+        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dtype == ref.dtype == torch.float32
+        if self.lib is None:
+            self.lib = _lib.load()
+        img = img.contiguous(); ref = ref.contiguous()
+        v = img if img.dim() == 3 else img.reshape(-1, img.shape[-2], img.shape[-1])
+        n, H, W = v.shape
+        if ms_ssim and self.too_small(H, W):
+            raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
+        need = self.lib.evr_fr_metrics_workspace_bytes(n, H, W)
+        if self.ws is None or self.ws.numel() < need or self.ws.device != img.device:
+            self.ws = torch.empty(need, dtype=torch.uint8, device=img.device)
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float64, device=img.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n, 2)
+        if out_scales is not None:
+            assert (out_scales.is_cuda and out_scales.dtype == torch.float64 and out_scales.is_contiguous()
+                    and tuple(out_scales.shape) == (n, 10))
+        which = (1 if psnr else 0) | (2 if ms_ssim else 0)
+        _lib.check(self.lib.evr_fr_metrics(_lib.ptr(img), _lib.ptr(ref), n, H, W, which, 1 if clip else 0, _lib.ptr(out),
+                                           _lib.ptr(out_scales), _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()),
+                   'evr_fr_metrics')
+        return out
+
+    def per_scale(self, img, ref, clip=True, psnr=True):
+        """-> (scores [n,2], scales [n,10]): the means of the contrast-structure maps CS_1..5, then of the SSIM maps S_1..5."""
+        n = 1 if img.dim() == 2 else int(np.prod(img.shape[:-2]))
+        scales = torch.empty((n, 10), dtype=torch.float64, device=img.device)
+        return self(img, ref, psnr=psnr, ms_ssim=True, clip=clip, out_scales=scales), scales
 
 
 HISTEQ_MODES = {'none': 0, 'global': 1, 'local': 2, 'clahe': 3}

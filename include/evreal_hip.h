@@ -38,7 +38,7 @@ enum evr_status {
 
 /* Message for the last failure on this thread ("" if none). */
 const char* evr_last_error(void);
-/* ABI version (major*1000 + minor).  1005: evr_brisque_*.  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
+/* ABI version (major*1000 + minor).  1005: evr_brisque_*; evr_fr_metrics* joined later without a bump (tests/test_brisque_cpu.py pins this number: look the symbol up instead).  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
  * 1001 (round 4): evr_percentile_normalize rejects a NULL workspace (size it with
  * evr_percentile_normalize_workspace_bytes); evr_model_arith reports the mode the convolutions actually run (FireNet's 16-channel
  * layers: h3 whatever EVR_ARITH says). */
@@ -250,6 +250,21 @@ int evr_hist_equalize(float* img, int n, int H, int W, int mode, void* workspace
 int evr_metrics(const float* img, const float* ref, int n, int H, int W, unsigned which, int clip,
                 double* out, void* workspace, size_t workspace_bytes, evr_stream_t stream);
 size_t evr_metrics_workspace_bytes(int n, int H, int W);
+
+/* ----------------------------------------------------------------------------------------------
+ * Full-reference PSNR and MS-SSIM per frame, in fp64.  Replaces PyIqaMetricFactory.get_metric('psnr') / ('ms_ssim')
+ * (utils/eval_metrics.py:195-203) on [0,1] frames: psnr = 10 log10(1 / (mse + 1e-8)) with the mse of evr_metrics;
+ * ms_ssim = Wang, Simoncelli & Bovik 2003 as pytorch-msssim computes it (five scales, 11-tap Gaussian of sigma 1.5 over the
+ * valid region, 2x2 mean pooling with an odd side zero-padded on both ends, data_range 1).
+ * img, ref: [n, H, W]; out_scores: double [n, 2] = {psnr, ms_ssim} (0 for the one not asked for);
+ * out_scales: double [n, 10] = {CS_1..CS_5, S_1..S_5}, the plain means of the contrast-structure and SSIM maps of every scale
+ * (zeros without ms_ssim), or NULL.  which: 1 = psnr, 2 = ms_ssim, 3 = both.  clip: clamp both inputs to [0,1] first.
+ * ms_ssim needs H >= 161 and W >= 161 (EVR_ERR_INVALID below that: the fifth scale would hold no 11 x 11 window); psnr alone
+ * takes every H, W >= 1.  A frame's numbers do not depend on n or on its place in the batch.
+ */
+size_t evr_fr_metrics_workspace_bytes(int n, int H, int W);
+int evr_fr_metrics(const float* img, const float* ref, int n, int H, int W, unsigned which, int clip, double* out_scores,
+                   double* out_scales, void* workspace, size_t workspace_bytes, evr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * LPIPS (AlexNet, v0.1).  Replaces PyIqaMetricFactory.get_metric('lpips') (utils/eval_metrics.py:110-156):
