@@ -11,7 +11,20 @@
 // PARITY: the split and the uint8 planes are pinned against the reference (tests/golden/colornet_seq.npz).  The merge
 // follows OpenCV's documented formulas in floating point; OpenCV's own 8-bit fixed-point resize / Lab tables are not
 // available offline (cv2 is absent), so merged pixels may differ from the reference by a few LSB -- UNPINNED.
+//
+//   evr_color_percentile_normalize   post_process_normalization (eval.py:380-395) of a merged uint8 BGR frame, as the reference
+//                     applies it in colour mode: img = float32(u8) / 255 (exp of that for 'exprobust'), lo / hi = np.percentile over
+//                     all 3*H*W values together, (img - lo) / (hi - lo), and the image writer's round(clip(., 0, 1) * 255).  Every
+//                     step is a function of the byte level alone given the frame's 256-bin histogram, so no float image exists:
+//                     color_hist_kernel counts the levels (integers: exact, order-independent), color_norm_apply_kernel finds the
+//                     four order statistics in the cumulative counts, forms lo and hi with the float32 rule of pct.h from the
+//                     caller's table level -> float32 value (the host's numpy computes it, exp included: no device expf), builds
+//                     the 256-entry byte table and remaps the frame through it.  Bit-exact against numpy (tests/color_norm_ref.py).
+//                     DEGENERATE FRAMES, hi == lo: the reference divides by zero -- levels above lo become +inf -> 255, levels
+//                     below lo -inf -> 0, and the levels equal to lo are NaN.  NaN is DEFINED as byte 0 here (what numpy's cast
+//                     to uint8 gives on x86); a constant frame therefore comes out all 0.
 #include "common.h"
+#include "pct.h"
 
 namespace {
 
@@ -99,6 +112,138 @@ __global__ __launch_bounds__(256) void color_merge_kernel(const float* __restric
     out[i * 3 + 0] = to8(bo); out[i * 3 + 1] = to8(go); out[i * 3 + 2] = to8(ro);
 }
 
+// ---------------------------------------------------------------- percentile normalisation of uint8 BGR frames
+// A clipped frame is often dominated by one or two levels (0 or 255) and a constant frame puts every byte in one bin, so the
+// sub-histograms are split BY LANE: hist[level][lane] (64 KB of LDS per work-group).  A lane only ever touches its own column,
+// column = LDS bank, so one ds_add instruction of a wave never meets a same-address or a same-bank conflict whatever the
+// frame holds; the four waves of a work-group share the columns through the atomics.
+constexpr int CH_THREADS = 256;
+constexpr int CH_UNROLL = 4;                    // 16-B loads in flight per lane
+constexpr int CH_VEC_PER_GROUP = 4096;          // 64 KB of the frame per work-group and grid-stride trip: amortises zeroing + merging
+
+__device__ __forceinline__ void ch_add_word(unsigned* hist, unsigned w, int lane) {
+    atomicAdd(&hist[(w & 255u) * 64 + lane], 1u);
+    atomicAdd(&hist[((w >> 8) & 255u) * 64 + lane], 1u);
+    atomicAdd(&hist[((w >> 16) & 255u) * 64 + lane], 1u);
+    atomicAdd(&hist[(w >> 24) * 64 + lane], 1u);
+}
+
+// the bytes of frame f that 16-B accesses aligned on `p` do not cover: [0, head) and [head + 16 * nvec, nbytes)
+__device__ __forceinline__ void ch_split(const void* p, int nbytes, int& head, int& nvec) {
+    head = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u);
+    if (head > nbytes) head = nbytes;
+    nvec = (nbytes - head) >> 4;
+}
+
+// in: [n][nbytes] uint8 (frame f starts at in + f * nbytes: any alignment); counts: [n][256], zeroed by the caller
+__global__ __launch_bounds__(CH_THREADS) void color_hist_kernel(const unsigned char* __restrict__ in, int nbytes,
+                                                                 unsigned* __restrict__ counts) {
+    __shared__ unsigned hist[256 * 64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const unsigned char* p = in + (int64_t)blockIdx.y * nbytes;
+    for (int i = tid; i < 256 * 64 / 4; i += CH_THREADS) ((uint4*)hist)[i] = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+    int head, nvec;
+    ch_split(p, nbytes, head, nvec);
+    const uint4* v = (const uint4*)(p + head);
+    for (int i0 = blockIdx.x * (CH_THREADS * CH_UNROLL); i0 < nvec; i0 += gridDim.x * (CH_THREADS * CH_UNROLL)) {
+        uint4 x[CH_UNROLL];
+#pragma unroll
+        for (int u = 0; u < CH_UNROLL; ++u) {
+            const int i = i0 + u * CH_THREADS + tid;
+            x[u] = (i < nvec) ? v[i] : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < CH_UNROLL; ++u) {
+            if (i0 + u * CH_THREADS + tid < nvec) {
+                ch_add_word(hist, x[u].x, lane); ch_add_word(hist, x[u].y, lane);
+                ch_add_word(hist, x[u].z, lane); ch_add_word(hist, x[u].w, lane);
+            }
+        }
+    }
+    if (blockIdx.x == 0) {          // the unaligned head (wave 0) and the tail (wave 1): at most 15 bytes each
+        const int tail0 = head + 16 * nvec;
+        if (tid < head) atomicAdd(&hist[(unsigned)p[tid] * 64 + lane], 1u);
+        else if (tid >= 64 && tail0 + (tid - 64) < nbytes) atomicAdd(&hist[(unsigned)p[tail0 + (tid - 64)] * 64 + lane], 1u);
+    }
+    __syncthreads();
+    // thread t sums level t over the 64 columns, starting at its own column so that a wave reads 64 different banks per step
+    unsigned s = 0;
+#pragma unroll 8
+    for (int j = 0; j < 64; ++j) s += hist[tid * 64 + ((j + tid) & 63)];
+    if (s) atomicAdd(&counts[(int64_t)blockIdx.y * 256 + tid], s);
+}
+
+// Every work-group rebuilds its frame's cumulative counts, lo, hi and the byte table (a few hundred operations), then remaps its
+// slice.  16-B accesses are aligned on the OUTPUT frame; the input is read through memcpy, so `in` and `out` may differ in alignment.
+// values: [256] float32, level -> image value (non-decreasing); range: [n][2] = {lo, hi}
+__global__ __launch_bounds__(CH_THREADS) void color_norm_apply_kernel(const unsigned char* in, unsigned char* out, int nbytes,
+                                                                       const float* __restrict__ values, float q_lo, float q_hi,
+                                                                       const unsigned* __restrict__ counts, float* __restrict__ range) {
+    __shared__ unsigned wsum[CH_THREADS / 64];
+    __shared__ int level[4];                    // lo.prev, lo.next, hi.prev, hi.next
+    __shared__ unsigned char table[256];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t off = (int64_t)blockIdx.y * nbytes;
+    const unsigned c = counts[(int64_t)blockIdx.y * 256 + tid];
+    unsigned incl = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = (unsigned)__shfl_up((int)incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) wsum[tid >> 6] = incl;
+    if (tid < 4) level[tid] = 0;
+    __syncthreads();
+    unsigned base = 0;
+    for (int w = 0; w < (tid >> 6); ++w) base += wsum[w];
+    const unsigned excl = base + incl - c;      // bytes of the frame below level tid
+    int rank[4]; float gamma[2];
+    pct_rank(nbytes, q_lo, rank[0], rank[1], gamma[0]);
+    pct_rank(nbytes, q_hi, rank[2], rank[3], gamma[1]);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)                 // the counts sum to nbytes: exactly one level holds each rank
+        if (c > 0 && (unsigned)rank[s] >= excl && (unsigned)rank[s] < excl + c) level[s] = tid;
+    __syncthreads();
+    const float lo = pct_lerp(values[level[0]], values[level[1]], gamma[0]);
+    const float hi = pct_lerp(values[level[2]], values[level[3]], gamma[1]);
+    if (blockIdx.x == 0 && tid == 0) { range[(int64_t)blockIdx.y * 2] = lo; range[(int64_t)blockIdx.y * 2 + 1] = hi; }
+    float x = (values[tid] - lo) / (hi - lo);
+    x = (x == x) ? x : 0.f;                     // NaN (hi == lo at this level) -> byte 0
+    x = fminf(fmaxf(x, 0.f), 1.f);
+    table[tid] = (unsigned char)rintf(x * 255.f);
+    __syncthreads();
+    const unsigned char* src = in + off;
+    unsigned char* dst = out + off;
+    int head, nvec;
+    ch_split(dst, nbytes, head, nvec);
+    // (`in` may be `out`, so the compiler keeps every load behind the stores before it: the loads of a trip are issued together by hand)
+    for (int i0 = blockIdx.x * (CH_THREADS * CH_UNROLL); i0 < nvec; i0 += gridDim.x * (CH_THREADS * CH_UNROLL)) {
+        uint4 x4[CH_UNROLL];
+#pragma unroll
+        for (int u = 0; u < CH_UNROLL; ++u) {
+            const int i = i0 + u * CH_THREADS + tid;
+            if (i < nvec) __builtin_memcpy(&x4[u], src + head + 16 * (int64_t)i, 16);
+            else x4[u] = make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < CH_UNROLL; ++u) {
+            const int i = i0 + u * CH_THREADS + tid;
+            unsigned w[4] = {x4[u].x, x4[u].y, x4[u].z, x4[u].w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                w[k] = (unsigned)table[w[k] & 255u] | ((unsigned)table[(w[k] >> 8) & 255u] << 8) |
+                       ((unsigned)table[(w[k] >> 16) & 255u] << 16) | ((unsigned)table[w[k] >> 24] << 24);
+            if (i < nvec) *(uint4*)(dst + head + 16 * (int64_t)i) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+    if (blockIdx.x == 0) {
+        const int tail0 = head + 16 * nvec;
+        if (tid < head) dst[tid] = table[src[tid]];
+        else if (tid >= 64 && tail0 + (tid - 64) < nbytes) dst[tail0 + (tid - 64)] = table[src[tail0 + (tid - 64)]];
+    }
+}
+
 }  // namespace
 
 extern "C" int evr_bayer_split(const float* vox, int n, int B, int H, int W, float* out, evr_stream_t stream) {
@@ -117,6 +262,42 @@ extern "C" int evr_color_merge(const float* planes, const float* gray, int n, in
     const int64_t total = (int64_t)n * H * W;
     hipLaunchKernelGGL(color_merge_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, planes, gray,
                        bgr_out, n, H / 2, W / 2);
+    EVR_LAUNCH_CHECK();
+    return EVR_OK;
+}
+
+extern "C" size_t evr_color_percentile_normalize_workspace_bytes(int n) {
+    return n > 0 ? (size_t)n * (256 * sizeof(unsigned) + 2 * sizeof(float)) : 0;      // counts [n][256], then {lo, hi} [n][2]
+}
+
+extern "C" int evr_color_percentile_normalize(const uint8_t* bgr_in, uint8_t* bgr_out, int n, int H, int W, const float* values256,
+                                              float q_lo, float q_hi, void* workspace, size_t workspace_bytes, evr_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    EVR_REQUIRE(n >= 0 && H >= 1 && W >= 1, "evr_color_percentile_normalize: bad shape");
+    EVR_REQUIRE(q_lo >= 0.f && q_hi <= 100.f && q_lo <= q_hi, "evr_color_percentile_normalize: percentiles must be in [0,100]");
+    // the ranks (n-1)*q are formed in float32 as numpy forms them: exact integers only below 2^24
+    EVR_REQUIRE(3 * (int64_t)H * W < (1LL << 24), "evr_color_percentile_normalize: frame %dx%dx3 has 2^24 bytes or more", W, H);
+    if (n == 0) return EVR_OK;
+    EVR_REQUIRE(bgr_in != nullptr && bgr_out != nullptr && values256 != nullptr, "evr_color_percentile_normalize: null argument");
+    const size_t need = evr_color_percentile_normalize_workspace_bytes(n);
+    if (!workspace || workspace_bytes < need) {
+        evr::set_error("evr_color_percentile_normalize: workspace %zu B < required %zu B", workspace_bytes, need);
+        return EVR_ERR_WORKSPACE;
+    }
+    EVR_REQUIRE((((uintptr_t)workspace) & 3) == 0, "evr_color_percentile_normalize: workspace must be 4-byte aligned");
+    const int nbytes = 3 * H * W;
+    unsigned* counts = (unsigned*)workspace;
+    float* range = (float*)(counts + (size_t)n * 256);
+    EVR_HIP(hipMemsetAsync(counts, 0, (size_t)n * 256 * sizeof(unsigned), stream));
+    const int nvec = nbytes / 16;
+    int gh = (nvec + CH_VEC_PER_GROUP - 1) / CH_VEC_PER_GROUP;
+    gh = gh < 1 ? 1 : (gh > 64 ? 64 : gh);
+    hipLaunchKernelGGL(color_hist_kernel, dim3(gh, n), dim3(CH_THREADS), 0, stream, bgr_in, nbytes, counts);
+    EVR_LAUNCH_CHECK();
+    int ga = (nvec + CH_THREADS * CH_UNROLL * 2 - 1) / (CH_THREADS * CH_UNROLL * 2);        // two trips of CH_UNROLL 16-B pieces per lane
+    ga = ga < 1 ? 1 : ga;
+    hipLaunchKernelGGL(color_norm_apply_kernel, dim3(ga, n), dim3(CH_THREADS), 0, stream, bgr_in, bgr_out, nbytes, values256, q_lo,
+                       q_hi, (const unsigned*)counts, range);
     EVR_LAUNCH_CHECK();
     return EVR_OK;
 }

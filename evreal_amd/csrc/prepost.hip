@@ -7,6 +7,7 @@
 // Both are HBM/L2-bound elementwise passes around small reductions; fp32 with one rounding per
 // operation (built with -ffp-contract=off) so the elementwise arithmetic matches numpy/torch.
 #include "common.h"
+#include "pct.h"        // pct_rank, pct_lerp (shared with color.hip)
 #include <cstdlib>
 
 namespace {
@@ -190,16 +191,6 @@ __device__ __forceinline__ unsigned radix_select(const unsigned (&keys)[PCT_MAXR
     return prefix;
 }
 
-// numpy: q = q/100 in the array dtype; virtual index (n-1)*q; method 'linear' (_get_indexes/_get_gamma)
-__device__ __forceinline__ void pct_rank(int n, float q100, int& prev, int& next, float& gamma) {
-    const float q = q100 / 100.0f;
-    const float vi = (float)(n - 1) * q;
-    prev = (int)floorf(vi); next = prev + 1;
-    if (vi >= (float)(n - 1)) { prev = next = n - 1; gamma = vi - (-1.0f); }
-    else if (vi < 0.f) { prev = next = 0; gamma = vi - 0.0f; }
-    else gamma = vi - (float)prev;
-}
-
 // The four selects a frame needs are the two neighbours of each percentile's virtual index.  pair = 0: one work-group per
 // (order statistic, image), all independent (4 x n work-groups; the single-work-group form of round 1 walked them one after
 // the other on 64 of 256 CUs).  pair = 1 (default): one work-group per (percentile, image) -- see below.
@@ -375,11 +366,7 @@ __global__ __launch_bounds__(256) void pct_apply_kernel(float* __restrict__ img,
     for (int which = 0; which < 2; ++which) {   // numpy _lerp
         int prev, next; float gamma;
         pct_rank(n, which ? q_hi : q_lo, prev, next, gamma);
-        const float a = val[2 * which], b = val[2 * which + 1];
-        const float diff = b - a;
-        float r = a + diff * gamma;
-        if (gamma >= 0.5f) r = b - diff * (1.0f - gamma);
-        res[which] = r;
+        res[which] = pct_lerp(val[2 * which], val[2 * which + 1], gamma);
     }
     const float lo = res[0], range = res[1] - res[0];
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) { const float d = v[i] - lo; v[i] = d / range; }

@@ -29,6 +29,7 @@ from .dataset import MemMapDataset
 from .dist import assign_sequences, force_collectives, reduce_metric_sums
 from .eval_metrics import EvalMetricsTracker, MetricTracker
 from .lib import EvrError
+from . import prepost
 from .prepost import normalize_event_tensor, post_process_normalization
 
 CHUNK = 16   # windows voxelised / frames scored per launch
@@ -275,8 +276,6 @@ def _eval_color_sequence(ds, tracker, eval_config, model, method_config, sequenc
         n = len(items)
         grid, stats = ds.voxel_batch(items)
         # eval.py:222-232 with color: normalise the full tensor, no outer pad/crop, ColorNet splits the streams
-        if post_norm != 'none':
-            raise NotImplementedError("colour evaluation supports post_process_norm='none' only")
         if norm_in:
             normalize_event_tensor(grid, stats)
         bgr = [model(grid[j:j + 1])['image'][0] for j in range(n)]
@@ -285,7 +284,10 @@ def _eval_color_sequence(ds, tracker, eval_config, model, method_config, sequenc
                 raise _Saturated()
             model.model.warn_if_saturated(sequence['name']) if hasattr(model, 'model') else model.warn_if_saturated(sequence['name'])
             guard = False
-        tracker.update_batch_color(items, torch.stack(bgr), [float(v) for v in tb['voxel_timestamp'][items]])
+        # post_process_norm acts on the merged BYTES (ColorNet clips every stream to uint8 first): one call per chunk, in place
+        frames = torch.stack(bgr)
+        frames = prepost.color_post_process_normalization(frames, post_norm, out=frames)
+        tracker.update_batch_color(items, frames, [float(v) for v in tb['voxel_timestamp'][items]])
         for i in items:
             cnt, dt = int(tb['event_count'][i]), float(tb['dt'][i])
             tracker.save_custom_metric(i, "event_rate", 0 if (cnt <= 1 or dt == 0) else cnt / dt)

@@ -94,6 +94,9 @@ SYMBOLS = {
     'evr_brisque_features': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'evr_bayer_split': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'evr_color_merge': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'evr_color_percentile_normalize_workspace_bytes': (c_size_t, [c_int]),
+    'evr_color_percentile_normalize': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p,
+                                               c_size_t, c_void_p]),
     'evr_split_pack': (c_int, [c_void_p, c_void_p, c_int64]),
     'evr_split_unpack': (c_int, [c_void_p, c_void_p, c_int64]),
     'evr_split_pack_device': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -36,6 +36,48 @@ def post_process_normalization(img, norm):
     return img
 
 
+_color_values = {}      # (device, exp?) -> float32 [256] on the device: byte level -> image value
+_color_ws = {}          # device -> workspace
+
+
+def color_post_process_normalization(bgr_u8, norm, out=None, return_range=False):
+    """eval.py:380-395 as colour mode applies it: on the merged uint8 BGR frames, cuda uint8 [n,H,W,3] (or [H,W,3]).
+    Per frame img = float32(u8) / 255 (np.exp of that for 'exprobust'), lo / hi = np.percentile over all 3*H*W values together,
+    and the result is the byte the image writer stores, round(clip((img - lo) / (hi - lo), 0, 1) * 255) -- bit-exact against numpy
+    (0/0 = NaN, where hi == lo, is byte 0).  Writes into `out` (default: a new tensor; `out=bgr_u8` works in place) and returns it,
+    with return_range=True also the float32 [n,2] = (lo, hi) of every frame.  'none' returns the input untouched."""
+    if norm not in ('none', 'robust', 'standard', 'exprobust'):
+        raise ValueError(f"Unrecognized normalization argument: {norm}")
+    if norm == 'none':
+        return (bgr_u8, None) if return_range else bgr_u8
+    lib = _lib.load()
+    assert bgr_u8.is_cuda and bgr_u8.dtype == torch.uint8 and bgr_u8.is_contiguous() and bgr_u8.shape[-1] == 3
+    assert bgr_u8.dim() in (3, 4)
+    if out is None:
+        out = torch.empty_like(bgr_u8)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.shape == bgr_u8.shape
+    n = bgr_u8.shape[0] if bgr_u8.dim() == 4 else 1
+    H, W = bgr_u8.shape[-3], bgr_u8.shape[-2]
+    dev, exp = bgr_u8.device, norm == 'exprobust'
+    values = _color_values.get((dev, exp))
+    if values is None:
+        v = np.arange(256).astype(np.uint8).astype(np.float32) / np.float32(255)
+        values = _color_values[(dev, exp)] = torch.from_numpy(np.exp(v) if exp else v).to(dev)
+    need = int(lib.evr_color_percentile_normalize_workspace_bytes(n))
+    ws = _color_ws.get(dev)
+    if return_range or ws is None or ws.numel() * 4 < need:       # (a caller who reads the range keeps its own workspace)
+        ws = torch.empty(max(need, 16) // 4, dtype=torch.int32, device=dev)
+        if not return_range:
+            _color_ws[dev] = ws
+    q = (0.0, 100.0) if norm == 'standard' else (1.0, 99.0)
+    _lib.check(lib.evr_color_percentile_normalize(_lib.ptr(bgr_u8), _lib.ptr(out), n, H, W, _lib.ptr(values), q[0], q[1],
+                                                  _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr()),
+               'evr_color_percentile_normalize')
+    if return_range:
+        return out, ws[n * 256:n * 258].view(torch.float32).view(n, 2)
+    return out
+
+
 class Metrics:
     """MSE + SSIM of utils/eval_metrics.py:77-97 (with the [0,1] clip of :253-255) for a batch of frames."""
 

@@ -349,6 +349,22 @@ int evr_bayer_split(const float* vox, int n, int B, int H, int W, float* out, ev
 int evr_color_merge(const float* planes, const float* gray, int n, int H, int W, unsigned char* bgr_out,
                     evr_stream_t stream);
 
+/* Post-process normalisation of merged colour frames (eval.py:380-395 as colour mode applies it: AFTER the uint8 truncation).
+ * bgr_in / bgr_out: uint8 [n,H,W,3] on the device, any alignment; bgr_out == bgr_in is allowed.  Per frame:
+ *   img = values256[byte]   (the host supplies float32(l)/255 for 'robust' / 'standard', np.exp of that for 'exprobust';
+ *                            non-decreasing in l)
+ *   lo, hi = np.percentile(img, (q_lo, q_hi)) over all 3*H*W values together, float32, method 'linear'
+ *   out = (uint8) rint(clip((img - lo) / (hi - lo), 0, 1) * 255)
+ * computed from the frame's 256-bin histogram: bit-exact against numpy.  hi == lo (a constant frame, or a frame whose two
+ * percentiles fall on one level): values above lo give 255, values below give 0, and the 0/0 = NaN of equal values is DEFINED
+ * as byte 0 (numpy's cast on x86).  3*H*W must be below 2^24 (the float32 rank arithmetic is exact only there).
+ * workspace: evr_color_percentile_normalize_workspace_bytes(n) bytes, 4-byte aligned; the call zeroes what it needs on the
+ * stream and leaves uint32 counts [n][256] followed by float32 {lo, hi} [n][2] in it.  n == 0 is a no-op.
+ * (Joined at ABI version 1005 without a bump, like evr_fr_metrics*: look the symbol up instead.) */
+size_t evr_color_percentile_normalize_workspace_bytes(int n);
+int evr_color_percentile_normalize(const uint8_t* bgr_in, uint8_t* bgr_out, int n, int H, int W, const float* values256,
+                                   float q_lo, float q_hi, void* workspace, size_t workspace_bytes, evr_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Split storage format (host utilities, no GPU): the default arithmetic mode keeps every activation tensor that feeds
  * the matrix cores in 64-byte groups of 16 values: 16 IEEE-half 'hi' (round-to-nearest-even of the value, saturating at
