@@ -816,3 +816,246 @@ extern "C" int evr_brisque_features(evr_brisque* h, const float* img, int n, int
     }
     return brisque_run(h, img, n, H, W, clip, nullptr, out_feat, workspace, workspace_bytes, stream, "evr_brisque_features");
 }
+
+// =====================================================================================================================
+// PIQE (N. Venkatanath, D. Praneeth, M. Chandrasekhar Bh, S. S. Channappayya, S. S. Medasani, "Blind image quality
+// evaluation using perception based features", NCC 2015): the no-reference score of the reference's `-qm piqe` (-> pyiqa),
+// as MATLAB's `piqe` and pyiqa's `piqe` compute it.  Opinion-unaware and training-free: no model file, no weights, no
+// handle.  Conventions (tests/piqe_ref.py states them in the same words):
+//   input     u = rint(255 * clip(v)) in fp32 (half to even), fp64 from here on
+//   padding   bottom and right up to multiples of 16 by edge replication (MATLAB's padarray(..., 'replicate', 'post')),
+//             THEN the filter
+//   MSCN      mu = G*u, sigma = sqrt(|G*(u.u) - mu^2|), m = (u - mu)/(sigma + 1); G: NIQE's 7x7 Gaussian, sigma 7/6, sum 1,
+//             a correlation with a replicate border over the padded image, the 49 taps accumulated row by row
+//   block     per 16 x 16 block of m: var = the unbiased variance of its 256 values (N - 1); active iff var > 0.1
+//   whsa      (noticeable artefacts) the four edges of an active block -- first row, last row, first column, last column --
+//             have 16 values and 11 sliding segments of length 6 each; set iff any of the 44 segments has an unbiased
+//             standard deviation < 0.1
+//   wnc       (noise) centre = the two central columns (0-based 7 and 8, 32 values), surround = the other 14 columns (224
+//             values); r = std(centre)/std(surround), unbiased, a NaN ratio (0/0) becomes 0; sg = sqrt(var),
+//             beta = |sg - r| / max(sg, r); set iff sg > 2 beta
+//   block     contribution: 1 - var if whsa (with or without wnc), var if only wnc, 0 otherwise
+//   score     100 (sum of contributions + 1) / (1 + number of active blocks); a frame with no active block (a constant
+//             frame) scores exactly 100: the formula's own value, not a special case
+//   NaN       comparisons with NaN are false
+// The centre columns and the 'post' padding are this project's reading of the ports, stated here as conventions.
+// (Replicating the padded image's border is replicating the frame's: an index is clamped to the frame, once.)
+// Launches per batch, whatever n: the block kernel (one work-group per 32 x 32 tile = 2 x 2 blocks of one frame, one wave
+// per block; the MSCN map lives in LDS only: the frame is read once) and the finisher (one work-group per frame adds the
+// block records in a fixed order).  No atomics: results are bitwise independent of the batch.
+// Tile: 38 x 39 fp32 + 32 x 33 fp64 = 14.4 KB of LDS -> eight 4-wave work-groups per CU (the 32-wave cap, not LDS, bounds the
+// occupancy), and a 346 x 260 frame is 99 work-groups; a 4 x 4-block tile (52 KB) would leave three per CU and 30 per frame.
+
+namespace {
+
+constexpr int PB = 16;                 // block
+constexpr int PTB = 2;                 // blocks per tile side: one wave per block
+constexpr int PT = PB * PTB;           // tile: PT x PT pixels per work-group
+constexpr unsigned char PIQE_ACTIVE = 1, PIQE_WHSA = 2, PIQE_WNC = 4;
+static_assert(PTB * PTB == NT / 64, "one wave per block");
+
+__device__ __forceinline__ double wave_sum_all(double v) { return __shfl(evr_wave_sum(v), 0, 64); }
+
+// One work-group per (tile, frame).  var / contribution / flags: [n, nby, nbx], blocks in raster order.
+__global__ __launch_bounds__(NT) void piqe_block_kernel(const float* __restrict__ img, int H, int W, int clip, int nby, int nbx,
+                                                        int ntx, Taps taps, double* __restrict__ var_out,
+                                                        double* __restrict__ contribution, unsigned char* __restrict__ flags) {
+    constexpr int TS = PT + 6;
+    __shared__ float tile[TS][TS + 1];
+    __shared__ double m[PT][PT + 1];
+    const int t = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+    const int y0 = (t / ntx) * PT, x0 = (t % ntx) * PT;
+    const float* src = img + (int64_t)f * H * W;
+
+    for (int i = tid; i < TS * TS; i += NT) {
+        const int r = i / TS, c = i % TS;
+        tile[r][c] = quant(src[(int64_t)clampi(y0 + r - 3, H) * W + clampi(x0 + c - 3, W)], clip);
+    }
+    __syncthreads();
+    // four pixels of one row per thread: a row of the neighbourhoods is read, widened and squared once for the four;
+    // each pixel's taps still accumulate row by row, as mscn_at does
+    static_assert(PT * PT == 4 * NT, "four pixels per thread");
+    {
+        const int r = tid / (PT / 4), c = (tid % (PT / 4)) * 4;
+        double mu[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0}, centre[4];
+#pragma unroll
+        for (int dy = 0; dy < 7; ++dy) {
+            double v[10], q[10];
+#pragma unroll
+            for (int k = 0; k < 10; ++k) {
+                v[k] = (double)tile[r + dy][c + k];
+                q[k] = v[k] * v[k];
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                if (dy == 3) centre[p] = v[p + 3];
+#pragma unroll
+                for (int dx = 0; dx < 7; ++dx) {
+                    const double g = taps.g[dy * 7 + dx];
+                    mu[p] = mu[p] + g * v[p + dx];
+                    s2[p] = s2[p] + g * q[p + dx];
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const double sigma = sqrt(fabs(s2[p] - mu[p] * mu[p]));
+            m[r][c + p] = (centre[p] - mu[p]) / (sigma + 1.0);
+        }
+    }
+    __syncthreads();
+
+    const int lane = tid & 63, wave = tid >> 6;
+    const int oy = (wave / PTB) * PB, ox = (wave % PTB) * PB;
+    const int by = (y0 + oy) / PB, bx = (x0 + ox) / PB;
+    if (by >= nby || bx >= nbx) return;                        // a ragged tile: no such block (no barrier follows)
+
+    // lane l holds row l / 4, columns 4 (l % 4) .. + 3; columns 7 and 8 are the last of quarter 1 and the first of quarter 2
+    const int q = lane & 3;
+    const double* row = &m[oy + (lane >> 2)][ox + 4 * q];
+    const double x0v = row[0], x1v = row[1], x2v = row[2], x3v = row[3];
+    const bool c0 = q == 2, c3 = q == 1;                       // x0v / x3v lies in the centre
+    const double sum_c = wave_sum_all((c0 ? x0v : 0.0) + (c3 ? x3v : 0.0));
+    const double sum_s = wave_sum_all((((c0 ? 0.0 : x0v) + x1v) + x2v) + (c3 ? 0.0 : x3v));
+    const double sum_a = wave_sum_all(((x0v + x1v) + x2v) + x3v);
+    const double mean_a = sum_a / 256.0, mean_c = sum_c / 32.0, mean_s = sum_s / 224.0;
+    const double a0 = x0v - mean_a, a1 = x1v - mean_a, a2 = x2v - mean_a, a3 = x3v - mean_a;
+    const double var = wave_sum_all(((a0 * a0 + a1 * a1) + a2 * a2) + a3 * a3) / 255.0;
+    const double e0 = x0v - (c0 ? mean_c : mean_s), e1 = x1v - mean_s, e2 = x2v - mean_s, e3 = x3v - (c3 ? mean_c : mean_s);
+    const double var_c = wave_sum_all((c0 ? e0 * e0 : 0.0) + (c3 ? e3 * e3 : 0.0)) / 31.0;
+    const double var_s = wave_sum_all((((c0 ? 0.0 : e0 * e0) + e1 * e1) + e2 * e2) + (c3 ? 0.0 : e3 * e3)) / 223.0;
+
+    // the 44 edge segments: lane = 11 edge + start
+    bool low = false;
+    if (lane < 44) {
+        const int e = lane / 11, s = lane % 11;
+        const int rr = oy + (e == 1 ? PB - 1 : (e >= 2 ? s : 0)), cc = ox + (e == 3 ? PB - 1 : (e < 2 ? s : 0));
+        const int dr = e >= 2 ? 1 : 0, dc = 1 - dr;
+        double v[6], sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            v[k] = m[rr + k * dr][cc + k * dc];
+            sum = sum + v[k];
+        }
+        const double mean = sum / 6.0;
+        double ssd = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) ssd = ssd + (v[k] - mean) * (v[k] - mean);
+        low = sqrt(ssd / 5.0) < 0.1;
+    }
+    const bool any_low = __any(low ? 1 : 0) != 0;
+
+    if (lane == 0) {
+        unsigned char fl = 0;
+        double contrib = 0.0;
+        if (var > 0.1) {
+            double r = sqrt(var_c) / sqrt(var_s);
+            if (isnan(r)) r = 0.0;
+            const double sg = sqrt(var);
+            const double beta = fabs(sg - r) / (sg > r ? sg : r);
+            const bool whsa = any_low, wnc = sg > 2.0 * beta;
+            fl = PIQE_ACTIVE | (whsa ? PIQE_WHSA : 0) | (wnc ? PIQE_WNC : 0);
+            contrib = whsa ? 1.0 - var : (wnc ? var : 0.0);
+        }
+        const int64_t o = ((int64_t)f * nby + by) * nbx + bx;
+        var_out[o] = var;
+        contribution[o] = contrib;
+        flags[o] = fl;
+    }
+}
+
+// One work-group per frame: the block records in a fixed order (thread t takes blocks t, t + 256, ...; then the waves).
+__global__ __launch_bounds__(NT) void piqe_finish_kernel(const double* __restrict__ contribution,
+                                                         const unsigned char* __restrict__ flags, int nb,
+                                                         double* __restrict__ scores) {
+    __shared__ double red[NT / 64];
+    __shared__ int cnt[NT / 64];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    double s = 0.0;
+    int c = 0;
+    for (int b = tid; b < nb; b += NT) {
+        s += contribution[(int64_t)f * nb + b];
+        c += flags[(int64_t)f * nb + b] & PIQE_ACTIVE;
+    }
+    s = evr_wave_sum(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((tid & 63) == 0) { red[tid >> 6] = s; cnt[tid >> 6] = c; }
+    __syncthreads();
+    if (tid == 0) {
+        const double sum = ((red[0] + red[1]) + red[2]) + red[3];
+        const int active = ((cnt[0] + cnt[1]) + cnt[2]) + cnt[3];
+        scores[f] = 100.0 * ((sum + 1.0) / (1.0 + (double)active));
+    }
+}
+
+struct PDims {
+    int nby, nbx, nb, ntx, nt;
+    size_t var_bytes, contrib_bytes, flag_bytes;
+};
+
+PDims pdims(int n, int H, int W) {
+    PDims d;
+    d.nby = (H + PB - 1) / PB; d.nbx = (W + PB - 1) / PB;
+    d.nb = d.nby * d.nbx;
+    d.ntx = (d.nbx + PTB - 1) / PTB;
+    d.nt = ((d.nby + PTB - 1) / PTB) * d.ntx;
+    d.var_bytes = evr::align_up((size_t)n * d.nb * sizeof(double), 256);
+    d.contrib_bytes = d.var_bytes;
+    d.flag_bytes = evr::align_up((size_t)n * d.nb, 256);
+    return d;
+}
+
+const Taps& piqe_taps() {
+    static const Taps t = gaussian_taps();
+    return t;
+}
+
+}  // namespace
+
+extern "C" size_t evr_piqe_workspace_bytes(int n, int H, int W) {
+    if (n < 1 || H < 1 || W < 1) return 0;
+    const PDims d = pdims(n, H, W);
+    return d.var_bytes + d.contrib_bytes + d.flag_bytes + 256;
+}
+
+static int piqe_run(const float* img, int n, int H, int W, int clip, double* scores, double* out_var, unsigned char* out_flags,
+                    void* ws, size_t ws_bytes, evr_stream_t stream_, const char* what) {
+    hipStream_t stream = (hipStream_t)stream_;
+    EVR_REQUIRE(n >= 1 && n <= 65535 && H >= 1 && W >= 1, "%s: bad shape n=%d H=%d W=%d", what, n, H, W);
+    EVR_REQUIRE((int64_t)H * W <= (int64_t)1 << 30, "%s: %d x %d frame is too large", what, H, W);
+    EVR_REQUIRE(img && (scores || (out_var && out_flags)), "%s: null pointer", what);
+    const size_t need = evr_piqe_workspace_bytes(n, H, W);
+    if (!ws || ws_bytes < need) {
+        evr::set_error("%s: workspace %zu B < required %zu B", what, ws_bytes, need);
+        return EVR_ERR_WORKSPACE;
+    }
+    const PDims d = pdims(n, H, W);
+    char* p = (char*)ws;
+    double* var = (double*)p; p += d.var_bytes;
+    double* contrib = (double*)p; p += d.contrib_bytes;
+    unsigned char* flags = (unsigned char*)p;
+    if (out_var) var = out_var;
+    if (out_flags) flags = out_flags;
+    hipLaunchKernelGGL(piqe_block_kernel, dim3(d.nt, n), dim3(NT), 0, stream, img, H, W, clip, d.nby, d.nbx, d.ntx, piqe_taps(), var,
+                       contrib, flags);
+    EVR_LAUNCH_CHECK();
+    if (scores) {
+        hipLaunchKernelGGL(piqe_finish_kernel, dim3(n), dim3(NT), 0, stream, (const double*)contrib, (const unsigned char*)flags,
+                           d.nb, scores);
+        EVR_LAUNCH_CHECK();
+    }
+    return EVR_OK;
+}
+
+extern "C" int evr_piqe_score(const float* img, int n, int H, int W, int clip, double* out_scores, void* workspace,
+                              size_t workspace_bytes, evr_stream_t stream) {
+    EVR_REQUIRE(out_scores, "evr_piqe_score: null pointer");
+    return piqe_run(img, n, H, W, clip, out_scores, nullptr, nullptr, workspace, workspace_bytes, stream, "evr_piqe_score");
+}
+
+extern "C" int evr_piqe_blocks(const float* img, int n, int H, int W, int clip, double* out_var, unsigned char* out_flags,
+                               void* workspace, size_t workspace_bytes, evr_stream_t stream) {
+    EVR_REQUIRE(out_var && out_flags, "evr_piqe_blocks: null pointer");
+    return piqe_run(img, n, H, W, clip, nullptr, out_var, out_flags, workspace, workspace_bytes, stream, "evr_piqe_blocks");
+}

@@ -303,7 +303,7 @@ class _ChunkBuffers:
     """Device + pinned host buffers of one in-flight chunk (the frame loop keeps two: while the host books chunk c, the
     GPU already works on chunk c + 1)."""
 
-    def __init__(self, S, B, H, W, dev, want_scores, want_lpips, want_u8, with_refs, want_niqe=False, want_brisque=False, want_fr=False):
+    def __init__(self, S, B, H, W, dev, want_scores, want_lpips, want_u8, with_refs, want_niqe=False, want_brisque=False, want_fr=False, want_piqe=False):
         f32 = dict(dtype=torch.float32, device=dev)
         self.grid = torch.empty((CHUNK, S, B, H, W), **f32)
         self.stats = torch.zeros((CHUNK, S, 3), dtype=torch.float64, device=dev)
@@ -317,6 +317,8 @@ class _ChunkBuffers:
         self.h_nq = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_niqe else None
         self.bq = torch.zeros((CHUNK * S,), dtype=torch.float64, device=dev) if want_brisque else None
         self.h_bq = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_brisque else None
+        self.pq = torch.zeros((CHUNK * S,), dtype=torch.float64, device=dev) if want_piqe else None
+        self.h_pq = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_piqe else None
         self.fr = torch.zeros((CHUNK * S, 2), dtype=torch.float64, device=dev) if want_fr else None      # psnr, ms_ssim
         self.h_fr = torch.empty((CHUNK * S, 2), dtype=torch.float64).pin_memory() if want_fr else None
         self.u8 = torch.empty((CHUNK, S, H, W), dtype=torch.uint8, device=dev) if want_u8 else None
@@ -336,7 +338,7 @@ def eval_method_on_sequences(dataset_name, eval_config, method_name, model, meth
 
     The loop is a two-deep pipeline over chunks of CHUNK steps: ONE tensorizer launch voxelizes the chunk's windows of all
     slots (their events share one resident array, dataset.SequenceBatch) straight into the step-major batch tensor; the
-    network steps run back to back on the main stream; post-normalisation, MSE/SSIM/LPIPS/PSNR/MS-SSIM/NIQE of every frame of the chunk and
+    network steps run back to back on the main stream; post-normalisation, MSE/SSIM/LPIPS/PSNR/MS-SSIM/NIQE/BRISQUE/PIQE of every frame of the chunk and
     the uint8 conversion for the PNG writers run on a second HIP stream (as pipeline.HotPath does per step) and land in
     pinned host memory; the host books chunk c (text files, PNG pool) while the GPU is already inside chunk c + 1.
     Returns [(num_evaluated, mean_scores)] in the order of `sequences`.
@@ -377,13 +379,14 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
     lp_model = EvalMetricsTracker._lpips_model() if 'lpips' in pre else None
     nq_model = EvalMetricsTracker._niqe_model() if 'niqe' in pre else None
     bq_model = EvalMetricsTracker._brisque_model() if 'brisque' in pre else None
+    pq_model = EvalMetricsTracker._piqe_model() if 'piqe' in pre else None
     gpu_metrics = trackers[0]._gpu
     # psnr / ms_ssim: one launch set for both; ms_ssim is left out where the frames are too small for it (decided from the shape:
     # the trackers print the exception and reset the metric, as the reference does for a metric that raises)
     fr_metrics = trackers[0]._fr
     fr_psnr, fr_ms = 'psnr' in pre, 'ms_ssim' in pre and fr_metrics.too_small(H, W) is None
     bufs = [_ChunkBuffers(S, batch.num_bins, H, W, dev, bool(set(pre) & {'mse', 'ssim'}), lp_model is not None, want_u8,
-                          all(ds.has_images for ds in dss), nq_model is not None, bq_model is not None, fr_psnr or fr_ms) for _ in range(2)]
+                          all(ds.has_images for ds in dss), nq_model is not None, bq_model is not None, fr_psnr or fr_ms, pq_model is not None) for _ in range(2)]
     main = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(device=dev)
     policy = _range_guard_policy(eval_config)
@@ -430,6 +433,9 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
             if b.bq is not None:
                 bq_model(im, clip=True, out=b.bq[:n * S])
                 b.h_bq[:n * S].copy_(b.bq[:n * S], non_blocking=True)
+            if b.pq is not None:
+                pq_model(im, clip=True, out=b.pq[:n * S])
+                b.h_pq[:n * S].copy_(b.pq[:n * S], non_blocking=True)
             if b.u8 is not None:
                 b.u8[:n].copy_(torch.round(torch.clamp(b.imgs[:n, :, 0], 0.0, 1.0) * 255))     # eval_utils.py:83
                 b.h_u8[:n].copy_(b.u8[:n], non_blocking=True)
@@ -448,6 +454,7 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
         lp = b.h_lp[:n * S].numpy().reshape(n, S) if b.h_lp is not None else None
         nq = b.h_nq[:n * S].numpy().reshape(n, S) if b.h_nq is not None else None
         bq = b.h_bq[:n * S].numpy().reshape(n, S) if b.h_bq is not None else None
+        pq = b.h_pq[:n * S].numpy().reshape(n, S) if b.h_pq is not None else None
         fr = b.h_fr[:n * S].numpy().reshape(n, S, 2) if b.h_fr is not None else None
         for j in range(S):
             it = b.items[j]
@@ -462,6 +469,7 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
                 if 'lpips' in pre and lp is not None: scores['lpips'] = lp[:k, j].copy()
                 if 'niqe' in pre and nq is not None: scores['niqe'] = nq[:k, j].copy()
                 if 'brisque' in pre and bq is not None: scores['brisque'] = bq[:k, j].copy()
+                if 'piqe' in pre and pq is not None: scores['piqe'] = pq[:k, j].copy()
                 if fr_psnr and fr is not None: scores['psnr'] = fr[:k, j, 0].copy()
                 if fr_ms and fr is not None: scores['ms_ssim'] = fr[:k, j, 1].copy()
             u8 = b.h_u8[:k, j] if b.h_u8 is not None else None      # (a strided view of the pinned buffer: the native writers copy it inside the call)

@@ -13,6 +13,8 @@ Metric plug-ins keep the reference's contract (utils/eval_metrics.py:18-75): a `
     same lines;
   * 'psnr' and 'ms_ssim' (full-reference, closed form: no file needed) run batched on the GPU in fp64 (evr_fr_metrics) and are
     booked through the same four-frame queue; EVREAL_GPU_FR_METRICS=0 sends the two names to pyiqa instead;
+  * 'piqe' (no-reference, training-free: no file needed) runs batched on the GPU in fp64 (evr_piqe_*) and is booked through
+    the same four-frame queue; EVREAL_GPU_PIQE=0 sends the name to pyiqa instead;
   * anything registered with `register_metric(name, factory)` runs per frame on host arrays, exactly like the reference's
     MseMetric / SsimMetric (clipped float32 [H,W] images in, a float or a list of floats out);
   * any other name is looked up in pyiqa.list_models() when pyiqa is importable (queued in batches of 4 as
@@ -33,6 +35,7 @@ from .prepost import FullRefMetrics, Metrics, histogram_equalization
 GPU_METRICS = ('mse', 'ssim')
 FR_METRICS = ('psnr', 'ms_ssim')                # full-reference, closed form, queued like the reference's pyiqa metrics
 FR_METRICS_ENV = 'EVREAL_GPU_FR_METRICS'        # '0': psnr / ms_ssim go to pyiqa (or are unknown without it)
+PIQE_ENV = 'EVREAL_GPU_PIQE'                    # '0': piqe goes to pyiqa (or is unknown without it)
 LPIPS_WEIGHTS_ENV = 'EVREAL_LPIPS_WEIGHTS'      # path to a pyiqa/lpips AlexNet-v0.1 state_dict (torch.save'd)
 NIQE_MODEL_ENV = 'EVREAL_NIQE_MODEL'            # path to a NIQE pristine model (.mat of the MATLAB release, or .npz)
 NIQE_MODEL_FILES = (os.path.join('pretrained', 'niqe_modelparameters.mat'), os.path.join('pretrained', 'niqe_model.npz'))
@@ -51,6 +54,10 @@ def _load_lpips():
 
 def gpu_fr_metrics_enabled():
     return os.environ.get(FR_METRICS_ENV, '1') != '0'
+
+
+def gpu_piqe_enabled():
+    return os.environ.get(PIQE_ENV, '1') != '0'
 
 
 def niqe_model_path():
@@ -306,6 +313,8 @@ class EvalMetricsTracker:
                 self.metrics.append(_REGISTRY[name]())
             elif name in FR_METRICS and gpu_fr_metrics_enabled():
                 self.metrics.append(QueuedGpuMetric(name, no_ref=False))
+            elif name == 'piqe' and gpu_piqe_enabled():
+                self.metrics.append(QueuedGpuMetric(name, no_ref=True))
             elif name in pyiqa_metric_factory().list_of_metrics:
                 self.metrics.append(pyiqa_metric_factory().get_metric(name))
             else:
@@ -345,6 +354,16 @@ class EvalMetricsTracker:
         if not cls._brisque_cache[0]:
             cls._brisque_cache = [True, _load_brisque()]
         return cls._brisque_cache[1]
+
+    _piqe_cache = [None]
+
+    @classmethod
+    def _piqe_model(cls):
+        """One PIQE object (its workspace) per process; there is no model file."""
+        if cls._piqe_cache[0] is None:
+            from .nriqa import PIQE
+            cls._piqe_cache[0] = PIQE()
+        return cls._piqe_cache[0]
 
     # -- files --------------------------------------------------------------------------------
     def reset(self):
@@ -464,13 +483,14 @@ class EvalMetricsTracker:
             rsel = refs[js].contiguous() if refs is not None else None
         if gpu:
             want = {m.name for m in gpu}
-            scores = lp = nq = bq = fr = None
+            scores = lp = nq = bq = pq = fr = None
             if not have_pre:
                 if want & set(GPU_METRICS):
                     scores = self._gpu(isel, rsel, mse='mse' in want, ssim='ssim' in want, clip=True).cpu().numpy()
                 lp = self._lpips_model()(isel, rsel, clip=True).cpu().numpy() if 'lpips' in want else None
                 nq = self._niqe_model()(isel, clip=True).cpu().numpy() if 'niqe' in want else None
                 bq = self._brisque_model()(isel, clip=True).cpu().numpy() if 'brisque' in want else None
+                pq = self._piqe_model()(isel, clip=True).cpu().numpy() if 'piqe' in want else None
                 if want & set(FR_METRICS):
                     fr = self._fr(isel, rsel, psnr='psnr' in want, ms_ssim='ms_ssim' in want, clip=True).cpu().numpy()
             for m in gpu:
@@ -478,7 +498,7 @@ class EvalMetricsTracker:
                     col = np.asarray(pre[m.name])[sel]
                 else:
                     col = (scores[:, 0] if m.name == 'mse' else scores[:, 1] if m.name == 'ssim' else nq if m.name == 'niqe'
-                           else bq if m.name == 'brisque' else fr[:, 0] if m.name == 'psnr'
+                           else bq if m.name == 'brisque' else pq if m.name == 'piqe' else fr[:, 0] if m.name == 'psnr'
                            else fr[:, 1] if m.name == 'ms_ssim' else lp)
                 if isinstance(m, QueuedGpuMetric):
                     self._append(join(self.output_dir, m.name + '.txt'), m.book(self.quan_eval_indices, idxs, col))

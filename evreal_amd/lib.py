@@ -92,6 +92,9 @@ SYMBOLS = {
     'evr_brisque_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'evr_brisque_score': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'evr_brisque_features': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'evr_piqe_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'evr_piqe_score': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'evr_piqe_blocks': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'evr_bayer_split': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'evr_color_merge': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'evr_color_percentile_normalize_workspace_bytes': (c_size_t, [c_int]),

@@ -1,6 +1,7 @@
-"""No-reference image quality on the GPU: NIQE (Mittal, Soundararajan, Bovik 2013) and BRISQUE (Mittal, Moorthy, Bovik
-2012), the `-qm niqe` / `-qm brisque` of the reference's no-reference datasets (utils/eval_metrics.py:100-156, 205-208 ->
-pyiqa), through evr_niqe_* and evr_brisque_* (csrc/nriqa.hip).
+"""No-reference image quality on the GPU: NIQE (Mittal, Soundararajan, Bovik 2013), BRISQUE (Mittal, Moorthy, Bovik
+2012) and PIQE (Venkatanath et al. 2015), the `-qm niqe` / `-qm brisque` / `-qm piqe` of the reference's no-reference
+datasets (utils/eval_metrics.py:100-156, 205-208 -> pyiqa), through evr_niqe_*, evr_brisque_* and evr_piqe_*
+(csrc/nriqa.hip).  PIQE is training-free: it needs no file.
 
 The pristine model is a 36-vector and a 36x36 covariance.  Offline it comes from a file:
   * the published MATLAB release's (or pyiqa's cached) `niqe_modelparameters.mat`: keys mu_prisparam, cov_prisparam;
@@ -365,6 +366,49 @@ def brisque_features(img, clip=True):
                                                     fmin=np.zeros(NUM_FEATURES), fmax=np.ones(NUM_FEATURES), lower=-1.0,
                                                     upper=1.0, source='features only')))
     return _brisque_feature_handle[0].features(img, clip)
+
+
+PIQE_BLOCK = 16
+PIQE_ACTIVE, PIQE_WHSA, PIQE_WNC = 1, 2, 4      # the bits of a block's flag byte
+
+
+class PIQE:
+    """PIQE scores of cuda fp32 frames [n,H,W] -> cuda fp64 [n] (100 for a frame without an active block, e.g. a constant
+    one).  No model: the metric is training-free.  The workspace is kept between calls."""
+
+    def __init__(self):
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.ws = None
+
+    def _workspace(self, n, H, W, device):
+        need = int(self.lib.evr_piqe_workspace_bytes(n, H, W))
+        if self.ws is None or self.ws.numel() < need or self.ws.device != device:
+            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
+        return self.ws
+
+    def __call__(self, img, clip=True, out=None):
+        v = _as_frames(img)
+        n, H, W = v.shape
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=v.device)
+        ws = self._workspace(n, H, W, v.device)
+        _lib.check(self.lib.evr_piqe_score(_lib.ptr(v), n, H, W, 1 if clip else 0, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_ptr()), 'evr_piqe_score')
+        return out
+
+    def blocks(self, img, clip=True):
+        """-> (var cuda fp64 [n, ceil(H/16), ceil(W/16)], flags cuda uint8 of the same shape: PIQE_ACTIVE | PIQE_WHSA |
+        PIQE_WNC).  MATLAB's activityMask / noticeableArtifactsMask / noiseMask are these bits spread over 16x16 pixels."""
+        v = _as_frames(img)
+        n, H, W = v.shape
+        shape = (n, -(-H // PIQE_BLOCK), -(-W // PIQE_BLOCK))
+        var = torch.empty(shape, dtype=torch.float64, device=v.device)
+        flags = torch.empty(shape, dtype=torch.uint8, device=v.device)
+        ws = self._workspace(n, H, W, v.device)
+        _lib.check(self.lib.evr_piqe_blocks(_lib.ptr(v), n, H, W, 1 if clip else 0, _lib.ptr(var), _lib.ptr(flags), _lib.ptr(ws),
+                                            ws.numel(), _lib.stream_ptr()), 'evr_piqe_blocks')
+        return var, flags
 
 
 def _sequence_frames(path, device, chunk=64):

@@ -38,7 +38,7 @@ enum evr_status {
 
 /* Message for the last failure on this thread ("" if none). */
 const char* evr_last_error(void);
-/* ABI version (major*1000 + minor).  1005: evr_brisque_*; evr_fr_metrics* joined later without a bump (tests/test_brisque_cpu.py pins this number: look the symbol up instead).  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
+/* ABI version (major*1000 + minor).  1005: evr_brisque_*; evr_fr_metrics* and evr_piqe_* joined later without a bump (tests/test_brisque_cpu.py pins this number: look the symbol up instead).  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
  * 1001 (round 4): evr_percentile_normalize rejects a NULL workspace (size it with
  * evr_percentile_normalize_workspace_bytes); evr_model_arith reports the mode the convolutions actually run (FireNet's 16-channel
  * layers: h3 whatever EVR_ARITH says). */
@@ -335,6 +335,30 @@ int evr_brisque_score(evr_brisque* h, const float* img, int n, int H, int W, int
                       void* workspace, size_t workspace_bytes, evr_stream_t stream);
 int evr_brisque_features(evr_brisque* h, const float* img, int n, int H, int W, int clip, double* out_feat,
                          void* workspace, size_t workspace_bytes, evr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * PIQE (Venkatanath et al., NCC 2015), the no-reference score of `-qm piqe` for datasets without frames (-> pyiqa in the
+ * reference), as MATLAB's and pyiqa's `piqe` compute it.  Opinion-unaware and training-free: no model file, hence no
+ * handle.  Conventions (csrc/nriqa.hip, tests/piqe_ref.py): u = rint(255 * v) in fp32 (v clamped to [0,1] first when
+ * clip != 0), fp64 from there on; the frame padded at the bottom and right to multiples of 16 by edge replication; MSCN
+ * with NIQE's replicate-padded 7x7 Gaussian; per 16x16 block the unbiased variance (active iff > 0.1), the
+ * noticeable-artefact criterion (any of the 44 length-6 edge segments with an unbiased deviation < 0.1) and the noise
+ * criterion (centre columns 7 and 8 against the other 14); score = 100 (sum of block contributions + 1) / (1 + active
+ * blocks).  A frame without an active block (a constant one) scores exactly 100.
+ * evr_piqe_score: img [n,H,W] fp32 -> out_scores double [n].
+ * evr_piqe_blocks: img [n,H,W] fp32 -> out_var double [n, ceil(H/16), ceil(W/16)] (the block variances) and out_flags,
+ *   one byte per block: bit 0 active, bit 1 noticeable artefacts, bit 2 noise (MATLAB's activityMask,
+ *   noticeableArtifactsMask and noiseMask are these bits spread over the block's pixels).
+ * Two launches per call whatever n (evr_piqe_blocks: one), no host synchronisation; results are bitwise independent of n
+ * and of a frame's position in the batch.  All pointers are caller-owned device memory.  Refused before any launch: a
+ * null pointer, n <= 0 or n > 65535, H or W < 1, a workspace shorter than evr_piqe_workspace_bytes(n, H, W) (which is 0
+ * for such a shape).
+ */
+size_t evr_piqe_workspace_bytes(int n, int H, int W);
+int evr_piqe_score(const float* img, int n, int H, int W, int clip, double* out_scores, void* workspace,
+                   size_t workspace_bytes, evr_stream_t stream);
+int evr_piqe_blocks(const float* img, int n, int H, int W, int clip, double* out_var, unsigned char* out_flags,
+                    void* workspace, size_t workspace_bytes, evr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Colour reconstruction (ColorNet, model/model.py:46-105; merge utils/color_utils.py:53-88).
