@@ -15,6 +15,8 @@ Metric plug-ins keep the reference's contract (utils/eval_metrics.py:18-75): a `
     booked through the same four-frame queue; EVREAL_GPU_FR_METRICS=0 sends the two names to pyiqa instead;
   * 'piqe' (no-reference, training-free: no file needed) runs batched on the GPU in fp64 (evr_piqe_*) and is booked through
     the same four-frame queue; EVREAL_GPU_PIQE=0 sends the name to pyiqa instead;
+  * 'gmsd' (full-reference, closed form: no file needed) runs batched on the GPU in fp64 (evr_gmsd) and is booked through the
+    same four-frame queue; EVREAL_GPU_GMSD=0 sends the name to pyiqa instead;
   * anything registered with `register_metric(name, factory)` runs per frame on host arrays, exactly like the reference's
     MseMetric / SsimMetric (clipped float32 [H,W] images in, a float or a list of floats out);
   * any other name is looked up in pyiqa.list_models() when pyiqa is importable (queued in batches of 4 as
@@ -30,12 +32,13 @@ from os.path import join
 import numpy as np
 import torch
 
-from .prepost import FullRefMetrics, Metrics, histogram_equalization
+from .prepost import GMSD, FullRefMetrics, Metrics, histogram_equalization
 
 GPU_METRICS = ('mse', 'ssim')
 FR_METRICS = ('psnr', 'ms_ssim')                # full-reference, closed form, queued like the reference's pyiqa metrics
 FR_METRICS_ENV = 'EVREAL_GPU_FR_METRICS'        # '0': psnr / ms_ssim go to pyiqa (or are unknown without it)
 PIQE_ENV = 'EVREAL_GPU_PIQE'                    # '0': piqe goes to pyiqa (or is unknown without it)
+GMSD_ENV = 'EVREAL_GPU_GMSD'                    # '0': gmsd goes to pyiqa (or is unknown without it)
 LPIPS_WEIGHTS_ENV = 'EVREAL_LPIPS_WEIGHTS'      # path to a pyiqa/lpips AlexNet-v0.1 state_dict (torch.save'd)
 NIQE_MODEL_ENV = 'EVREAL_NIQE_MODEL'            # path to a NIQE pristine model (.mat of the MATLAB release, or .npz)
 NIQE_MODEL_FILES = (os.path.join('pretrained', 'niqe_modelparameters.mat'), os.path.join('pretrained', 'niqe_model.npz'))
@@ -58,6 +61,10 @@ def gpu_fr_metrics_enabled():
 
 def gpu_piqe_enabled():
     return os.environ.get(PIQE_ENV, '1') != '0'
+
+
+def gpu_gmsd_enabled():
+    return os.environ.get(GMSD_ENV, '1') != '0'
 
 
 def niqe_model_path():
@@ -315,6 +322,8 @@ class EvalMetricsTracker:
                 self.metrics.append(QueuedGpuMetric(name, no_ref=False))
             elif name == 'piqe' and gpu_piqe_enabled():
                 self.metrics.append(QueuedGpuMetric(name, no_ref=True))
+            elif name == 'gmsd' and gpu_gmsd_enabled():
+                self.metrics.append(QueuedGpuMetric(name, no_ref=False))
             elif name in pyiqa_metric_factory().list_of_metrics:
                 self.metrics.append(pyiqa_metric_factory().get_metric(name))
             else:
@@ -324,6 +333,7 @@ class EvalMetricsTracker:
         self.only_no_ref = all(m.no_ref for m in self.metrics)
         self._gpu = Metrics()
         self._fr = FullRefMetrics()
+        self._gmsd = GMSD()
         self.reset()
 
     _lpips_cache = [False, None]
@@ -424,12 +434,13 @@ class EvalMetricsTracker:
         return [m.name for m in self.metrics if getattr(m, 'on_gpu', False)]
 
     def _shape_refused(self, m, imgs):
-        """A GPU metric that is not defined on frames of this size (ms_ssim below 161 pixels a side) ends like a metric that
+        """A GPU metric that is not defined on frames of this size (ms_ssim below 161 pixels a side, gmsd below 2) ends like a metric that
         raises on every frame in the reference (utils/eval_metrics.py:233-242: the exception is printed, the metric reset): its
         file stays empty and its mean is -1.  Decided from the shape, before any launch, and printed once per sequence."""
         if m.name in self._failed:
             return True
-        why = FullRefMetrics.too_small(int(imgs.shape[-2]), int(imgs.shape[-1])) if m.name == 'ms_ssim' else None
+        H, W = int(imgs.shape[-2]), int(imgs.shape[-1])
+        why = FullRefMetrics.too_small(H, W) if m.name == 'ms_ssim' else GMSD.too_small(H, W) if m.name == 'gmsd' else None
         if why is None:
             return False
         print("Exception in metric " + m.get_name() + ": " + why)
@@ -483,7 +494,7 @@ class EvalMetricsTracker:
             rsel = refs[js].contiguous() if refs is not None else None
         if gpu:
             want = {m.name for m in gpu}
-            scores = lp = nq = bq = pq = fr = None
+            scores = lp = nq = bq = pq = fr = gm = None
             if not have_pre:
                 if want & set(GPU_METRICS):
                     scores = self._gpu(isel, rsel, mse='mse' in want, ssim='ssim' in want, clip=True).cpu().numpy()
@@ -493,13 +504,14 @@ class EvalMetricsTracker:
                 pq = self._piqe_model()(isel, clip=True).cpu().numpy() if 'piqe' in want else None
                 if want & set(FR_METRICS):
                     fr = self._fr(isel, rsel, psnr='psnr' in want, ms_ssim='ms_ssim' in want, clip=True).cpu().numpy()
+                gm = self._gmsd(isel, rsel, clip=True).cpu().numpy() if 'gmsd' in want else None
             for m in gpu:
                 if have_pre:
                     col = np.asarray(pre[m.name])[sel]
                 else:
                     col = (scores[:, 0] if m.name == 'mse' else scores[:, 1] if m.name == 'ssim' else nq if m.name == 'niqe'
                            else bq if m.name == 'brisque' else pq if m.name == 'piqe' else fr[:, 0] if m.name == 'psnr'
-                           else fr[:, 1] if m.name == 'ms_ssim' else lp)
+                           else fr[:, 1] if m.name == 'ms_ssim' else gm if m.name == 'gmsd' else lp)
                 if isinstance(m, QueuedGpuMetric):
                     self._append(join(self.output_dir, m.name + '.txt'), m.book(self.quan_eval_indices, idxs, col))
                     continue

@@ -151,7 +151,60 @@ class FullRefMetrics:
         return self(img, ref, psnr=psnr, ms_ssim=True, clip=clip, out_scales=scales), scales
 
 
-HISTEQ_MODES = {'none': 0, 'global': 1, 'local': 2, 'clahe': 3}
+class GMSD:
+    """GMSD (Xue et al. 2014; pyiqa's `gmsd`) for a batch of frame pairs, in fp64 (evr_gmsd): frames quantised to
+    rint(255 * clip(v)), 2x2 mean pooling, Prewitt / 3 with zero padding, GMS with c = 170, the standard deviation over the
+    pooled pixels with N - 1.  Constructing one touches neither the library nor the GPU; the workspace is owned and grows on
+    demand."""
+    MIN_SIDE = 2            # one pixel of the 2x2-pooled plane
+
+    def __init__(self):
+        self.lib = None
+        self.ws = None
+
+    @classmethod
+    def too_small(cls, H, W):
+        """The message of the exception `gmsd` raises on frames of this size, or None where it is defined."""
+        if min(H, W) >= cls.MIN_SIDE:
+            return None
+        return f"gmsd needs frames of at least {cls.MIN_SIDE}x{cls.MIN_SIDE} pixels (it pools 2x2 first), got {H}x{W}"
+
+    def stats(self, img, ref, clip=True, out=None, out_map=None):
+        """img, ref: cuda float32 [n,H,W] (or [H,W]) -> float64 [n,2] = (score, mean GMS).
+        out / out_map: optional contiguous float64 [n,2] / [n,H//2,W//2] to write into (out_map: the GMS map q)."""
+        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dtype == ref.dtype == torch.float32
+        img = img.contiguous(); ref = ref.contiguous()
+        v = img if img.dim() == 3 else img.reshape(-1, img.shape[-2], img.shape[-1])
+        n, H, W = v.shape
+        if self.too_small(H, W):
+            raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
+        if self.lib is None:
+            self.lib = _lib.load()
+        need = self.lib.evr_gmsd_workspace_bytes(n, H, W)
+        if self.ws is None or self.ws.numel() < need or self.ws.device != img.device:
+            self.ws = torch.empty(need, dtype=torch.uint8, device=img.device)
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float64, device=img.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n, 2)
+        if out_map is not None:
+            assert (out_map.is_cuda and out_map.dtype == torch.float64 and out_map.is_contiguous()
+                    and tuple(out_map.shape) == (n, H // 2, W // 2))
+        _lib.check(self.lib.evr_gmsd(_lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0, _lib.ptr(out), _lib.ptr(out_map),
+                                     _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()), 'evr_gmsd')
+        return out
+
+    def __call__(self, img, ref, clip=True, out=None):
+        """-> float64 [n] scores.  out: optional float64 [n,2] (score, mean GMS) to write into; its first column is returned."""
+        return self.stats(img, ref, clip=clip, out=out)[:, 0]
+
+    def map(self, img, ref, clip=True):
+        """-> (stats [n,2], GMS map [n,H//2,W//2])."""
+        n = 1 if img.dim() == 2 else int(np.prod(img.shape[:-2]))
+        q = torch.empty((n, img.shape[-2] // 2, img.shape[-1] // 2), dtype=torch.float64, device=img.device)
+        return self.stats(img, ref, clip=clip, out_map=q), q
+
+
+HISTEQ_MODES ={'none': 0, 'global': 1, 'local': 2, 'clahe': 3}
 _histeq_ws = {}
 
 

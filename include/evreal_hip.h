@@ -38,7 +38,7 @@ enum evr_status {
 
 /* Message for the last failure on this thread ("" if none). */
 const char* evr_last_error(void);
-/* ABI version (major*1000 + minor).  1005: evr_brisque_*; evr_fr_metrics* and evr_piqe_* joined later without a bump (tests/test_brisque_cpu.py pins this number: look the symbol up instead).  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
+/* ABI version (major*1000 + minor).  1005: evr_brisque_*; evr_fr_metrics*, evr_piqe_* and evr_gmsd* joined later without a bump (tests/test_brisque_cpu.py pins this number: look the symbol up instead).  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
  * 1001 (round 4): evr_percentile_normalize rejects a NULL workspace (size it with
  * evr_percentile_normalize_workspace_bytes); evr_model_arith reports the mode the convolutions actually run (FireNet's 16-channel
  * layers: h3 whatever EVR_ARITH says). */
@@ -265,6 +265,22 @@ size_t evr_metrics_workspace_bytes(int n, int H, int W);
 size_t evr_fr_metrics_workspace_bytes(int n, int H, int W);
 int evr_fr_metrics(const float* img, const float* ref, int n, int H, int W, unsigned which, int clip, double* out_scores,
                    double* out_scales, void* workspace, size_t workspace_bytes, evr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Full-reference GMSD per frame, in fp64, with its map.  Replaces PyIqaMetricFactory.get_metric('gmsd')
+ * (utils/eval_metrics.py:195-203): Xue, Zhang, Mou & Bovik, IEEE TIP 2014.  Both frames are quantised to
+ * u = rint(255 * clip(v, 0, 1)), pooled by a 2x2 mean of stride 2 (h2 = H / 2, w2 = W / 2: a trailing odd row or column is
+ * dropped), differentiated with Prewitt / 3 under one pixel of zero padding, g = sqrt(gx^2 + gy^2 + 1e-12);
+ * GMS q = (2 g_img g_ref + 170) / (g_img^2 + g_ref^2 + 170); the score is the standard deviation of q over the h2 * w2 pooled
+ * pixels with N - 1 in the denominator (NaN for N == 1).  The full statement: csrc/gmsd.hip, tests/gmsd_ref.py.
+ * img, ref: [n, H, W]; out: double [n, 2] = {score, mean GMS}; out_map: double [n, h2, w2] = q, or NULL.
+ * clip: clamp both inputs to [0,1] first (0: only the rounding stays).  Needs H >= 2 and W >= 2 (EVR_ERR_INVALID below that, the
+ * message names the size, nothing is launched).  A frame's numbers and map do not depend on n, on its place in the batch or
+ * on earlier calls.
+ */
+size_t evr_gmsd_workspace_bytes(int n, int H, int W);
+int evr_gmsd(const float* img, const float* ref, int n, int H, int W, int clip, double* out, double* out_map, void* workspace,
+             size_t workspace_bytes, evr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * LPIPS (AlexNet, v0.1).  Replaces PyIqaMetricFactory.get_metric('lpips') (utils/eval_metrics.py:110-156):
