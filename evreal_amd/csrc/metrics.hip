@@ -158,7 +158,8 @@ extern "C" int evr_metrics(const float* img, const float* ref, int n, int H, int
     EVR_REQUIRE(n >= 0 && H >= 1 && W >= 1, "evr_metrics: bad shape");
     if (n == 0) return EVR_OK;
     EVR_REQUIRE(img && ref && out, "evr_metrics: null pointer");
-    EVR_REQUIRE(!(which & 2u) || (H > 2 * R && W > 2 * R), "evr_metrics: SSIM needs images larger than 11x11 (win_size)");
+    // 12 x 12 is the smallest frame: at 11 x 11 the crop leaves ONE pixel of the SSIM map, not a mean over a frame
+    EVR_REQUIRE(!(which & 2u) || (H > 2 * R + 1 && W > 2 * R + 1), "evr_metrics: SSIM needs images larger than 11x11 (win_size)");
     const size_t need = evr_metrics_workspace_bytes(n, H, W);
     if (!workspace || workspace_bytes < need) {
         evr::set_error("evr_metrics: workspace %zu B < required %zu B", workspace_bytes, need);

@@ -245,7 +245,8 @@ int evr_hist_equalize(float* img, int n, int H, int W, int mode, void* workspace
  * Per-frame metrics.  Replaces EvalMetricsTracker.update's clip (utils/eval_metrics.py:253-255),
  * MseMetric.calculate (:82-84) and SsimMetric.calculate (:95-97; gaussian_weights=True, sigma=1.5,
  * use_sample_covariance=False, data_range=1.0).  img, ref: [n, H, W]; out: double [n, 2] = {mse, ssim}.
- * which: bit 0 = mse, bit 1 = ssim.  clip: clamp both inputs to [0,1] first.
+ * which: bit 0 = mse, bit 1 = ssim.  clip: clamp both inputs to [0,1] first.  ssim needs H >= 12 and W >= 12 (EVR_ERR_INVALID
+ * below that, nothing launched: the 11 x 11 window and the 5-pixel crop leave at most one pixel of the map).
  */
 int evr_metrics(const float* img, const float* ref, int n, int H, int W, unsigned which, int clip,
                 double* out, void* workspace, size_t workspace_bytes, evr_stream_t stream);
