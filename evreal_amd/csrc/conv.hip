@@ -2238,7 +2238,7 @@ static int launch_wide(const ConvArgs& a, const ConvArgs* d_args, hipStream_t st
 #if EVR_ARITH == 3
 // ---------------------------------------------------------------------------------------------------
 // conv3x3_wide_kernel<true, WN> -- the ConvLSTM gate launches -- on v_mfma_f32_16x16x32_f16 (h3 build only; EVR_MFMA16=0 restores the
-// 32x32x16 form above).  Under the h3 mix the chip holds a higher clock on this shape at equal matrix cycles per FLOP
+// 32x32x16 form above; ALT: the skewed main loop of the 256 x 256 form, namespace alt16 below).  Under the h3 mix the chip holds a higher clock on this shape at equal matrix cycles per FLOP
 // (tools/mfma_shape_probe.hip, profiles/r07_mfma_shape_probe.txt).  Block tile, wave tile (64 px x 128 columns), LDS layout, band /
 // weight-ring DMA, counted waits and the XCD remap are the kernel's above; what changes is the fragment addressing and the epilogue.
 //   operands   lane l = (p = l & 15, o = l >> 4) holds row / column p and k = 8o .. 8o + 7 of the 32-channel chunk: of an H2 row's
@@ -2259,7 +2259,82 @@ __device__ __forceinline__ f4 mma16_h3(f4 acc, f16x8 wh, f16x8 wl, f16x8 xh, f16
 }
 #endif
 
-template <int WN>
+// The skewed loop of the 256 x 256 form (conv3x3_wide16_kernel<2, true>; EVR_WIDE16_ALT=0: the lock-step loop).  The block's waves form
+// an early half (wni == 0) and a late half (wni == 1); waves w and w + 4 share a SIMD (tools/wave_simd_probe.hip), so every SIMD holds
+// one wave of each.  A step is cut into a LOAD part (request the next step's weights and, at taps 0 / 3 / 6, the next band; read the
+// step's 8 pixel fragments and first weight fragment into registers) and an MMA part (96 MFMAs, the other 14 weight reads, the counted
+// wait for the requests).  Every part is one SEGMENT; segment k ends at the block's barrier k; the late half runs one segment behind:
+//     segment   2s      2s + 1    2s + 2
+//     early     LOAD s  MMA s     LOAD s+1         -> while one wave of a SIMD loads and parks, its partner feeds the matrix pipe
+//     late      MMA s-1 LOAD s    MMA s
+// A 256-column weight slot is two 128-column halves, each requested, awaited and read by one half only; the two band buffers are shared,
+// and each half requests its pieces of the next band in its own LOAD of taps 0 / 3 / 6 -- for the early half that is the segment after the
+// late half's last read of the band being replaced.  Only s_barrier and counted s_waitcnt order the halves, and both halves execute the
+// same number of barriers whatever nchunks and M are.  The functions below ARE the schedule (the kernel calls them) and check() replays
+// it per half with a model of vmcnt (requests retire in order), so a schedule that breaks a rule does not compile.
+namespace alt16 {
+constexpr int W_PIECES = 4;                                            // weight DMA pieces per wave and step (its half of a slot)
+constexpr int seg_load(int h, int s) { return 2 * s + h; }             // h: 0 early, 1 late
+constexpr int seg_mma(int h, int s) { return 2 * s + h + 1; }
+constexpr int idle_barriers(int h) { return h; }                       // executed before the half's first LOAD
+constexpr bool barrier_after_mma(int h, int s, int nsteps) { return !(h == 1 && s == nsteps - 1); }   // (the early half is in its epilogue by then)
+constexpr bool band_request(int t) { return t % 3 == 0; }              // in LOAD of tap t: the band of the next dy
+constexpr int vm_after_mma(int t) { return t % 3 == 0 ? 4 : 0; }       // requests that may still fly when MMA of tap t ends
+// nchunks chunks of 9 taps; a wave requests band_pieces (4 or 5) pieces of a band.  Checks: equal barrier counts; the segment numbering
+// above is what the barriers executed give; no weight half-slot and no band buffer is requested before a barrier that follows its last
+// read (in both halves for a band); every read follows a barrier that follows the wait covering all pieces of its request; nothing flies
+// when the loop ends.  Steps / bands past the end are the clamped, unread requests the loop issues to keep the counts static.
+constexpr bool check(int nchunks, int band_pieces) {
+    constexpr int MAXS = 9 * 16 + 2, INF = 1 << 30;
+    const int S = 9 * nchunks, G = 3 * nchunks;
+    if (S + 1 >= MAXS) return false;
+    int w_req[2][MAXS] = {}, w_done[2][MAXS] = {}, b_req[2][MAXS] = {}, b_done[2][MAXS] = {}, nbar[2] = {};
+    for (int h = 0; h < 2; ++h) {
+        int q_kind[8 * MAXS] = {}, q_idx[8 * MAXS] = {}, head = 0, tail = 0;   // the wave's requests in flight, oldest first
+        int w_left[MAXS] = {}, b_left[MAXS] = {};
+        for (int i = 0; i < MAXS; ++i) { w_req[h][i] = b_req[h][i] = -1; w_done[h][i] = b_done[h][i] = INF; }
+        w_done[h][0] = b_done[h][0] = -1;                                      // prologue: vmcnt(0) before "barrier -1"
+        int cur = idle_barriers(h);
+        for (int s = 0; s < S; ++s) {
+            const int t = s % 9;
+            if (cur != seg_load(h, s)) return false;
+            w_req[h][s + 1] = cur; w_left[s + 1] = W_PIECES;
+            for (int i = 0; i < W_PIECES; ++i) { q_kind[tail] = 0; q_idx[tail++] = s + 1; }
+            if (band_request(t)) {
+                const int g = s / 3 + 1;
+                b_req[h][g] = cur; b_left[g] = band_pieces;
+                for (int i = 0; i < band_pieces; ++i) { q_kind[tail] = 1; q_idx[tail++] = g; }
+            }
+            ++cur;                                                             // the barrier between LOAD and MMA
+            if (cur != seg_mma(h, s)) return false;
+            while (tail - head > vm_after_mma(t)) {
+                const int i = q_idx[head];
+                if (q_kind[head++] == 0) { if (--w_left[i] == 0) w_done[h][i] = cur; }
+                else if (--b_left[i] == 0) b_done[h][i] = cur;
+            }
+            if (barrier_after_mma(h, s, S)) ++cur;
+        }
+        if (head != tail) return false;
+        nbar[h] = cur;
+    }
+    if (nbar[0] != nbar[1]) return false;
+    for (int h = 0; h < 2; ++h) {
+        for (int s = 0; s < S; ++s) if (!(w_done[h][s] < seg_load(h, s))) return false;              // first read of step s's weights
+        for (int s = 2; s <= S; ++s) if (!(w_req[h][s] > seg_mma(h, s - 2))) return false;           // last read of the half-slot's step s - 2
+        for (int hh = 0; hh < 2; ++hh) {
+            for (int g = 0; g < G; ++g) if (!(b_done[h][g] < seg_load(hh, 3 * g))) return false;        // first read of band g by either half
+            for (int g = 2; g <= G; ++g) if (!(b_req[h][g] > seg_load(hh, 3 * (g - 2) + 2))) return false;   // last read of band g - 2
+        }
+    }
+    return true;
+}
+constexpr bool waits_encodable() { for (int t = 0; t < 9; ++t) if (vm_after_mma(t) != 0 && vm_after_mma(t) != 4) return false; return true; }
+static_assert(waits_encodable(), "the kernel spells out s_waitcnt vmcnt(0) and vmcnt(4) only");
+static_assert(check(1, 4) && check(1, 5) && check(2, 4) && check(2, 5) && check(3, 5) && check(4, 4) && check(4, 5) && check(8, 4) &&
+              check(8, 5) && check(16, 4) && check(16, 5), "the skewed schedule of conv3x3_wide16_kernel<2, true> breaks one of its rules");
+}   // namespace alt16
+
+template <int WN, bool ALT = false>
 __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvArgs* __restrict__ ap) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const ConvArgs& a = *ap;
@@ -2273,6 +2348,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
     constexpr int NA_MAX = (A_PIECES + NW - 1) / NW, NA_MIN = A_PIECES / NW;
     constexpr int NBW = (B_F4 / 64) / NW;
     static_assert(NBW == 4 && (SINGLE || NA_MIN == 4), "update the counted waits");
+    static_assert(!ALT || (WN == 2 && NBW == alt16::W_PIECES && NA_MIN == 4 && NA_MAX == 5), "alt16::check models these request counts");
     __shared__ __attribute__((aligned(16))) float4 lds[NBUF * A_F4 + 2 * B_F4 + SP];   // [band 0 | band 1 | weight slot 0 | 1 | a zero row]
     constexpr int ZROW = (NBUF * A_F4 + 2 * B_F4) / SP;
 
@@ -2304,7 +2380,10 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
     const int row0 = 8 * wv + (lane >> 3);
     const int a_pix0 = m0 - 1 + row0;
     const unsigned a_q0 = (unsigned)((((lane & 7) ^ swz<32>(row0)) * 4));
-    const unsigned b_off0 = (unsigned)((n0 + row0) * ktot) + a_q0;
+    // (ALT: a wave requests weight rows of its own half's 128 columns only -- piece 16 * wni + wmi + 4 * jj; 32 * wni, 128 * wni and
+    // 32 * jj leave the swizzle bits of row0 alone)
+    const int wpiece0 = ALT ? 16 * wni + wmi : wv, wpiece_step = ALT ? 4 : NW;
+    const unsigned b_off0 = (unsigned)((n0 + 8 * wpiece0 + (lane >> 3)) * ktot) + a_q0;
     const unsigned a_v0 = ((unsigned)(a_pix0 * c0) + a_q0) * 4u, a_v1 = ((unsigned)(a_pix0 * c1) + a_q0) * 4u;
     auto issue_band = [&](int cc, int dyi, int buf) {
         int coff = cc * 32;
@@ -2328,8 +2407,8 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
         const unsigned kofs = (unsigned)((t * nchunks + cc) * 32);
 #pragma unroll
         for (int jj = 0; jj < NBW; ++jj) {
-            lds_ptr_t dst = (lds_ptr_t)&lds[NBUF * A_F4 + slot * B_F4 + (wv + jj * NW) * 64];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, dst, 16, b_off0 * 4u, (kofs + (unsigned)(8 * NW * jj * ktot)) * 4u, 0, 0);
+            lds_ptr_t dst = (lds_ptr_t)&lds[NBUF * A_F4 + slot * B_F4 + (wpiece0 + jj * wpiece_step) * 64];
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, dst, 16, b_off0 * 4u, (kofs + (unsigned)(8 * wpiece_step * jj * ktot)) * 4u, 0, 0);
         }
     };
 
@@ -2364,6 +2443,62 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
     issue_w(0, 0, 0);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
+    if constexpr (ALT) {
+        // the skewed loop: alt16 above.  Per accumulator the same MFMAs in the same order as the loop below
+        const bool late = wni != 0;                                        // wave-uniform
+        if (late) asm volatile("s_barrier" ::: "memory");                 // alt16::idle_barriers(1): the late half sits out segment 0
+        static_assert(alt16::idle_barriers(0) == 0 && alt16::idle_barriers(1) == 1);
+        for (int c = 0; c < nchunks; ++c) {
+            const int pa = c & 1;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                // ---- LOAD
+                const int t2 = (t + 1) % 9;
+                int cw = c + (t + 1) / 9;
+                if (cw >= nchunks) cw = nchunks - 1;
+                const int d2 = (t / 3 + 1) % 3;
+                int cb = c + (t / 3 + 1) / 3;
+                if (cb >= nchunks) cb = nchunks - 1;
+                issue_w(t2, cw, pa ^ ((t + 1) & 1));
+                if (alt16::band_request(t)) issue_band(cb, d2, pa ^ ((t / 3 + 1) & 1));
+                __builtin_amdgcn_sched_barrier(0);
+                const int ab = pa ^ ((t / 3) & 1);
+                const float4* lb = &lds[NBUF * A_F4 + (pa ^ (t & 1)) * B_F4 + (wni * 128 + p) * SP];
+                int l0 = wmi * 64 + p + (t % 3);
+                asm volatile("" : "+v"(l0));
+                const int xs = swz<32>(l0);
+                int iA = ab * A_ROWS + l0, iB = iA + 16, iC = iA + 32, iD = iA + 48;
+                if (t != 4) {
+                    iA = ((vmA >> t) & 1u) ? iA : ZROW; iB = ((vmB >> t) & 1u) ? iB : ZROW;
+                    iC = ((vmC >> t) & 1u) ? iC : ZROW; iD = ((vmD >> t) & 1u) ? iD : ZROW;
+                }
+                auto ld = [&](const float4* q) { return __builtin_bit_cast(f16x8, *q); };
+                const f16x8 xhA = ld(&lds[iA * SP + (hs ^ xs)]), xlA = ld(&lds[iA * SP + ((hs | 2) ^ xs)]);
+                const f16x8 xhB = ld(&lds[iB * SP + (hs ^ xs)]), xlB = ld(&lds[iB * SP + ((hs | 2) ^ xs)]);
+                const f16x8 xhC = ld(&lds[iC * SP + (hs ^ xs)]), xlC = ld(&lds[iC * SP + ((hs | 2) ^ xs)]);
+                const f16x8 xhD = ld(&lds[iD * SP + (hs ^ xs)]), xlD = ld(&lds[iD * SP + ((hs | 2) ^ xs)]);
+                f16x8 wh = ld(lb + wq_h), wl = ld(lb + wq_l);
+                // the fragments are in registers before the barrier: the band may be replaced from the next segment on
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+                // ---- MMA
+#pragma unroll
+                for (int f = 0; f < NF; ++f) {
+                    f16x8 whn = wh, wln = wl;
+                    if (f + 1 < NF) { whn = ld(lb + (f + 1) * 16 * SP + wq_h); wln = ld(lb + (f + 1) * 16 * SP + wq_l); }
+                    accA[f] = mma16_h3(accA[f], wh, wl, xhA, xlA);
+                    accB[f] = mma16_h3(accB[f], wh, wl, xhB, xlB);
+                    accC[f] = mma16_h3(accC[f], wh, wl, xhC, xlC);
+                    accD[f] = mma16_h3(accD[f], wh, wl, xhD, xlD);
+                    __builtin_amdgcn_sched_barrier(0);
+                    wh = whn; wl = wln;
+                }
+                if (alt16::vm_after_mma(t) == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                if (alt16::barrier_after_mma(late ? 1 : 0, 9 * c + t, 9 * nchunks)) asm volatile("s_barrier" ::: "memory");
+            }
+        }
+    } else
     for (int c = 0; c < nchunks; ++c) {
         const int pa = c & 1;
 #pragma unroll
@@ -2462,12 +2597,15 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
 #endif
 }
 
-template <int WN>
+static std::atomic<int64_t> g_wide16_alt_launches{0};
+
+template <int WN, bool ALT = false>
 static int launch_wide16(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream) {
     const int M = a.n * a.hm * a.wm;
     const int total = ((M + 255) / 256) * (a.cout / (128 * WN));
-    hipLaunchKernelGGL((conv3x3_wide16_kernel<WN>), dim3(total), dim3(256 * WN), 0, stream, d_args);
+    hipLaunchKernelGGL((conv3x3_wide16_kernel<WN, ALT>), dim3(total), dim3(256 * WN), 0, stream, d_args);
     EVR_LAUNCH_CHECK();
+    if (ALT) g_wide16_alt_launches.fetch_add(1, std::memory_order_relaxed);
     return EVR_OK;
 }
 #endif   // EVR_ARITH == 3
@@ -2920,6 +3058,9 @@ static int launch_t(const ConvArgs& a, const ConvArgs* d_args, hipStream_t strea
 
 }  // namespace EVR_ANS
 using namespace EVR_ANS;
+#if EVR_ARITH == 3
+int64_t conv_wide16_alt_launches() { return g_wide16_alt_launches.load(std::memory_order_relaxed); }
+#endif
 
 int EVR_LAUNCH_NAME(const ConvArgs& a, const ConvArgs* d_args, int kc, int wm, int nb, hipStream_t stream, float* img) {
     EVR_REQUIRE(!a.pred_w || (a.cout == 32 * nb && img), "conv_igemm: fused prediction needs a single N tile and an image pointer");
@@ -2986,6 +3127,10 @@ int EVR_LAUNCH_NAME(const ConvArgs& a, const ConvArgs* d_args, int kc, int wm, i
         static const int wide_min = getenv("EVR_WIDE_MIN") ? atoi(getenv("EVR_WIDE_MIN")) : 600;   // (round 5: 600 tiles, was 1024 -- +2 % at 8 / 16 / 32 sequences, equal at 4 and 64; 300: -1 % at 16 / 32.  Tests lower it)
         // two 256 x 128 blocks per CU (one band buffer each) while K is short, one 256 x 256 block otherwise: measured
         // 1486 / 1449 / 1405 us against 1585 / 1489 / 1401 us for 128 / 256 / 512 input channels (EVR_WIDE=2 / 3 force one)
+        // (round 8, the 256 x 256 form on its skewed loop, 64 sequences, two-stream step, us per launch enc0 / enc1 / enc2.rec: this rule
+        // 1885 / 1822 / 1708 and 1925 / 1850 / 1703, EVR_WIDE=3 1855 / 1803 / 1696 and 1879 / 1810 / 1706, EVR_WIDE=3 on the lock-step
+        // loop 1991 / 1904 / 1790 and 2040 / 1953 / 1849.  The 256 x 256 form now leads on the short-K layers too, by 1-2 %; the rule
+        // stays until the tile-count thresholds below, taken on the lock-step loop, are measured again at 4 - 32 sequences)
         const bool twin = (wide == 2) || (wide == 1 && a.c0 + a.c1 <= 256);
         // (the twin form already pays from ~1.4 rounds of its 512 slots on: per-layer times at 4 / 8 sequences, enc0.rec 144 -> 138 us
         // with 726 twin tiles, enc1.rec 262 -> 249 us with 728; below one round it loses -- enc1.rec 136 -> 151 us with 364 tiles -- and
@@ -2997,7 +3142,9 @@ int EVR_LAUNCH_NAME(const ConvArgs& a, const ConvArgs* d_args, int kc, int wm, i
 #if EVR_ARITH == 3
             // the same tiles on 16x16x32 MFMAs (conv3x3_wide16_kernel); EVR_MFMA16=0: the 32x32x16 form
             static const int mfma16 = getenv("EVR_MFMA16") ? atoi(getenv("EVR_MFMA16")) : 1;
-            if (mfma16) return twin ? launch_wide16<1>(a, d_args, stream) : launch_wide16<2>(a, d_args, stream);
+            // the 256 x 256 form runs its skewed loop (wave halves alternate load and MFMA); EVR_WIDE16_ALT=0: the lock-step loop
+            static const int alt = getenv("EVR_WIDE16_ALT") ? atoi(getenv("EVR_WIDE16_ALT")) : 1;
+            if (mfma16) return twin ? launch_wide16<1>(a, d_args, stream) : (alt ? launch_wide16<2, true>(a, d_args, stream) : launch_wide16<2>(a, d_args, stream));
 #endif
             return twin ? launch_wide<true, 1>(a, d_args, stream, img) : launch_wide<true, 2>(a, d_args, stream, img);
         }

@@ -146,6 +146,7 @@ struct evr_model {
     std::vector<ProfPair> prof_pending;
     std::vector<double> prof_ms;
     std::vector<int64_t> prof_n;
+    int64_t prof_alt0 = 0;          // conv_wide16_alt_launches() when the profile was enabled
 
     ~evr_model() { release_shape(); for (auto& c : convs) { if (c.d_w) (void)hipFree(c.d_w); if (c.d_b) (void)hipFree(c.d_b); if (c.d_wino) (void)hipFree(c.d_wino);
                                             if (c.d_w2) (void)hipFree(c.d_w2); if (c.d_prog) (void)hipFree(c.d_prog); }
@@ -1853,6 +1854,7 @@ extern "C" int evr_model_profile_enable(evr_model* m, const char* filter) {
     m->prof_n.assign(m->convs.size() + 80, 0);
     m->prof_on = filter != nullptr;
     m->prof_filter = filter ? filter : "";
+    m->prof_alt0 = conv_wide16_alt_launches();
     return EVR_OK;
 }
 
@@ -1885,6 +1887,14 @@ extern "C" int evr_model_profile_read(evr_model* m, int max_layers, char* names,
             fl = 2.0 * 2.0 * a0.n * (double)a0.Lq * a0.Lk * 32.0 * a0.heads;
         }
         ms[k] = m->prof_ms[i]; flops_per_launch[k] = fl; launches[k] = m->prof_n[i];
+        ++k;
+    }
+    // a row that is no layer, for a non-empty filter it matches only: launches of the skewed 256 x 256 ConvLSTM loop by this process
+    // since the profile was enabled (no time, no FLOPs -- the layers' own rows carry those)
+    static const char* const alt_row = "kernel.wide16_alt";
+    if (m->prof_on && !m->prof_filter.empty() && std::string(alt_row).find(m->prof_filter) != std::string::npos && k < max_layers) {
+        snprintf(names + (size_t)k * 64, 64, "%s", alt_row);
+        ms[k] = 0.0; flops_per_launch[k] = 0.0; launches[k] = conv_wide16_alt_launches() - m->prof_alt0;
         ++k;
     }
     *n_layers = k;
