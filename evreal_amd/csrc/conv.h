@@ -422,6 +422,8 @@ int launch_conv_igemm_h3(const ConvArgs& a, const ConvArgs* d_args, int kc, int 
 int launch_conv_igemm_m6(const ConvArgs& a, const ConvArgs* d_args, int kc, int wm, int nb, hipStream_t stream, float* img);
 // launches of the skewed 256 x 256 ConvLSTM loop (conv3x3_wide16_kernel<2, true>) in this process; evr_model_profile_read reports them
 int64_t conv_wide16_alt_launches();
+// ... and of conv3x3_wide16_kernel, either form, with the trimmed prologue / epilogue (TAIL; EVR_WIDE16_TAIL=0: none)
+int64_t conv_wide16_tail_launches();
 // Winograd F(2x2, 3x3) path of the exact-fp32 mode (wino.hip; EVR_WINO=0: never): host-side weight transform (w = [n_gemm][9][cin]
 // in prep_conv2d's order; lstm_hidden > 0: ConvLSTM row permutation), the eligibility test of a launch plan, the launch
 void wino_pack_weights(const std::vector<float>& w, int n_gemm, int cin, int lstm_hidden, std::vector<float>& out);

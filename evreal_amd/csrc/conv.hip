@@ -171,6 +171,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsig
 // channels in registers.  epi_setup (before the main loop) starts the accumulators at the bias and requests the
 // epilogue's operands (cell state / residual / fused skip) a whole main loop before they are needed.
 // timing ablation of the epilogues' memory traffic (tools/ablate_wide.sh; results are garbage): bit 4 (16) no operand loads, bit 6 (64) no stores
+// (conv3x3_wide16_kernel only: bit 9 (512) no gate arithmetic, bit 10 (1024) no bias loads / neighbour decodes in the prologue)
 #ifdef EVR_WIDE_ABLATE
 constexpr int EPI_ABLATE = EVR_WIDE_ABLATE;
 #else
@@ -2334,10 +2335,18 @@ static_assert(check(1, 4) && check(1, 5) && check(2, 4) && check(2, 5) && check(
               check(8, 5) && check(16, 4) && check(16, 5), "the skewed schedule of conv3x3_wide16_kernel<2, true> breaks one of its rules");
 }   // namespace alt16
 
-template <int WN, bool ALT = false>
+// TAIL (EVR_WIDE16_TAIL=0: without): the tile's fixed part outside the main loop, trimmed.  Results are the same bits: every accumulator
+// sees the same MFMAs in the same order, the cell update and the H2 split are finish()'s and pack4_h2's as before.
+//   prologue   the first band and the first weight (half-)slot are requested as soon as their addresses exist; the bias loads, the four
+//              neighbour decodes and the zero row run under that round trip instead of ahead of it (one vmcnt(0) + barrier, as before)
+//   h stores   lanes (p, o) and (p, o ^ 1) trade halves (v_permlane16_swap: partners share their pixel, so they are active together):
+//              the even lane stores 16 B of hi, the odd lane 16 B of lo -- 8 stores per lane where there were 16, same bytes
+// (tried with these and dropped, DESIGN.md section 8: a c_prev warm-up piece in the last step, static priority for the late half)
+template <int WN, bool ALT = false, bool TAIL = false>
 __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvArgs* __restrict__ ap) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const ConvArgs& a = *ap;
+    constexpr bool T_PRO = TAIL, T_ST16 = TAIL && FMT == 2;
     constexpr int WM = 4, NW = WM * WN, SP = 8, NF = 8;
     constexpr bool SINGLE = (WN == 1);
     constexpr int NBUF = SINGLE ? 1 : 2;
@@ -2412,6 +2421,12 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
         }
     };
 
+    if constexpr (T_PRO) {      // requests first: what follows up to the wait runs under their round trip
+        issue_band(0, 0, 0);
+        issue_w(0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
     const int p = lane & 15, o = lane >> 4;
     const int hs = 4 * (o >> 1) + (o & 1);                     // the lane's hi slot; its lo slot is hs | 2
     const int wq_h = hs ^ (p >> 1), wq_l = (hs | 2) ^ (p >> 1);     // weight rows 16f + p: swz<32> = p >> 1 for every f
@@ -2419,12 +2434,14 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
     f4 accA[NF], accB[NF], accC[NF], accD[NF];
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
-        const f4 b4 = *(const f4*)(a.bias + n0w + 16 * f + 4 * o);
+        f4 b4 = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (!(EPI_ABLATE & 1024)) b4 = *(const f4*)(a.bias + n0w + 16 * f + 4 * o);
         accA[f] = b4; accB[f] = b4; accC[f] = b4; accD[f] = b4;
     }
     const int mP = m0 + wmi * 64 + p;                          // the lane's pixel of block 0; block b: + 16b
     auto neighbours = [&](int m) -> unsigned {   // validity of the pixel's 9 neighbours (bit t = tap (t/3 - 1, t%3 - 1))
         unsigned vm = 0;
+        if constexpr (EPI_ABLATE & 1024) return 0x1ffu;
         if (m < M) {
             const int img = fdiv(m, a.div_hw_mul, a.div_hw_sh), rem = m - img * hw;
             const int py = fdiv(rem, a.div_w_mul, a.div_w_sh), px = rem - py * W;
@@ -2439,8 +2456,10 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
     const unsigned vmA = neighbours(mP), vmB = neighbours(mP + 16), vmC = neighbours(mP + 32), vmD = neighbours(mP + 48);
 
     if (tid < SP) lds[NBUF * A_F4 + 2 * B_F4 + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-    issue_band(0, 0, 0);
-    issue_w(0, 0, 0);
+    if constexpr (!T_PRO) {
+        issue_band(0, 0, 0);
+        issue_w(0, 0, 0);
+    }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
     if constexpr (ALT) {
@@ -2576,6 +2595,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
             f4 cn, hn;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
+                if constexpr (EPI_ABLATE & 512) { cn[j] = acc[s][j] + acc[2 + s][j] + cp[s][j]; hn[j] = acc[4 + s][j] + acc[6 + s][j]; continue; }
                 const float gi = sigmoid_t<true>(acc[s][j] * sc);
                 const float gf = sigmoid_t<true>(acc[2 + s][j] * sc);
                 const float go = sigmoid_t<true>(acc[4 + s][j] * sc);
@@ -2583,10 +2603,24 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
                 cn[j] = __fadd_rn(__fmul_rn(gf, cp[s][j]), __fmul_rn(gi, gc));
                 hn[j] = go * tanh_t<true>(cn[j]);
             }
+            [[maybe_unused]] unsigned h16[4];
+            if constexpr (T_ST16) {
+                // pack4_h2's halves, then swap(hi, lo) across the row pair: odd rows of the first operand <-> even rows of the second.
+                // Even lane: [own hi | partner's hi] = dwords 2o .. 2o + 3 of the group's hi half; odd lane: [partner's lo | own lo]
+                // = dwords 2(o - 1) .. 2o + 1 of its lo half.  Outside the divergent store: both lanes of a pair take part
+                uint2 hi, lo;
+                pack4_h2(hn, hi, lo);
+                const auto x = __builtin_amdgcn_permlane16_swap(hi.x, lo.x, false, false);
+                const auto y = __builtin_amdgcn_permlane16_swap(hi.y, lo.y, false, false);
+                h16[0] = x[0]; h16[1] = y[0]; h16[2] = x[1]; h16[3] = y[1];
+            }
             if (ok && (!(EPI_ABLATE & 64) || cn[0] == 123.456f)) {
                 *(f4*)(a.state + row + ch0 + 16 * s) = cn;                      // the cell state stays fp32
                 if (!a.out_packed) *(f4*)(a.out + row + ch0 + 16 * s) = hn;
-                else store4_fmt<FMT>(a.out, row, ch0 + 16 * s, hn);
+                else if constexpr (T_ST16) {
+                    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+                    *(u4*)(a.out + row + (unsigned)((n0w >> 2) + 16 * s + 2 * (o & 2) + 8 * (o & 1))) = u4{h16[0], h16[1], h16[2], h16[3]};
+                } else store4_fmt<FMT>(a.out, row, ch0 + 16 * s, hn);
             }
         }
     };
@@ -2597,15 +2631,19 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
 #endif
 }
 
-static std::atomic<int64_t> g_wide16_alt_launches{0};
+static std::atomic<int64_t> g_wide16_alt_launches{0}, g_wide16_tail_launches{0};
 
 template <int WN, bool ALT = false>
 static int launch_wide16(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream) {
+    // the trimmed prologue / epilogue (TAIL, above the kernel); EVR_WIDE16_TAIL=0: the tile's fixed part as it was
+    static const int tail = getenv("EVR_WIDE16_TAIL") ? atoi(getenv("EVR_WIDE16_TAIL")) : 1;
     const int M = a.n * a.hm * a.wm;
     const int total = ((M + 255) / 256) * (a.cout / (128 * WN));
-    hipLaunchKernelGGL((conv3x3_wide16_kernel<WN, ALT>), dim3(total), dim3(256 * WN), 0, stream, d_args);
+    if (tail) hipLaunchKernelGGL((conv3x3_wide16_kernel<WN, ALT, true>), dim3(total), dim3(256 * WN), 0, stream, d_args);
+    else hipLaunchKernelGGL((conv3x3_wide16_kernel<WN, ALT, false>), dim3(total), dim3(256 * WN), 0, stream, d_args);
     EVR_LAUNCH_CHECK();
     if (ALT) g_wide16_alt_launches.fetch_add(1, std::memory_order_relaxed);
+    if (tail) g_wide16_tail_launches.fetch_add(1, std::memory_order_relaxed);
     return EVR_OK;
 }
 #endif   // EVR_ARITH == 3
@@ -3060,6 +3098,7 @@ static int launch_t(const ConvArgs& a, const ConvArgs* d_args, hipStream_t strea
 using namespace EVR_ANS;
 #if EVR_ARITH == 3
 int64_t conv_wide16_alt_launches() { return g_wide16_alt_launches.load(std::memory_order_relaxed); }
+int64_t conv_wide16_tail_launches() { return g_wide16_tail_launches.load(std::memory_order_relaxed); }
 #endif
 
 int EVR_LAUNCH_NAME(const ConvArgs& a, const ConvArgs* d_args, int kc, int wm, int nb, hipStream_t stream, float* img) {
@@ -3131,7 +3170,17 @@ int EVR_LAUNCH_NAME(const ConvArgs& a, const ConvArgs* d_args, int kc, int wm, i
         // 1885 / 1822 / 1708 and 1925 / 1850 / 1703, EVR_WIDE=3 1855 / 1803 / 1696 and 1879 / 1810 / 1706, EVR_WIDE=3 on the lock-step
         // loop 1991 / 1904 / 1790 and 2040 / 1953 / 1849.  The 256 x 256 form now leads on the short-K layers too, by 1-2 %; the rule
         // stays until the tile-count thresholds below, taken on the lock-step loop, are measured again at 4 - 32 sequences)
-        const bool twin = (wide == 2) || (wide == 1 && a.c0 + a.c1 <= 256);
+        // (round 9, measured again on the skewed loop with the trimmed tail, us per launch twin / 256 x 256, single-stream step,
+        // profiles/r09_layer_times.txt: enc0.rec -- 128 input channels -- 5808 tiles 1852 / 1822, 2904 tiles 902 / 915, 1452 tiles 471 / 454,
+        // 726 tiles 240 / 235; enc1.rec -- 256 channels -- 2904 tiles 1841 / 1800, 1452 tiles 890 / 852, 726 tiles 447 / 422.  From the
+        // 256 x 256 form's own threshold on the short-K layers take it too, with one exception that keeps the twin form: 128 channels and
+        // a last round of 256 blocks less than half full (2904 = 11.34 rounds), which the twin form's 512 half-width slots finish in
+        // finer pieces.  Below that threshold, and with an explicit EVR_WIDE_MIN, the rule is what it was)
+        const int64_t wide_tiles = (((int64_t)a.n * a.hm * a.wm + 255) / 256) * (a.cout / 256);
+        const bool ragged = wide_tiles % 256 != 0 && wide_tiles % 256 < 128;
+        static const bool wide_min_set = getenv("EVR_WIDE_MIN") != nullptr;
+        const bool short_k_twin = wide_min_set || wide_tiles < wide_min || (a.c0 + a.c1 <= 128 && ragged);
+        const bool twin = (wide == 2) || (wide == 1 && a.c0 + a.c1 <= 256 && short_k_twin);
         // (the twin form already pays from ~1.4 rounds of its 512 slots on: per-layer times at 4 / 8 sequences, enc0.rec 144 -> 138 us
         // with 726 twin tiles, enc1.rec 262 -> 249 us with 728; below one round it loses -- enc1.rec 136 -> 151 us with 364 tiles -- and
         // the 256 x 256 form loses up to its own threshold: enc2.rec 256 -> 279 us at 8 sequences.  Explicit EVR_WIDE_MIN: one threshold)

@@ -147,6 +147,7 @@ struct evr_model {
     std::vector<double> prof_ms;
     std::vector<int64_t> prof_n;
     int64_t prof_alt0 = 0;          // conv_wide16_alt_launches() when the profile was enabled
+    int64_t prof_tail0 = 0;         // conv_wide16_tail_launches() likewise
 
     ~evr_model() { release_shape(); for (auto& c : convs) { if (c.d_w) (void)hipFree(c.d_w); if (c.d_b) (void)hipFree(c.d_b); if (c.d_wino) (void)hipFree(c.d_wino);
                                             if (c.d_w2) (void)hipFree(c.d_w2); if (c.d_prog) (void)hipFree(c.d_prog); }
@@ -1855,6 +1856,7 @@ extern "C" int evr_model_profile_enable(evr_model* m, const char* filter) {
     m->prof_on = filter != nullptr;
     m->prof_filter = filter ? filter : "";
     m->prof_alt0 = conv_wide16_alt_launches();
+    m->prof_tail0 = conv_wide16_tail_launches();
     return EVR_OK;
 }
 
@@ -1891,11 +1893,15 @@ extern "C" int evr_model_profile_read(evr_model* m, int max_layers, char* names,
     }
     // a row that is no layer, for a non-empty filter it matches only: launches of the skewed 256 x 256 ConvLSTM loop by this process
     // since the profile was enabled (no time, no FLOPs -- the layers' own rows carry those)
-    static const char* const alt_row = "kernel.wide16_alt";
-    if (m->prof_on && !m->prof_filter.empty() && std::string(alt_row).find(m->prof_filter) != std::string::npos && k < max_layers) {
-        snprintf(names + (size_t)k * 64, 64, "%s", alt_row);
-        ms[k] = 0.0; flops_per_launch[k] = 0.0; launches[k] = conv_wide16_alt_launches() - m->prof_alt0;
-        ++k;
+    // (likewise "kernel.wide16_tail": launches of conv3x3_wide16_kernel, either tile form, with its trimmed prologue / epilogue)
+    const struct { const char* name; int64_t n; } kernel_rows[] = {{"kernel.wide16_alt", conv_wide16_alt_launches() - m->prof_alt0},
+                                                                   {"kernel.wide16_tail", conv_wide16_tail_launches() - m->prof_tail0}};
+    for (const auto& kr : kernel_rows) {
+        if (m->prof_on && !m->prof_filter.empty() && std::string(kr.name).find(m->prof_filter) != std::string::npos && k < max_layers) {
+            snprintf(names + (size_t)k * 64, 64, "%s", kr.name);
+            ms[k] = 0.0; flops_per_launch[k] = 0.0; launches[k] = kr.n;
+            ++k;
+        }
     }
     *n_layers = k;
     return EVR_OK;
