@@ -1,0 +1,567 @@
+// LPIPS (VGG-16, v0.1) on gfx950 -- the 'lpips-vgg' metric of the reference (utils/eval_metrics.py:100-156:
+// pyiqa.create_metric('lpips-vgg') on [n,3,H,W] batches built by cv2torch(img, num_ch=3), eval_utils.py:46-54).
+//
+// PARITY UNPINNED: pyiqa and torchvision are neither in the reference tree nor installed, and the VGG + linear-head weights are
+// downloaded at run time (unobtainable offline).  The arithmetic below follows the published algorithm (Zhang et al. 2018;
+// richzhang/PerceptualSimilarity v0.1 with net='vgg', as wrapped by pyiqa): x <- 2g-1; (x-shift)/scale per channel (the constants
+// of lpips.hip); torchvision vgg16.features with taps after relu1_2, relu2_2, relu3_3, relu4_3, relu5_3; MaxPool2d(2, 2) in floor
+// mode as the first operation of slices 2-5; unit-normalise every pixel's feature vector, f/(|f| + 1e-10); squared difference;
+// non-negative 1x1 "lin" weights; spatial mean; sum over the five layers.  Conventions that stay unpinned until
+// tests/test_lpips_vgg_pins.py has run where pyiqa exists -- recalled from the published code, not read from it: the state-dict
+// names net.slice1.{0,2}, net.slice2.{5,7}, net.slice3.{10,12,14}, net.slice4.{17,19,21}, net.slice5.{24,26,28} (.weight, .bias)
+// and lin{0..4}.model.1.weight (64, 128, 256, 512, 512 elements), and the pool positions (torchvision indices 4, 9, 16, 23).
+// Scores agree with the restatement tests/lpips_vgg_ref.py on any weights, and with pyiqa only once its weights are supplied.
+//
+// Layers: conv1_1 (3->64) is a direct VALU kernel on the gray input (the three input channels are affine in the same gray value);
+// the other twelve 3x3 convolutions run on the convolution kernels of conv.hip exactly as lpips.hip drives its conv3..conv5 (split
+// arithmetic: every activation tensor is PACKED / H2; fp32 mode: PLAIN, Winograd where eligible); one streaming kernel per tap
+// layer scores it and writes the 2x2 max pool of both images' features -- the 64-channel full-resolution tensor is read once.
+//
+// Memory plan: relu1_2 is 2*H*W*64*4 B per pair (46 MB at 346x260), so features are NOT kept: two ping-pong activation buffers
+// sized for the largest layer, 2*P*H*W*64*4 B each for P pairs per pass, P chosen so that both fit ACT_BUDGET_BYTES (at least 1;
+// `max_pairs` at create overrides it); a call with more pairs runs in passes, both frames of a pair always in the same pass.
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "conv.h"
+#include "packed.h"
+
+using namespace evr;
+
+namespace {
+
+constexpr size_t ACT_BUDGET_BYTES = (size_t)1 << 30;      // both activation buffers of a handle together (default pass size)
+// one buffer, whatever max_pairs asks: conv.hip sizes the buffer descriptor of a tensor in 32-bit bytes and offsets its pixel rows in
+// 32-bit float elements (this file's own kernels index in 64 bits), and its launcher wants n*hm*wm < 2^31.  2 GiB keeps all three;
+// a frame whose single pair does not fit (H*W >= 2^22) is refused
+constexpr int64_t ACT_BUFFER_MAX_BYTES = (int64_t)1 << 31;
+constexpr int MIN_SIDE = 16;                               // four floor-mode 2x2 pools must leave one pixel
+constexpr int NCONV = 12;                                  // convolutions on conv.hip (conv1_2 .. conv5_3)
+constexpr int VGG_CIN[NCONV] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
+constexpr int VGG_COUT[NCONV] = {64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
+constexpr int VGG_LEVEL[NCONV] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4};      // resolution level: H >> level (floor at every pool)
+constexpr int TAP_C[5] = {64, 128, 256, 512, 512};
+
+// ---- conv1_1: gray [n2,H,W] -> [n2,H,W,64], 3x3 pad 1, relu ---------------------------------------------------------
+// x_c = ((2g-1) - shift_c)/scale_c = alpha_c*g + beta_c inside the image and 0 where the convolution pads, so
+//   sum_c sum_t w[co][c][t] x_c[t] = sum_t inside[t] * (wg[t][co]*g[t] + wb[t][co])
+// with wg = sum_c w*alpha_c, wb = sum_c w*beta_c folded on the host in fp64: a ONE-channel 3x3 convolution plus, for pixels on
+// the image border, the wb term under the inside mask; interior pixels take sum_t wb[t] from the bias.
+// A thread owns 16 consecutive channels (one 64-B group of the output row: four 16-B stores in every format) of two pixels in
+// a row; the 2 x 9 x 64 folded weights sit in LDS (a lane reads the 16-B slots of its group: four distinct addresses per wave).
+struct Conv11Args {
+    const float* img; const float* ref;   // [n,H,W] each; batch index >= n reads ref
+    int n, H, W, clip;
+    const float* wg;                       // [9][64]
+    const float* wb;                       // [9][64]
+    const float* bias;                     // [64]
+    const float* bias_in;                  // [64] bias + sum_t wb[t]  (interior pixels)
+    float* out;
+    unsigned* sat;
+};
+
+constexpr int C11_PX = 2;      // pixels per thread (four: 172 registers, two waves per SIMD)
+template <int FMT>
+__global__ __launch_bounds__(256) void vgg_conv1_1_kernel(const Conv11Args a) {
+    constexpr int PX = C11_PX;
+    __shared__ __attribute__((aligned(16))) float s_w[2 * 9 * 64];      // wg | wb
+    for (int i = threadIdx.x; i < 2 * 9 * 64; i += 256) s_w[i] = i < 576 ? a.wg[i] : a.wb[i - 576];
+    __syncthreads();
+    const int wq = (a.W + PX - 1) / PX;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)2 * a.n * a.H * wq * 4) return;
+    const int g = (int)(i & 3); int64_t p = i >> 2;
+    const int x0 = (int)(p % wq) * PX; p /= wq;
+    const int y = (int)(p % a.H);
+    const int b = (int)(p / a.H);
+    const float* src = (b < a.n ? a.img + (int64_t)b * a.H * a.W : a.ref + (int64_t)(b - a.n) * a.H * a.W);
+    // the 3 x (PX + 2) gray window of the thread's pixels (0 outside the image); inside mask = rowm x colm
+    float gv[3][PX + 2], rowm[3], colm[PX + 2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) rowm[r] = (unsigned)(y + r - 1) < (unsigned)a.H ? 1.f : 0.f;
+#pragma unroll
+    for (int c = 0; c < PX + 2; ++c) colm[c] = (unsigned)(x0 + c - 1) < (unsigned)a.W ? 1.f : 0.f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < PX + 2; ++c) {
+            const int yy = y + r - 1, xx = x0 + c - 1;
+            float v = 0.f;
+            if ((unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W) {
+                v = src[(int64_t)yy * a.W + xx];
+                if (a.clip) v = fminf(fmaxf(v, 0.f), 1.f);
+            }
+            gv[r][c] = v;
+        }
+    const bool interior = y >= 1 && y + 1 < a.H && x0 >= 1 && x0 + PX < a.W;      // every tap of the thread's pixels is inside
+    float acc[PX][16];
+    {
+        const float4* bp = (const float4*)((interior ? a.bias_in : a.bias) + 16 * g);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 bv = bp[q];
+#pragma unroll
+            for (int px = 0; px < PX; ++px) { acc[px][4 * q] = bv.x; acc[px][4 * q + 1] = bv.y; acc[px][4 * q + 2] = bv.z; acc[px][4 * q + 3] = bv.w; }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int ky = t / 3, kx = t % 3;
+        float w[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 wv = *(const float4*)(s_w + t * 64 + 16 * g + 4 * q);
+            w[4 * q] = wv.x; w[4 * q + 1] = wv.y; w[4 * q + 2] = wv.z; w[4 * q + 3] = wv.w;
+        }
+#pragma unroll
+        for (int px = 0; px < PX; ++px)
+#pragma unroll
+            for (int k = 0; k < 16; ++k) acc[px][k] = fmaf(gv[ky][px + kx], w[k], acc[px][k]);
+        if (!interior) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 wv = *(const float4*)(s_w + 576 + t * 64 + 16 * g + 4 * q);
+                w[4 * q] = wv.x; w[4 * q + 1] = wv.y; w[4 * q + 2] = wv.z; w[4 * q + 3] = wv.w;
+            }
+#pragma unroll
+            for (int px = 0; px < PX; ++px) {
+                const float mk = rowm[ky] * colm[px + kx];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) acc[px][k] = fmaf(mk, w[k], acc[px][k]);
+            }
+        }
+    }
+#pragma unroll
+    for (int px = 0; px < PX; ++px) {
+        if (x0 + px >= a.W) continue;
+        float* o = a.out + (((int64_t)b * a.H + y) * a.W + x0 + px) * 64;
+        float v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v[k] = fmaxf(acc[px][k], 0.f);
+        if constexpr (FMT == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) *(float4*)(o + 16 * g + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+        } else {
+#if defined(__HIP_DEVICE_COMPILE__)
+            sat_check16<FMT>(a.sat, v);
+            store16_fmt<FMT>(o, 0u, 16 * g, v);
+#endif
+        }
+    }
+}
+
+// ---- one tap layer: LPIPS partial sums + the 2x2 max pool of both images' features -------------------------------------
+// feat: [2n, h, w, C] (first n = img, last n = ref) in format `fmt`; pooled: [2n, h/2, w/2, C] in the same format, or null
+// (relu5_3).  Work item = one 2x2 window of the grid ceil(h/2) x ceil(w/2): its pixels inside the image are scored (the odd last
+// row / column too, which the floor-mode pool drops), and a window that lies wholly inside writes its pooled pixel.  A lane owns
+// 4-channel runs (16 B on PLAIN rows): with R = C/4 runs per pixel a wave takes 64/R windows at once for R <= 64 (reductions
+// over R lanes), one window and two runs per lane at C = 512.  Per-lane fp64 partial sums, reduced in a fixed order.
+// NOT DONE: in the split modes a 4-channel run is an 8-B + 8-B (H2) or 8-B + 4-B + 4-B (PACKED) access through ld4_any / st4_any,
+// not 16 B per lane; a whole-group form (16 channels per lane, four 16-B pieces each way as conv1_1 stores them) is the next step.
+struct TapArgs {
+    const float* feat; float* pooled; const float* lin;
+    int n, h, w, C, fmt;
+    double* partials;      // [n][blocks]
+};
+
+__global__ __launch_bounds__(256) void vgg_pool_score_kernel(const TapArgs a) {
+    __shared__ double red[4];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int R = a.C >> 2;
+    const int L = R < 64 ? R : 64;            // lanes per pixel (16, 32, 64)
+    const int PW = 64 / L;                    // windows per wave
+    const int sub = lane / L, run0 = lane % L;
+    const int hw2 = (a.h + 1) >> 1, ww2 = (a.w + 1) >> 1, ho = a.h >> 1, wo = a.w >> 1;
+    const int nwin = hw2 * ww2;
+    const float* f0 = a.feat + (int64_t)b * a.h * a.w * a.C;
+    const float* f1 = a.feat + (int64_t)(b + a.n) * a.h * a.w * a.C;
+    float4 lw[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) lw[k] = (run0 + 64 * k < R) ? *(const float4*)(a.lin + (run0 + 64 * k) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    double acc = 0.0;
+    for (int w0 = (blockIdx.x * 4 + wave) * PW; w0 < nwin; w0 += gridDim.x * 4 * PW) {
+        const int win = w0 + sub;
+        const bool wok = win < nwin;
+        const int wy = wok ? win / ww2 : 0, wx = wok ? win % ww2 : 0;
+        // the window's four pixels are loaded first and their eight squared norms reduced together: one dependent chain of
+        // lane exchanges per window instead of one per pixel
+        float4 va[4][2], vc[4][2];
+        float s0[4], s1[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int y = 2 * wy + (q >> 1), x = 2 * wx + (q & 1);
+            const bool pok = wok && y < a.h && x < a.w;
+            const int64_t poff = ((int64_t)y * a.w + x) * a.C;
+            s0[q] = 0.f; s1[q] = 0.f;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int run = run0 + 64 * k;
+                va[q][k] = make_float4(0.f, 0.f, 0.f, 0.f); vc[q][k] = va[q][k];
+                if (pok && run < R) {
+                    va[q][k] = ld4_any(f0 + poff, run * 4, a.fmt);
+                    vc[q][k] = ld4_any(f1 + poff, run * 4, a.fmt);
+                }
+                s0[q] += (va[q][k].x * va[q][k].x + va[q][k].y * va[q][k].y) + (va[q][k].z * va[q][k].z + va[q][k].w * va[q][k].w);
+                s1[q] += (vc[q][k].x * vc[q][k].x + vc[q][k].y * vc[q][k].y) + (vc[q][k].z * vc[q][k].z + vc[q][k].w * vc[q][k].w);
+            }
+        }
+        for (int o = L >> 1; o > 0; o >>= 1) {      // over the lanes of one pixel
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { s0[q] += __shfl_xor(s0[q], o, 64); s1[q] += __shfl_xor(s1[q], o, 64); }
+        }
+        float4 ma[2], mc[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) { ma[k] = make_float4(0.f, 0.f, 0.f, 0.f); mc[k] = ma[k]; }      // (relu outputs: 0 is the identity of max)
+        float d = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            // (a reciprocal per pixel and image instead of a division per channel: one more rounding of 2^-24, the same for both
+            // images -- identical frames still score exactly 0)
+            const float r0 = 1.0f / (sqrtf(s0[q]) + 1e-10f), r1 = 1.0f / (sqrtf(s1[q]) + 1e-10f);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const float4 u = va[q][k], v = vc[q][k];
+                ma[k].x = fmaxf(ma[k].x, u.x); ma[k].y = fmaxf(ma[k].y, u.y); ma[k].z = fmaxf(ma[k].z, u.z); ma[k].w = fmaxf(ma[k].w, u.w);
+                mc[k].x = fmaxf(mc[k].x, v.x); mc[k].y = fmaxf(mc[k].y, v.y); mc[k].z = fmaxf(mc[k].z, v.z); mc[k].w = fmaxf(mc[k].w, v.w);
+                float e0, e1, e2, e3;
+                {   // both products rounded: contracted into a fused multiply-add, u r0 - v r1 is not 0 for u = v
+#pragma clang fp contract(off)
+                    e0 = u.x * r0 - v.x * r1; e1 = u.y * r0 - v.y * r1; e2 = u.z * r0 - v.z * r1; e3 = u.w * r0 - v.w * r1;
+                }
+                d = fmaf(lw[k].x, e0 * e0, d); d = fmaf(lw[k].y, e1 * e1, d); d = fmaf(lw[k].z, e2 * e2, d); d = fmaf(lw[k].w, e3 * e3, d);
+            }
+        }
+        acc += (double)d;
+        if (a.pooled && wok && wy < ho && wx < wo) {
+            const int64_t ooff = ((int64_t)wy * wo + wx) * a.C;
+            float* o0 = a.pooled + (int64_t)b * ho * wo * a.C + ooff;
+            float* o1 = a.pooled + (int64_t)(b + a.n) * ho * wo * a.C + ooff;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int run = run0 + 64 * k;
+                if (run < R) { st4_any(o0, run * 4, ma[k], a.fmt); st4_any(o1, run * 4, mc[k], a.fmt); }
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) a.partials[(int64_t)b * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// one wave per pair: lanes stride over a layer's partial sums, fixed-order tree, layers added in order
+struct FinalArgs { const double* partials[5]; int hw[5]; int blocks[5]; };
+__global__ __launch_bounds__(64) void vgg_final_kernel(const FinalArgs f, int n, double* __restrict__ out, double* __restrict__ out_layers) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= n) return;
+    double total = 0.0;
+    for (int l = 0; l < 5; ++l) {
+        double s = 0.0;
+        for (int k = lane; k < f.blocks[l]; k += 64) s += f.partials[l][(int64_t)b * f.blocks[l] + k];
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        const double dl = s / (double)f.hw[l];
+        if (lane == 0 && out_layers) out_layers[(int64_t)b * 5 + l] = dl;
+        total += dl;
+    }
+    if (lane == 0) out[b] = total;
+}
+
+// work-groups per pair of the tap kernel: every wave of a block wants at least a few windows; at most SCORE_BLOCKS_MAX
+constexpr int SCORE_BLOCKS_MAX = 256;
+int score_blocks(int n, int nwin, int C) {
+    const int pw = C >= 256 ? 1 : 256 / C;                  // windows per wave and round
+    int want = (nwin + 4 * pw * 4 - 1) / (4 * pw * 4);      // four rounds per wave
+    const int cap = 4096 / (n > 0 ? n : 1);                 // ~16 blocks per CU over the whole launch
+    if (want > cap) want = cap;
+    if (want > SCORE_BLOCKS_MAX) want = SCORE_BLOCKS_MAX;
+    return want < 1 ? 1 : want;
+}
+
+struct Layer { int cin, cout; int x3 = 0; int mx_e = 0; std::vector<float> w, b; float* d_w = nullptr; float* d_b = nullptr; float* d_wino = nullptr; };
+
+}  // namespace
+
+struct evr_lpips_vgg {
+    std::vector<float> wg, wb, b1, b1in;
+    float* d_wg = nullptr; float* d_wb = nullptr; float* d_b1 = nullptr; float* d_b1in = nullptr;
+    float* d_lin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    unsigned* d_sat = nullptr;       // range guard of the packed formats (packed.h sat_note): every producer of this handle counts here
+    Layer L[NCONV];
+    int mode = 0;                    // arithmetic of the twelve convolutions (arith_mode(), mode 4 as mode 2)
+    int max_pairs = 0;               // constructor argument: pairs per pass (0: from ACT_BUDGET_BYTES)
+    // shape-dependent.  Buffers are sized for `cap` pairs per pass at H x W and only ever grow; what depends on the pair count of
+    // a pass (the twelve ConvArgs with their tile choice) lives in a small cache of plans, as in lpips.hip.
+    int n = 0, H = 0, W = 0, cap = 0;      // n: pairs of the last call (evr_lpips_vgg_flops)
+    int h[5], w[5];                  // feature map sizes of the five levels
+    std::vector<void*> allocs;
+    float* act[2] = {nullptr, nullptr};
+    struct Plan { int n = 0; unsigned stamp = 0; ConvArgs args[NCONV]; int wm[NCONV], nb[NCONV]; };
+    static constexpr int NPLANS = 8;
+    Plan plans[NPLANS]; unsigned clock = 0;
+    ConvArgs* d_args = nullptr;      // [NPLANS][NCONV]
+    float* kws = nullptr; bool kws_tried = false;
+    double* partials = nullptr;      // [5][cap][SCORE_BLOCKS_MAX]
+    void release() {
+        for (void* p : allocs) (void)hipFree(p);
+        allocs.clear(); cap = 0; d_args = nullptr; kws = nullptr; kws_tried = false; act[0] = act[1] = nullptr; partials = nullptr;
+        for (auto& pl : plans) pl.n = 0;
+    }
+    ~evr_lpips_vgg() {
+        release();
+        if (d_wg) (void)hipFree(d_wg); if (d_wb) (void)hipFree(d_wb); if (d_b1) (void)hipFree(d_b1); if (d_b1in) (void)hipFree(d_b1in);
+        if (d_sat) (void)hipFree(d_sat);
+        for (auto& p : d_lin) if (p) (void)hipFree(p);
+        for (auto& l : L) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_wino) (void)hipFree(l.d_wino); }
+    }
+};
+
+namespace {
+int up(const std::vector<float>& h, float** d) {
+    EVR_HIP(hipMalloc((void**)d, h.size() * sizeof(float) + 64));
+    EVR_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return EVR_OK;
+}
+template <typename T>
+int dalloc(evr_lpips_vgg* m, T** p, size_t count) {
+    EVR_HIP(hipMalloc((void**)p, count * sizeof(T) + 256));
+    m->allocs.push_back((void*)*p);
+    return EVR_OK;
+}
+// pairs per pass at H x W
+int pass_pairs(const evr_lpips_vgg* m, int H, int W) {
+    const int64_t per_pair = (int64_t)2 * H * W * 64 * 4;      // one buffer, one pair
+    int64_t p = m->max_pairs > 0 ? m->max_pairs : (int64_t)(ACT_BUDGET_BYTES / 2) / per_pair;
+    if (p * per_pair >= ACT_BUFFER_MAX_BYTES) p = (ACT_BUFFER_MAX_BYTES - 1) / per_pair;      // (>= 1: evr_lpips_vgg_forward refuses larger frames)
+    return p < 1 ? 1 : (int)p;
+}
+}  // namespace
+
+extern "C" int evr_lpips_vgg_create(const evr_tensor* tensors, int n_tensors, int max_pairs, evr_lpips_vgg** out) {
+    EVR_REQUIRE(tensors && out && max_pairs >= 0, "evr_lpips_vgg_create: bad argument");
+    std::map<std::string, const evr_tensor*> sd;
+    for (int i = 0; i < n_tensors; ++i) if (tensors[i].name) sd[tensors[i].name] = &tensors[i];
+    auto get = [&](const std::string& k, int64_t numel, const evr_tensor** t) -> int {
+        auto it = sd.find(k);
+        if (it == sd.end()) { set_error("LPIPS-VGG state_dict is missing '%s'", k.c_str()); return EVR_ERR_MISSING_TENSOR; }
+        int64_t ne = 1; for (int d = 0; d < it->second->ndim; ++d) ne *= it->second->shape[d];
+        if (ne != numel) { set_error("LPIPS-VGG tensor '%s' has %lld elements, expected %lld", k.c_str(), (long long)ne, (long long)numel); return EVR_ERR_INVALID; }
+        *t = it->second; return EVR_OK;
+    };
+    evr_lpips_vgg* m = new evr_lpips_vgg();
+    m->max_pairs = max_pairs;
+    m->mode = arith_mode();
+    if (m->mode == 4) m->mode = 2;      // (P6 tensors have no 4-channel writer -- the pools: as lpips.hip, the fp8 form)
+    int rc = EVR_OK;
+    const evr_tensor *w, *b;
+    // torchvision vgg16.features indices inside pyiqa's slices (conv1_1 first)
+    const char* names[NCONV + 1] = {"net.slice1.0", "net.slice1.2", "net.slice2.5", "net.slice2.7", "net.slice3.10", "net.slice3.12", "net.slice3.14",
+                                    "net.slice4.17", "net.slice4.19", "net.slice4.21", "net.slice5.24", "net.slice5.26", "net.slice5.28"};
+    do {
+        if ((rc = get(std::string(names[0]) + ".weight", 64 * 3 * 9, &w))) break;
+        if ((rc = get(std::string(names[0]) + ".bias", 64, &b))) break;
+        m->wg.assign((size_t)9 * 64, 0.f); m->wb.assign((size_t)9 * 64, 0.f);
+        m->b1.assign(b->data_host, b->data_host + 64); m->b1in.assign(64, 0.f);
+        {   // scaling layer of LPIPS folded into conv1_1: x_c = alpha_c * g + beta_c
+            const double shift[3] = {-.030, -.088, -.188}, scale[3] = {.458, .448, .450};
+            for (int co = 0; co < 64; ++co) {
+                double bsum = 0.0;
+                for (int t = 0; t < 9; ++t) {
+                    double g = 0.0, bb = 0.0;
+                    for (int c = 0; c < 3; ++c) {
+                        const double wv = w->data_host[((size_t)co * 3 + c) * 9 + t];
+                        g += wv * (2.0 / scale[c]); bb += wv * ((-1.0 - shift[c]) / scale[c]);
+                    }
+                    m->wg[(size_t)t * 64 + co] = (float)g; m->wb[(size_t)t * 64 + co] = (float)bb;
+                    bsum += bb;
+                }
+                m->b1in[co] = (float)((double)m->b1[co] + bsum);
+            }
+        }
+        if ((rc = up(m->wg, &m->d_wg))) break;
+        if ((rc = up(m->wb, &m->d_wb))) break;
+        if ((rc = up(m->b1, &m->d_b1))) break;
+        if ((rc = up(m->b1in, &m->d_b1in))) break;
+        for (int l = 0; l < NCONV && !rc; ++l) {
+            Layer& L = m->L[l];
+            L.cin = VGG_CIN[l]; L.cout = VGG_COUT[l];
+            if ((rc = get(std::string(names[l + 1]) + ".weight", (int64_t)L.cout * L.cin * 9, &w))) break;
+            if ((rc = get(std::string(names[l + 1]) + ".bias", L.cout, &b))) break;
+            L.w.assign((size_t)L.cout * 9 * L.cin, 0.f); L.b.assign(b->data_host, b->data_host + L.cout);
+            for (int co = 0; co < L.cout; ++co) for (int ci = 0; ci < L.cin; ++ci) for (int t = 0; t < 9; ++t)
+                L.w[((size_t)co * 9 + t) * L.cin + ci] = w->data_host[((size_t)co * L.cin + ci) * 9 + t];
+            L.x3 = m->mode;
+            // exact-fp32 mode: the Winograd-domain weights too (model.cpp finish_conv; EVR_WINO=0: never)
+            if (L.x3 == 0 && wino_enabled() && L.cin % 16 == 0 && L.cout % 64 == 0) {
+                std::vector<float> u;
+                wino_pack_weights(L.w, L.cout, L.cin, 0, u);
+                if ((rc = up(u, &L.d_wino))) break;
+            }
+            if (L.x3) L.mx_e = pack_weights_for(L.x3, L.w);
+            if (L.x3 == 3) for (float& bv : L.b) bv = std::ldexp(bv, L.mx_e + H2_ACT_EXP);      // (model.cpp finish_conv)
+            if ((rc = up(L.w, &L.d_w))) break;
+            if ((rc = up(L.b, &L.d_b))) break;
+            std::vector<float>().swap(L.w);      // (the packed host copy -- 9 MB for a 512 x 512 layer -- is not needed again)
+        }
+        if (rc) break;
+        for (int l = 0; l < 5 && !rc; ++l) {
+            if ((rc = get("lin" + std::to_string(l) + ".model.1.weight", TAP_C[l], &w))) break;
+            std::vector<float> lw(w->data_host, w->data_host + TAP_C[l]);
+            rc = up(lw, &m->d_lin[l]);
+        }
+        if (rc) break;
+        if (hipMalloc((void**)&m->d_sat, 64) != hipSuccess) { rc = hip_fail(hipGetLastError(), "hipMalloc(sat)", __FILE__, __LINE__); break; }
+        if (hipMemset(m->d_sat, 0, 64) != hipSuccess) { rc = hip_fail(hipGetLastError(), "hipMemset(sat)", __FILE__, __LINE__); break; }
+    } while (0);
+    if (rc) { delete m; return rc; }
+    *out = m;
+    return EVR_OK;
+}
+
+extern "C" int evr_lpips_vgg_destroy(evr_lpips_vgg* m) { delete m; return EVR_OK; }
+
+// (re)allocate the activation buffers for `cap` pairs per pass of H x W: the only place that synchronises
+static int vgg_buffers(evr_lpips_vgg* m, int cap, int H, int W, hipStream_t stream) {
+    EVR_HIP(hipStreamSynchronize(stream));
+    m->release();
+    m->cap = cap; m->H = H; m->W = W;
+    m->h[0] = H; m->w[0] = W;
+    for (int l = 1; l < 5; ++l) { m->h[l] = m->h[l - 1] / 2; m->w[l] = m->w[l - 1] / 2; }
+    int rc;
+    const size_t act = (size_t)2 * cap * H * W * 64;      // the largest layer: relu1_1 / relu1_2 (every later one is at most half of it)
+    for (int i = 0; i < 2; ++i) if ((rc = dalloc(m, &m->act[i], act))) return rc;
+    if ((rc = dalloc(m, &m->partials, (size_t)5 * cap * SCORE_BLOCKS_MAX))) return rc;
+    if ((rc = dalloc(m, &m->d_args, (size_t)evr_lpips_vgg::NPLANS * NCONV))) return rc;
+    return EVR_OK;
+}
+
+// input / output buffer of convolution i (0 = conv1_2): conv1_1 writes act[0]; every convolution and every pool flips
+static int conv_src(int i) {
+    // ops in order: conv1_1 (-> 0), then per convolution one flip, plus one flip per pool in front of it
+    return (1 + i + VGG_LEVEL[i]) & 1 ? 0 : 1;
+}
+
+// the plan of n pairs inside the current buffers: cached, or built into the least recently used slot (its ConvArgs go to the
+// device in stream order, behind whatever launch still reads the slot's previous contents)
+static int vgg_plan(evr_lpips_vgg* m, int n, hipStream_t stream, evr_lpips_vgg::Plan** out) {
+    evr_lpips_vgg::Plan* pl = nullptr;
+    for (auto& c : m->plans) if (c.n == n) pl = &c;
+    if (pl) { pl->stamp = ++m->clock; *out = pl; return EVR_OK; }
+    for (auto& c : m->plans) {
+        if (c.n == 0) { pl = &c; break; }
+        if (!pl || c.stamp < pl->stamp) pl = &c;
+    }
+    pl->n = 0;
+    const int n2 = 2 * n;
+    bool may_split = false;
+    for (int i = 0; i < NCONV; ++i) {
+        Layer& L = m->L[i];
+        ConvArgs& a = pl->args[i];
+        const int lv = VGG_LEVEL[i], hh = m->h[lv], ww = m->w[lv], src = conv_src(i);
+        memset(&a, 0, sizeof(a));
+        a.in0 = m->act[src]; a.c0 = L.cin; a.in_mode = IN_SINGLE; a.n = n2; a.hin = hh; a.win = ww;
+        a.hm = hh; a.wm = ww; a.stride = 1; a.os = 1; a.hout = hh; a.wout = ww;
+        a.tp.ntaps = 9; a.tp.ngroups = 1; a.tp.grp_cols = L.cout;
+        for (int ky = 0; ky < 3; ++ky) for (int kx = 0; kx < 3; ++kx) a.tp.set_tap(ky * 3 + kx, ky - 1, kx - 1, 1);
+        a.wgt = L.d_w; a.bias = L.d_b; a.cout = L.cout; a.n_valid = L.cout; a.out = m->act[src ^ 1]; a.cout_total = L.cout;
+        a.epi = EPI_BIAS_RELU; a.x3 = L.x3;
+        a.wgt_wino = L.d_wino; set_wino_grid(a);
+        a.acc_scale = (L.x3 == 3) ? std::ldexp(1.0f, -(L.mx_e + H2_ACT_EXP)) : 1.0f;
+        a.in_packed = a.out_packed = L.x3 ? 1 : 0;
+        a.mx_sa = 127 - MX_LO_EXP; a.mx_sb = 127 - L.mx_e; a.group_store = use_group_store(); set_fastdiv(a);
+        a.sat = m->d_sat;
+        pick_conv_tile(a, 32, &pl->wm[i], &pl->nb[i]);
+        if (a.x3 && (int64_t)n2 * a.hm * a.wm <= 192LL * 128) may_split = true;      // (conv.h KSPLIT_WS_BYTES; as lpips_plan)
+    }
+    // split-K partial sums at small batches: this handle's own; a failed allocation degrades to "never split"
+    if (may_split && !m->kws && !m->kws_tried) {
+        m->kws_tried = true;
+        if (hipMalloc((void**)&m->kws, KSPLIT_WS_BYTES) != hipSuccess) { (void)hipGetLastError(); m->kws = nullptr; }
+        else m->allocs.push_back((void*)m->kws);
+    }
+    for (int i = 0; i < NCONV; ++i) pl->args[i].ksplit_ws = may_split ? m->kws : nullptr;
+    EVR_HIP(hipMemcpyAsync(m->d_args + NCONV * (pl - m->plans), pl->args, NCONV * sizeof(ConvArgs), hipMemcpyHostToDevice, stream));
+    pl->n = n; pl->stamp = ++m->clock; *out = pl;
+    return EVR_OK;
+}
+
+template <int FMT>
+static int launch_conv1_1(const Conv11Args& c, hipStream_t stream) {
+    const int64_t total = (int64_t)2 * c.n * c.H * ((c.W + C11_PX - 1) / C11_PX) * 4;
+    hipLaunchKernelGGL(vgg_conv1_1_kernel<FMT>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, c);
+    EVR_LAUNCH_CHECK();
+    return EVR_OK;
+}
+
+// one pass: np pairs starting at img / ref, scores to out[0..np) (and out_layers[0..5 np))
+static int vgg_pass(evr_lpips_vgg* m, const float* img, const float* ref, int np, int clip, double* out, double* out_layers, hipStream_t stream) {
+    int rc;
+    evr_lpips_vgg::Plan* P = nullptr;
+    if ((rc = vgg_plan(m, np, stream, &P))) return rc;
+    ConvArgs* const d_args = m->d_args + NCONV * (P - m->plans);
+    const int fmt = packed_fmt(m->mode);
+    Conv11Args c1{};
+    c1.img = img; c1.ref = ref; c1.n = np; c1.H = m->H; c1.W = m->W; c1.clip = clip;
+    c1.wg = m->d_wg; c1.wb = m->d_wb; c1.bias = m->d_b1; c1.bias_in = m->d_b1in; c1.out = m->act[0]; c1.sat = m->d_sat;
+    if ((rc = fmt == 2 ? launch_conv1_1<2>(c1, stream) : fmt == 1 ? launch_conv1_1<1>(c1, stream) : launch_conv1_1<0>(c1, stream))) return rc;
+    FinalArgs fa{};
+    int ci = 0;
+    for (int l = 0; l < 5; ++l) {
+        for (; ci < NCONV && VGG_LEVEL[ci] == l; ++ci)
+            if ((rc = launch_conv_igemm(P->args[ci], d_args + ci, 32, P->wm[ci], P->nb[ci], stream))) return rc;
+        // the tap layer sits where the level's last convolution wrote it; its pool goes to the other buffer
+        const int src = conv_src(ci - 1) ^ 1;
+        TapArgs t{};
+        t.feat = m->act[src]; t.pooled = l < 4 ? m->act[src ^ 1] : nullptr; t.lin = m->d_lin[l];
+        t.n = np; t.h = m->h[l]; t.w = m->w[l]; t.C = TAP_C[l]; t.fmt = fmt;
+        t.partials = m->partials + (size_t)l * m->cap * SCORE_BLOCKS_MAX;
+        const int nwin = ((t.h + 1) / 2) * ((t.w + 1) / 2), blocks = score_blocks(np, nwin, t.C);
+        hipLaunchKernelGGL(vgg_pool_score_kernel, dim3(blocks, np), dim3(256), 0, stream, t);
+        EVR_LAUNCH_CHECK();
+        fa.partials[l] = t.partials; fa.hw[l] = t.h * t.w; fa.blocks[l] = blocks;
+    }
+    hipLaunchKernelGGL(vgg_final_kernel, dim3(np), dim3(64), 0, stream, fa, np, out, out_layers);
+    EVR_LAUNCH_CHECK();
+    return EVR_OK;
+}
+
+extern "C" int evr_lpips_vgg_forward(evr_lpips_vgg* m, const float* img, const float* ref, int n, int H, int W, int clip, double* out,
+                                     double* out_layers, evr_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    EVR_REQUIRE(m && img && ref && out && n >= 1 && H >= 1 && W >= 1, "evr_lpips_vgg_forward: bad argument");
+    EVR_REQUIRE(H >= MIN_SIDE && W >= MIN_SIDE, "evr_lpips_vgg: image %dx%d too small for VGG-16 (four 2x2 pools need %d pixels a side)", W, H, MIN_SIDE);
+    EVR_REQUIRE((int64_t)2 * H * W * 64 * 4 < ACT_BUFFER_MAX_BYTES, "evr_lpips_vgg: image %dx%d too large: one pair's 64-channel features must stay below 2 GiB (H*W < 2^22)", W, H);
+    int rc;
+    const int P = pass_pairs(m, H, W), need = n < P ? n : P;
+    if (m->H != H || m->W != W || need > m->cap) if ((rc = vgg_buffers(m, need, H, W, stream))) { m->release(); m->H = m->W = 0; return rc; }
+    m->n = n;
+    for (int o = 0; o < n; o += P) {
+        const int np = n - o < P ? n - o : P;
+        if ((rc = vgg_pass(m, img + (int64_t)o * H * W, ref + (int64_t)o * H * W, np, clip, out + o, out_layers ? out_layers + (int64_t)5 * o : nullptr, stream))) return rc;
+    }
+    return EVR_OK;
+}
+
+// algorithmic operations of the last call: 2 per multiply-add of the thirteen convolutions, conv1_1 in the folded one-channel form it
+// runs in (304,704 multiply-adds per input pixel at sides that are multiples of 16)
+extern "C" double evr_lpips_vgg_flops(const evr_lpips_vgg* m) {
+    if (!m || m->n == 0) return 0.0;
+    double f = 2.0 * (2.0 * m->n) * m->H * m->W * 64 * 9;
+    for (int l = 0; l < NCONV; ++l) f += 2.0 * (2.0 * m->n) * m->h[VGG_LEVEL[l]] * m->w[VGG_LEVEL[l]] * VGG_CIN[l] * VGG_COUT[l] * 9;
+    return f;
+}
+
+// the range-guard counter (output runs beyond the packed format's exact range, packed.h sat_note) since the last read; cleared.
+// Waits for the stream.
+extern "C" int evr_lpips_vgg_saturation(evr_lpips_vgg* m, int64_t* count, evr_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    EVR_REQUIRE(m && count, "evr_lpips_vgg_saturation: null argument");
+    unsigned v = 0;
+    EVR_HIP(hipMemcpyAsync(&v, m->d_sat, sizeof(v), hipMemcpyDeviceToHost, stream));
+    EVR_HIP(hipMemsetAsync(m->d_sat, 0, sizeof(v), stream));
+    EVR_HIP(hipStreamSynchronize(stream));
+    *count = (int64_t)v;
+    return EVR_OK;
+}

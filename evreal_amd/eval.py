@@ -29,6 +29,7 @@ from .dataset import MemMapDataset
 from .dist import assign_sequences, force_collectives, reduce_metric_sums
 from .eval_metrics import EvalMetricsTracker, MetricTracker
 from .lib import EvrError
+from .lpips import LPIPSVGG
 from . import prepost
 from .prepost import normalize_event_tensor, post_process_normalization
 
@@ -303,7 +304,7 @@ class _ChunkBuffers:
     """Device + pinned host buffers of one in-flight chunk (the frame loop keeps two: while the host books chunk c, the
     GPU already works on chunk c + 1)."""
 
-    def __init__(self, S, B, H, W, dev, want_scores, want_lpips, want_u8, with_refs, want_niqe=False, want_brisque=False, want_fr=False, want_piqe=False, want_gmsd=False):
+    def __init__(self, S, B, H, W, dev, want_scores, want_lpips, want_u8, with_refs, want_niqe=False, want_brisque=False, want_fr=False, want_piqe=False, want_gmsd=False, want_lpips_vgg=False):
         f32 = dict(dtype=torch.float32, device=dev)
         self.grid = torch.empty((CHUNK, S, B, H, W), **f32)
         self.stats = torch.zeros((CHUNK, S, 3), dtype=torch.float64, device=dev)
@@ -323,6 +324,8 @@ class _ChunkBuffers:
         self.h_fr = torch.empty((CHUNK * S, 2), dtype=torch.float64).pin_memory() if want_fr else None
         self.gm = torch.zeros((CHUNK * S, 2), dtype=torch.float64, device=dev) if want_gmsd else None    # gmsd, mean GMS
         self.h_gm = torch.empty((CHUNK * S, 2), dtype=torch.float64).pin_memory() if want_gmsd else None
+        self.lv = torch.zeros((CHUNK * S,), dtype=torch.float64, device=dev) if want_lpips_vgg else None
+        self.h_lv = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_lpips_vgg else None
         self.u8 = torch.empty((CHUNK, S, H, W), dtype=torch.uint8, device=dev) if want_u8 else None
         self.h_u8 = torch.empty((CHUNK, S, H, W), dtype=torch.uint8).pin_memory() if want_u8 else None
         self.ev_model = torch.cuda.Event()
@@ -340,7 +343,7 @@ def eval_method_on_sequences(dataset_name, eval_config, method_name, model, meth
 
     The loop is a two-deep pipeline over chunks of CHUNK steps: ONE tensorizer launch voxelizes the chunk's windows of all
     slots (their events share one resident array, dataset.SequenceBatch) straight into the step-major batch tensor; the
-    network steps run back to back on the main stream; post-normalisation, MSE/SSIM/LPIPS/PSNR/MS-SSIM/GMSD/NIQE/BRISQUE/PIQE of every frame of the chunk and
+    network steps run back to back on the main stream; post-normalisation, MSE/SSIM/LPIPS/LPIPS-VGG/PSNR/MS-SSIM/GMSD/NIQE/BRISQUE/PIQE of every frame of the chunk and
     the uint8 conversion for the PNG writers run on a second HIP stream (as pipeline.HotPath does per step) and land in
     pinned host memory; the host books chunk c (text files, PNG pool) while the GPU is already inside chunk c + 1.
     Returns [(num_evaluated, mean_scores)] in the order of `sequences`.
@@ -388,8 +391,10 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
     fr_metrics = trackers[0]._fr
     fr_psnr, fr_ms = 'psnr' in pre, 'ms_ssim' in pre and fr_metrics.too_small(H, W) is None
     gm_model = trackers[0]._gmsd if 'gmsd' in pre and trackers[0]._gmsd.too_small(H, W) is None else None
+    # lpips-vgg: left out where the frames are too small for it (the trackers print the exception and reset the metric)
+    lv_model = EvalMetricsTracker._lpips_vgg_model() if 'lpips-vgg' in pre and LPIPSVGG.too_small(H, W) is None else None
     bufs = [_ChunkBuffers(S, batch.num_bins, H, W, dev, bool(set(pre) & {'mse', 'ssim'}), lp_model is not None, want_u8,
-                          all(ds.has_images for ds in dss), nq_model is not None, bq_model is not None, fr_psnr or fr_ms, pq_model is not None, gm_model is not None) for _ in range(2)]
+                          all(ds.has_images for ds in dss), nq_model is not None, bq_model is not None, fr_psnr or fr_ms, pq_model is not None, gm_model is not None, lv_model is not None) for _ in range(2)]
     main = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(device=dev)
     policy = _range_guard_policy(eval_config)
@@ -433,6 +438,9 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
                 if b.gm is not None:
                     gm_model(im, rf, clip=True, out=b.gm[:n * S])
                     b.h_gm[:n * S].copy_(b.gm[:n * S], non_blocking=True)
+                if b.lv is not None:
+                    lv_model(im, rf, clip=True, out=b.lv[:n * S])
+                    b.h_lv[:n * S].copy_(b.lv[:n * S], non_blocking=True)
             if b.nq is not None:
                 nq_model(im, clip=True, out=b.nq[:n * S])
                 b.h_nq[:n * S].copy_(b.nq[:n * S], non_blocking=True)
@@ -463,6 +471,7 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
         pq = b.h_pq[:n * S].numpy().reshape(n, S) if b.h_pq is not None else None
         fr = b.h_fr[:n * S].numpy().reshape(n, S, 2) if b.h_fr is not None else None
         gm = b.h_gm[:n * S].numpy().reshape(n, S, 2) if b.h_gm is not None else None
+        lv = b.h_lv[:n * S].numpy().reshape(n, S) if b.h_lv is not None else None
         for j in range(S):
             it = b.items[j]
             if not it:
@@ -480,6 +489,7 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
                 if fr_psnr and fr is not None: scores['psnr'] = fr[:k, j, 0].copy()
                 if fr_ms and fr is not None: scores['ms_ssim'] = fr[:k, j, 1].copy()
                 if gm is not None: scores['gmsd'] = gm[:k, j, 0].copy()
+                if lv is not None: scores['lpips-vgg'] = lv[:k, j].copy()
             u8 = b.h_u8[:k, j] if b.h_u8 is not None else None      # (a strided view of the pinned buffer: the native writers copy it inside the call)
             if ds.has_images:
                 refs = b.refs[:k, j] if b.refs is not None else ds.frames(tb['frame_index'][it])[:, 0]

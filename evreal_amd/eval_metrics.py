@@ -17,6 +17,8 @@ Metric plug-ins keep the reference's contract (utils/eval_metrics.py:18-75): a `
     the same four-frame queue; EVREAL_GPU_PIQE=0 sends the name to pyiqa instead;
   * 'gmsd' (full-reference, closed form: no file needed) runs batched on the GPU in fp64 (evr_gmsd) and is booked through the
     same four-frame queue; EVREAL_GPU_GMSD=0 sends the name to pyiqa instead;
+  * 'lpips-vgg' (full-reference, the VGG-16 backbone of LPIPS) runs batched on the GPU (evr_lpips_vgg_*) when a weights file is
+    available, and is booked through the same four-frame queue;
   * anything registered with `register_metric(name, factory)` runs per frame on host arrays, exactly like the reference's
     MseMetric / SsimMetric (clipped float32 [H,W] images in, a float or a list of floats out);
   * any other name is looked up in pyiqa.list_models() when pyiqa is importable (queued in batches of 4 as
@@ -32,6 +34,7 @@ from os.path import join
 import numpy as np
 import torch
 
+from .lpips import LPIPSVGG
 from .prepost import GMSD, FullRefMetrics, Metrics, histogram_equalization
 
 GPU_METRICS = ('mse', 'ssim')
@@ -40,6 +43,7 @@ FR_METRICS_ENV = 'EVREAL_GPU_FR_METRICS'        # '0': psnr / ms_ssim go to pyiq
 PIQE_ENV = 'EVREAL_GPU_PIQE'                    # '0': piqe goes to pyiqa (or is unknown without it)
 GMSD_ENV = 'EVREAL_GPU_GMSD'                    # '0': gmsd goes to pyiqa (or is unknown without it)
 LPIPS_WEIGHTS_ENV = 'EVREAL_LPIPS_WEIGHTS'      # path to a pyiqa/lpips AlexNet-v0.1 state_dict (torch.save'd)
+LPIPS_VGG_WEIGHTS_ENV = 'EVREAL_LPIPS_VGG_WEIGHTS'      # path to a pyiqa lpips-vgg (VGG-16, v0.1) state_dict (torch.save'd)
 NIQE_MODEL_ENV = 'EVREAL_NIQE_MODEL'            # path to a NIQE pristine model (.mat of the MATLAB release, or .npz)
 NIQE_MODEL_FILES = (os.path.join('pretrained', 'niqe_modelparameters.mat'), os.path.join('pretrained', 'niqe_model.npz'))
 BRISQUE_MODEL_ENV = 'EVREAL_BRISQUE_MODEL'      # path to a BRISQUE model (.npz, or a libsvm text model such as allmodel)
@@ -53,6 +57,14 @@ def _load_lpips():
         return None
     from .lpips import LPIPS
     return LPIPS(torch.load(path, map_location='cpu', weights_only=False))
+
+
+def _load_lpips_vgg():
+    """As _load_lpips: made where pyiqa exists by torch.save(pyiqa.create_metric('lpips-vgg').net.state_dict(), path)."""
+    path = os.environ.get(LPIPS_VGG_WEIGHTS_ENV, os.path.join('pretrained', 'lpips_vgg.pth'))
+    if not os.path.exists(path):
+        return None
+    return LPIPSVGG(torch.load(path, map_location='cpu', weights_only=False))
 
 
 def gpu_fr_metrics_enabled():
@@ -312,6 +324,8 @@ class EvalMetricsTracker:
                 self.metrics.append(GpuMetric(name))
             elif name == 'lpips' and self._lpips_model() is not None:
                 self.metrics.append(GpuMetric(name))
+            elif name == 'lpips-vgg' and self._lpips_vgg_model() is not None:
+                self.metrics.append(QueuedGpuMetric(name, no_ref=False))
             elif name == 'niqe' and self._niqe_model() is not None:
                 self.metrics.append(QueuedGpuMetric(name, no_ref=True))
             elif name == 'brisque' and self._brisque_model() is not None:
@@ -346,6 +360,18 @@ class EvalMetricsTracker:
                 print(f"lpips: no weights at ${LPIPS_WEIGHTS_ENV} or pretrained/lpips_alex.pth (pyiqa downloads them; "
                       "offline they must be provided) -> falling back to pyiqa if it is installed")
         return cls._lpips_cache[1]
+
+    _lpips_vgg_cache = [False, None]
+
+    @classmethod
+    def _lpips_vgg_model(cls):
+        """One LPIPS-VGG handle per process; None without a weights file (then `lpips-vgg` goes to pyiqa, or is unknown)."""
+        if not cls._lpips_vgg_cache[0]:
+            cls._lpips_vgg_cache = [True, _load_lpips_vgg()]
+            if cls._lpips_vgg_cache[1] is None:
+                print(f"lpips-vgg: no weights at ${LPIPS_VGG_WEIGHTS_ENV} or pretrained/lpips_vgg.pth (pyiqa downloads them; "
+                      "offline they must be provided) -> falling back to pyiqa if it is installed")
+        return cls._lpips_vgg_cache[1]
 
     _niqe_cache = [False, None]
 
@@ -434,13 +460,14 @@ class EvalMetricsTracker:
         return [m.name for m in self.metrics if getattr(m, 'on_gpu', False)]
 
     def _shape_refused(self, m, imgs):
-        """A GPU metric that is not defined on frames of this size (ms_ssim below 161 pixels a side, gmsd below 2) ends like a metric that
+        """A GPU metric that is not defined on frames of this size (ms_ssim below 161 pixels a side, gmsd below 2, lpips-vgg below 16) ends like a metric that
         raises on every frame in the reference (utils/eval_metrics.py:233-242: the exception is printed, the metric reset): its
         file stays empty and its mean is -1.  Decided from the shape, before any launch, and printed once per sequence."""
         if m.name in self._failed:
             return True
         H, W = int(imgs.shape[-2]), int(imgs.shape[-1])
-        why = FullRefMetrics.too_small(H, W) if m.name == 'ms_ssim' else GMSD.too_small(H, W) if m.name == 'gmsd' else None
+        why = (FullRefMetrics.too_small(H, W) if m.name == 'ms_ssim' else GMSD.too_small(H, W) if m.name == 'gmsd'
+               else LPIPSVGG.too_small(H, W) if m.name == 'lpips-vgg' else None)
         if why is None:
             return False
         print("Exception in metric " + m.get_name() + ": " + why)
@@ -494,7 +521,7 @@ class EvalMetricsTracker:
             rsel = refs[js].contiguous() if refs is not None else None
         if gpu:
             want = {m.name for m in gpu}
-            scores = lp = nq = bq = pq = fr = gm = None
+            scores = lp = nq = bq = pq = fr = gm = lv = None
             if not have_pre:
                 if want & set(GPU_METRICS):
                     scores = self._gpu(isel, rsel, mse='mse' in want, ssim='ssim' in want, clip=True).cpu().numpy()
@@ -505,13 +532,14 @@ class EvalMetricsTracker:
                 if want & set(FR_METRICS):
                     fr = self._fr(isel, rsel, psnr='psnr' in want, ms_ssim='ms_ssim' in want, clip=True).cpu().numpy()
                 gm = self._gmsd(isel, rsel, clip=True).cpu().numpy() if 'gmsd' in want else None
+                lv = self._lpips_vgg_model()(isel, rsel, clip=True).cpu().numpy() if 'lpips-vgg' in want else None
             for m in gpu:
                 if have_pre:
                     col = np.asarray(pre[m.name])[sel]
                 else:
                     col = (scores[:, 0] if m.name == 'mse' else scores[:, 1] if m.name == 'ssim' else nq if m.name == 'niqe'
                            else bq if m.name == 'brisque' else pq if m.name == 'piqe' else fr[:, 0] if m.name == 'psnr'
-                           else fr[:, 1] if m.name == 'ms_ssim' else gm if m.name == 'gmsd' else lp)
+                           else fr[:, 1] if m.name == 'ms_ssim' else gm if m.name == 'gmsd' else lv if m.name == 'lpips-vgg' else lp)
                 if isinstance(m, QueuedGpuMetric):
                     self._append(join(self.output_dir, m.name + '.txt'), m.book(self.quan_eval_indices, idxs, col))
                     continue
@@ -632,6 +660,7 @@ class EvalMetricsTracker:
         """eval_metrics.py:225-228: flush the queued metrics; then wait for this tracker's files.  wait_png=False (the drop-in's
         sequence loops): the native writers keep working on this tracker's last frames while the next sequence starts; the caller
         owes a wait_all_pngs() before it reports the dataset (evreal_amd.eval does it per dataset) -- 3 ms per 160-frame sequence."""
+        self._warn_lpips_vgg_range()
         for m in self.metrics:
             if isinstance(m, QueuedGpuMetric):
                 m.finish_queue()
@@ -653,6 +682,21 @@ class EvalMetricsTracker:
         if wait_png:
             self._wait_native()                              # ... and a native writer's failure here
         self._close_files()
+
+    def _warn_lpips_vgg_range(self):
+        """One line per sequence when an activation of the VGG trunk left the exact range of the arithmetic mode's packed format
+        (the handle's counter, read and cleared here: it is shared by the trackers of a process, so sequences evaluated in lock-step
+        report together with the first of them that finishes).  The scores are kept; EVR_ARITH=fp32 computes them without a limit."""
+        # (only this project's GPU metric: the same name served by pyiqa or by register_metric has no handle)
+        if not any(m.name == 'lpips-vgg' and getattr(m, 'on_gpu', False) for m in self.metrics):
+            return
+        model = self._lpips_vgg_cache[1]
+        if model is None or 'lpips-vgg' in self._failed or not self.quan_eval_indices:
+            return
+        count = model.saturation()
+        if count:
+            print(f"WARNING: lpips-vgg: {count} activation runs left the exact range of the packed format in {self.output_dir} "
+                  "(scores kept; EVR_ARITH=fp32 evaluates without the limit)")
 
     @classmethod
     def wait_all_pngs(cls):

@@ -82,6 +82,11 @@ SYMBOLS = {
     'evr_lpips_destroy': (c_int, [c_void_p]),
     'evr_lpips_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'evr_lpips_flops': (c_double, [c_void_p]),
+    'evr_lpips_vgg_create': (c_int, [ctypes.POINTER(Tensor), c_int, c_int, ctypes.POINTER(c_void_p)]),
+    'evr_lpips_vgg_destroy': (c_int, [c_void_p]),
+    'evr_lpips_vgg_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'evr_lpips_vgg_flops': (c_double, [c_void_p]),
+    'evr_lpips_vgg_saturation': (c_int, [c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     'evr_niqe_create': (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
     'evr_niqe_destroy': (c_int, [c_void_p]),
     'evr_niqe_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),

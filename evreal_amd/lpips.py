@@ -7,23 +7,29 @@ import torch
 from . import lib as _lib
 
 
+def _tensor_table(state_dict):
+    """-> (ctypes array of evr_tensor, the host arrays it points into) for a state dict of tensors or arrays."""
+    sd = {k: np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float32)
+          for k, v in state_dict.items()}
+    tensors = (_lib.Tensor * len(sd))()
+    keep = []
+    for i, (k, v) in enumerate(sd.items()):
+        name = k.encode(); keep.append((name, v))
+        tensors[i].name = name
+        tensors[i].data_host = v.ctypes.data_as(ctypes.c_void_p)
+        tensors[i].ndim = v.ndim
+        for d in range(v.ndim):
+            tensors[i].shape[d] = v.shape[d]
+    return tensors, keep
+
+
 class LPIPS:
     def __init__(self, state_dict):
         _lib.require_gpu()
         self.lib = _lib.load()
-        sd = {k: np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float32)
-              for k, v in state_dict.items()}
-        tensors = (_lib.Tensor * len(sd))()
-        self._keep = []
-        for i, (k, v) in enumerate(sd.items()):
-            name = k.encode(); self._keep.append((name, v))
-            tensors[i].name = name
-            tensors[i].data_host = v.ctypes.data_as(ctypes.c_void_p)
-            tensors[i].ndim = v.ndim
-            for d in range(v.ndim):
-                tensors[i].shape[d] = v.shape[d]
+        tensors, self._keep = _tensor_table(state_dict)
         h = ctypes.c_void_p()
-        _lib.check(self.lib.evr_lpips_create(tensors, len(sd), ctypes.byref(h)), 'evr_lpips_create')
+        _lib.check(self.lib.evr_lpips_create(tensors, len(tensors), ctypes.byref(h)), 'evr_lpips_create')
         self.handle = h
 
     def __call__(self, img, ref, clip=True, out=None):
@@ -44,5 +50,71 @@ class LPIPS:
         try:
             if self.handle is not None:
                 self.lib.evr_lpips_destroy(self.handle); self.handle = None
+        except Exception:
+            pass
+
+
+class LPIPSVGG:
+    """pyiqa.create_metric('lpips-vgg') stand-in on the GPU (evr_lpips_vgg_*): same call shape as LPIPS.
+
+    max_pairs: frame pairs per pass (0: as many as keep the handle's two activation buffers within 1 GiB); a call with more pairs
+    runs in passes."""
+    MIN_SIDE = 16           # four floor-mode 2x2 pools must leave one pixel
+
+    def __init__(self, state_dict, max_pairs=0):
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        tensors, self._keep = _tensor_table(state_dict)
+        h = ctypes.c_void_p()
+        self.handle = None
+        _lib.check(self.lib.evr_lpips_vgg_create(tensors, len(tensors), int(max_pairs), ctypes.byref(h)), 'evr_lpips_vgg_create')
+        self.handle = h
+
+    @classmethod
+    def too_small(cls, H, W):
+        """The message of the exception `lpips-vgg` raises on frames of this size, or None where it is defined."""
+        if min(H, W) >= cls.MIN_SIDE:
+            return None
+        return (f"lpips-vgg needs frames of at least {cls.MIN_SIDE}x{cls.MIN_SIDE} pixels (VGG-16 pools 2x2 four times), "
+                f"got {H}x{W}")
+
+    def _forward(self, img, ref, clip, out, layers):
+        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dim() == 3
+        assert img.dtype == ref.dtype == torch.float32
+        img = img.contiguous(); ref = ref.contiguous()
+        n, H, W = img.shape
+        if self.too_small(H, W):
+            raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=img.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n
+        _lib.check(self.lib.evr_lpips_vgg_forward(self.handle, _lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0,
+                                                  _lib.ptr(out), _lib.ptr(layers), _lib.stream_ptr()), 'evr_lpips_vgg_forward')
+        return out
+
+    def __call__(self, img, ref, clip=True, out=None):
+        """img, ref: cuda fp32 [n,H,W] in [0,1] -> double [n] on device."""
+        return self._forward(img, ref, clip, out, None)
+
+    def layers(self, img, ref, clip=True):
+        """-> double [n,5]: the distances of relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 (their sum is the score)."""
+        layers = torch.empty((img.shape[0], 5), dtype=torch.float64, device=img.device)
+        self._forward(img, ref, clip, None, layers)
+        return layers
+
+    def saturation(self):
+        """Output runs that left the exact range of the arithmetic mode's activation format since the last call (the counter is
+        cleared); waits for the current stream."""
+        c = ctypes.c_int64(0)
+        _lib.check(self.lib.evr_lpips_vgg_saturation(self.handle, ctypes.byref(c), _lib.stream_ptr()), 'evr_lpips_vgg_saturation')
+        return int(c.value)
+
+    def flops(self):
+        return float(self.lib.evr_lpips_vgg_flops(self.handle))
+
+    def __del__(self):
+        try:
+            if self.handle is not None:
+                self.lib.evr_lpips_vgg_destroy(self.handle); self.handle = None
         except Exception:
             pass

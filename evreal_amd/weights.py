@@ -216,6 +216,31 @@ def synth_lpips_state_dict(seed=0):
     return sd
 
 
+def lpips_vgg_schema():
+    """State dict of pyiqa's LPIPS(net='vgg', version='0.1'): the thirteen 3x3 convolutions of torchvision's vgg16.features under
+    their indices there, grouped into the five slices that end at relu1_2, relu2_2, relu3_3, relu4_3, relu5_3, + the five 1x1 'lin'
+    heads.  The names are recalled from the published code and stay unpinned until tests/test_lpips_vgg_pins.py has run."""
+    s = OrderedDict()
+    for name, co, ci in [("net.slice1.0", 64, 3), ("net.slice1.2", 64, 64), ("net.slice2.5", 128, 64), ("net.slice2.7", 128, 128),
+                         ("net.slice3.10", 256, 128), ("net.slice3.12", 256, 256), ("net.slice3.14", 256, 256),
+                         ("net.slice4.17", 512, 256), ("net.slice4.19", 512, 512), ("net.slice4.21", 512, 512),
+                         ("net.slice5.24", 512, 512), ("net.slice5.26", 512, 512), ("net.slice5.28", 512, 512)]:
+        _conv(s, name, co, ci, 3)
+    for l, c in enumerate([64, 128, 256, 512, 512]):
+        s[f'lin{l}.model.1.weight'] = (1, c, 1, 1)
+    return s
+
+
+def synth_lpips_vgg_state_dict(seed=0):
+    """Deterministic stand-in for the (offline-unobtainable) LPIPS-VGG weights; the lin heads are non-negative.  gain = sqrt(2):
+    with zero-mean weights a ReLU halves the second moment, and at gain 1 the thirteen layers fade (relu5_3 peaks at 0.2)."""
+    sd = synth_state_dict(lpips_vgg_schema(), seed=seed, gain=float(np.sqrt(2.0)))
+    for k in sd:
+        if k.startswith('lin'):
+            sd[k] = np.abs(sd[k]).astype(np.float32)
+    return sd
+
+
 def synth_state_dict(schema, seed=0, gain=1.0, fixed=None):
     """Deterministic fp32 numpy weights for a schema.  Each tensor is drawn from its own
     PCG64 stream keyed by (seed, crc32(name)) so adding/removing tensors never shifts the

@@ -305,6 +305,29 @@ int evr_lpips_forward(evr_lpips* m, const float* img, const float* ref, int n, i
 double evr_lpips_flops(const evr_lpips* m);
 
 /* ----------------------------------------------------------------------------------------------
+ * LPIPS (VGG-16, v0.1).  Replaces PyIqaMetricFactory.get_metric('lpips-vgg'), called like 'lpips' above.
+ * tensors: the metric's state_dict with pyiqa's names: the thirteen convolutions "net.slice1.{0,2}", "net.slice2.{5,7}",
+ * "net.slice3.{10,12,14}", "net.slice4.{17,19,21}", "net.slice5.{24,26,28}" (".weight", ".bias") and the heads
+ * "lin0.model.1.weight" ... "lin4.model.1.weight" (64, 128, 256, 512, 512 elements).  img, ref: [n,H,W] in [0,1] (clip: clamp
+ * first), H and W at least 16 (four 2x2 pools) and H * W below 2^22; out: double [n]; out_layers: double [n,5], the five layers' distances whose sum
+ * is out, or null.  PARITY UNPINNED: pyiqa, torchvision and the downloaded weights are unavailable offline; the names above and the
+ * pool positions are recalled from the published code (csrc/lpips_vgg.hip).
+ * The handle owns two activation buffers of 2 * P * H * W * 64 * 4 bytes each, P pairs per pass: the largest P for which both fit
+ * 1 GiB (at least 1), or max_pairs when that is positive; a call with n > P runs in passes.  Buffers only grow (a new H x W
+ * re-allocates) and the launch plans of the last eight distinct pass sizes are cached.  One handle is used from one host thread
+ * and one stream at a time.
+ * evr_lpips_vgg_saturation: the number of output runs that left the exact range of the arithmetic mode's activation format since the
+ * last read (0 in the exact-fp32 mode); clears the counter; waits for the stream.
+ */
+typedef struct evr_lpips_vgg evr_lpips_vgg;
+int evr_lpips_vgg_create(const evr_tensor* tensors, int n_tensors, int max_pairs, evr_lpips_vgg** out);
+int evr_lpips_vgg_destroy(evr_lpips_vgg* m);
+int evr_lpips_vgg_forward(evr_lpips_vgg* m, const float* img, const float* ref, int n, int H, int W, int clip,
+                          double* out, double* out_layers, evr_stream_t stream);
+double evr_lpips_vgg_flops(const evr_lpips_vgg* m);
+int evr_lpips_vgg_saturation(evr_lpips_vgg* m, int64_t* count, evr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * NIQE (Mittal, Soundararajan, Bovik 2013), the no-reference score of `-qm niqe` for datasets without frames
  * (utils/eval_metrics.py:100-156 -> pyiqa), after the published MATLAB release.  Conventions (tests/nriqa_ref.py):
  * u = rint(255 * v) in fp32 (v clamped to [0,1] first when clip != 0), fp64 from there on; the frame is cropped to whole
