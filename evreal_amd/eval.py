@@ -27,9 +27,8 @@ from . import model as model_arch
 from .config import get_dataset_configs, get_eval_configs, get_method_config
 from .dataset import MemMapDataset
 from .dist import assign_sequences, force_collectives, reduce_metric_sums
-from .eval_metrics import EvalMetricsTracker, MetricTracker
+from .eval_metrics import DEFAULT_METRICS, EvalMetricsTracker, MetricTracker, chunk_scorers
 from .lib import EvrError
-from .lpips import LPIPSVGG
 from . import prepost
 from .prepost import normalize_event_tensor, post_process_normalization
 
@@ -304,28 +303,15 @@ class _ChunkBuffers:
     """Device + pinned host buffers of one in-flight chunk (the frame loop keeps two: while the host books chunk c, the
     GPU already works on chunk c + 1)."""
 
-    def __init__(self, S, B, H, W, dev, want_scores, want_lpips, want_u8, with_refs, want_niqe=False, want_brisque=False, want_fr=False, want_piqe=False, want_gmsd=False, want_lpips_vgg=False):
+    def __init__(self, S, B, H, W, dev, scorers, *, want_u8, with_refs):
         f32 = dict(dtype=torch.float32, device=dev)
         self.grid = torch.empty((CHUNK, S, B, H, W), **f32)
         self.stats = torch.zeros((CHUNK, S, 3), dtype=torch.float64, device=dev)
         self.imgs = torch.empty((CHUNK, S, 1, H, W), **f32)
         self.refs = torch.zeros((CHUNK, S, H, W), **f32) if with_refs else None
-        self.scores = torch.zeros((CHUNK * S, 2), dtype=torch.float64, device=dev) if want_scores else None
-        self.lp = torch.zeros((CHUNK * S,), dtype=torch.float64, device=dev) if want_lpips else None
-        self.h_scores = torch.empty((CHUNK * S, 2), dtype=torch.float64).pin_memory() if want_scores else None
-        self.h_lp = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_lpips else None
-        self.nq = torch.zeros((CHUNK * S,), dtype=torch.float64, device=dev) if want_niqe else None
-        self.h_nq = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_niqe else None
-        self.bq = torch.zeros((CHUNK * S,), dtype=torch.float64, device=dev) if want_brisque else None
-        self.h_bq = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_brisque else None
-        self.pq = torch.zeros((CHUNK * S,), dtype=torch.float64, device=dev) if want_piqe else None
-        self.h_pq = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_piqe else None
-        self.fr = torch.zeros((CHUNK * S, 2), dtype=torch.float64, device=dev) if want_fr else None      # psnr, ms_ssim
-        self.h_fr = torch.empty((CHUNK * S, 2), dtype=torch.float64).pin_memory() if want_fr else None
-        self.gm = torch.zeros((CHUNK * S, 2), dtype=torch.float64, device=dev) if want_gmsd else None    # gmsd, mean GMS
-        self.h_gm = torch.empty((CHUNK * S, 2), dtype=torch.float64).pin_memory() if want_gmsd else None
-        self.lv = torch.zeros((CHUNK * S,), dtype=torch.float64, device=dev) if want_lpips_vgg else None
-        self.h_lv = torch.empty((CHUNK * S,), dtype=torch.float64).pin_memory() if want_lpips_vgg else None
+        # the score rows of every active scorer (eval_metrics._SCORERS), one row per frame and slot
+        self.scores = {s: torch.zeros((CHUNK * S, s.width), dtype=torch.float64, device=dev) for s in scorers}
+        self.h_scores = {s: torch.empty((CHUNK * S, s.width), dtype=torch.float64).pin_memory() for s in scorers}
         self.u8 = torch.empty((CHUNK, S, H, W), dtype=torch.uint8, device=dev) if want_u8 else None
         self.h_u8 = torch.empty((CHUNK, S, H, W), dtype=torch.uint8).pin_memory() if want_u8 else None
         self.ev_model = torch.cuda.Event()
@@ -343,7 +329,7 @@ def eval_method_on_sequences(dataset_name, eval_config, method_name, model, meth
 
     The loop is a two-deep pipeline over chunks of CHUNK steps: ONE tensorizer launch voxelizes the chunk's windows of all
     slots (their events share one resident array, dataset.SequenceBatch) straight into the step-major batch tensor; the
-    network steps run back to back on the main stream; post-normalisation, MSE/SSIM/LPIPS/LPIPS-VGG/PSNR/MS-SSIM/GMSD/NIQE/BRISQUE/PIQE of every frame of the chunk and
+    network steps run back to back on the main stream; post-normalisation, the GPU metrics (eval_metrics._SCORERS) of every frame of the chunk and
     the uint8 conversion for the PNG writers run on a second HIP stream (as pipeline.HotPath does per step) and land in
     pinned host memory; the host books chunk c (text files, PNG pool) while the GPU is already inside chunk c + 1.
     Returns [(num_evaluated, mean_scores)] in the order of `sequences`.
@@ -381,20 +367,11 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
     # (no-reference metrics too when no sequence has frames; a group that mixes the two kinds books frame by frame)
     pre = trackers[0].wants_precomputed() if len({ds.has_images for ds in dss}) == 1 else []
     want_u8 = trackers[0].save_images
-    lp_model = EvalMetricsTracker._lpips_model() if 'lpips' in pre else None
-    nq_model = EvalMetricsTracker._niqe_model() if 'niqe' in pre else None
-    bq_model = EvalMetricsTracker._brisque_model() if 'brisque' in pre else None
-    pq_model = EvalMetricsTracker._piqe_model() if 'piqe' in pre else None
-    gpu_metrics = trackers[0]._gpu
-    # psnr / ms_ssim: one launch set for both; ms_ssim is left out where the frames are too small for it (decided from the shape:
-    # the trackers print the exception and reset the metric, as the reference does for a metric that raises)
-    fr_metrics = trackers[0]._fr
-    fr_psnr, fr_ms = 'psnr' in pre, 'ms_ssim' in pre and fr_metrics.too_small(H, W) is None
-    gm_model = trackers[0]._gmsd if 'gmsd' in pre and trackers[0]._gmsd.too_small(H, W) is None else None
-    # lpips-vgg: left out where the frames are too small for it (the trackers print the exception and reset the metric)
-    lv_model = EvalMetricsTracker._lpips_vgg_model() if 'lpips-vgg' in pre and LPIPSVGG.too_small(H, W) is None else None
-    bufs = [_ChunkBuffers(S, batch.num_bins, H, W, dev, bool(set(pre) & {'mse', 'ssim'}), lp_model is not None, want_u8,
-                          all(ds.has_images for ds in dss), nq_model is not None, bq_model is not None, fr_psnr or fr_ms, pq_model is not None, gm_model is not None, lv_model is not None) for _ in range(2)]
+    # [(scorer, handle, names)]: a name the frames are too small for is left out (decided from the shape: the trackers print the
+    # exception and reset the metric, as the reference does for a metric that raises)
+    scorers = chunk_scorers(trackers[0], pre, H, W)
+    bufs = [_ChunkBuffers(S, batch.num_bins, H, W, dev, [s for s, _, _ in scorers], want_u8=want_u8,
+                          with_refs=all(ds.has_images for ds in dss)) for _ in range(2)]
     main = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(device=dev)
     policy = _range_guard_policy(eval_config)
@@ -421,35 +398,21 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
             side.wait_event(b.ev_model)
             im = b.imgs[:n].view(n * S, H, W)
             post_process_normalization(im, post_norm)
+
+            def score(s, handle, names, rf):
+                s.run(handle, im, rf, names, b.scores[s][:n * S])
+                b.h_scores[s][:n * S].copy_(b.scores[s][:n * S], non_blocking=True)
             if b.refs is not None:
                 for j, (ds, it) in enumerate(zip(dss, items)):
                     if it:
                         b.refs[:len(it), j] = ds.frames(fidx[j][c0:c0 + len(it)])[:, 0]
                 rf = b.refs[:n].view(n * S, H, W)
-                if b.scores is not None:
-                    b.scores[:n * S].copy_(gpu_metrics(im, rf, mse='mse' in pre, ssim='ssim' in pre, clip=True))
-                    b.h_scores[:n * S].copy_(b.scores[:n * S], non_blocking=True)
-                if b.lp is not None:
-                    b.lp[:n * S].copy_(lp_model(im, rf, clip=True))
-                    b.h_lp[:n * S].copy_(b.lp[:n * S], non_blocking=True)
-                if b.fr is not None:
-                    fr_metrics(im, rf, psnr=fr_psnr, ms_ssim=fr_ms, clip=True, out=b.fr[:n * S])
-                    b.h_fr[:n * S].copy_(b.fr[:n * S], non_blocking=True)
-                if b.gm is not None:
-                    gm_model(im, rf, clip=True, out=b.gm[:n * S])
-                    b.h_gm[:n * S].copy_(b.gm[:n * S], non_blocking=True)
-                if b.lv is not None:
-                    lv_model(im, rf, clip=True, out=b.lv[:n * S])
-                    b.h_lv[:n * S].copy_(b.lv[:n * S], non_blocking=True)
-            if b.nq is not None:
-                nq_model(im, clip=True, out=b.nq[:n * S])
-                b.h_nq[:n * S].copy_(b.nq[:n * S], non_blocking=True)
-            if b.bq is not None:
-                bq_model(im, clip=True, out=b.bq[:n * S])
-                b.h_bq[:n * S].copy_(b.bq[:n * S], non_blocking=True)
-            if b.pq is not None:
-                pq_model(im, clip=True, out=b.pq[:n * S])
-                b.h_pq[:n * S].copy_(b.pq[:n * S], non_blocking=True)
+                for s, handle, names in scorers:
+                    if not s.no_ref:
+                        score(s, handle, names, rf)
+            for s, handle, names in scorers:
+                if s.no_ref:
+                    score(s, handle, names, None)
             if b.u8 is not None:
                 b.u8[:n].copy_(torch.round(torch.clamp(b.imgs[:n, :, 0], 0.0, 1.0) * 255))     # eval_utils.py:83
                 b.h_u8[:n].copy_(b.u8[:n], non_blocking=True)
@@ -464,32 +427,13 @@ def _eval_method_on_sequences(dataset_name, eval_config, method_name, model, met
                 warned[0] = True
                 model.warn_if_saturated(', '.join(q['name'] for q in sequences) + " (range_guard: 'warn' -- results of the first pass are kept)")
         n = b.n
-        sc = b.h_scores[:n * S].numpy().reshape(n, S, 2) if b.h_scores is not None else None
-        lp = b.h_lp[:n * S].numpy().reshape(n, S) if b.h_lp is not None else None
-        nq = b.h_nq[:n * S].numpy().reshape(n, S) if b.h_nq is not None else None
-        bq = b.h_bq[:n * S].numpy().reshape(n, S) if b.h_bq is not None else None
-        pq = b.h_pq[:n * S].numpy().reshape(n, S) if b.h_pq is not None else None
-        fr = b.h_fr[:n * S].numpy().reshape(n, S, 2) if b.h_fr is not None else None
-        gm = b.h_gm[:n * S].numpy().reshape(n, S, 2) if b.h_gm is not None else None
-        lv = b.h_lv[:n * S].numpy().reshape(n, S) if b.h_lv is not None else None
+        rows = {s: b.h_scores[s][:n * S].numpy().reshape(n, S, s.width) for s in b.h_scores}
         for j in range(S):
             it = b.items[j]
             if not it:
                 continue
             tb, ds, k = tbs[j], dss[j], len(it)
-            scores = None
-            if pre:
-                scores = {}
-                if 'mse' in pre: scores['mse'] = sc[:k, j, 0].copy()
-                if 'ssim' in pre: scores['ssim'] = sc[:k, j, 1].copy()
-                if 'lpips' in pre and lp is not None: scores['lpips'] = lp[:k, j].copy()
-                if 'niqe' in pre and nq is not None: scores['niqe'] = nq[:k, j].copy()
-                if 'brisque' in pre and bq is not None: scores['brisque'] = bq[:k, j].copy()
-                if 'piqe' in pre and pq is not None: scores['piqe'] = pq[:k, j].copy()
-                if fr_psnr and fr is not None: scores['psnr'] = fr[:k, j, 0].copy()
-                if fr_ms and fr is not None: scores['ms_ssim'] = fr[:k, j, 1].copy()
-                if gm is not None: scores['gmsd'] = gm[:k, j, 0].copy()
-                if lv is not None: scores['lpips-vgg'] = lv[:k, j].copy()
+            scores = {name: rows[s][:k, j, s.columns[name]].copy() for s, _, names in scorers for name in names} if pre else None
             u8 = b.h_u8[:k, j] if b.h_u8 is not None else None      # (a strided view of the pinned buffer: the native writers copy it inside the call)
             if ds.has_images:
                 refs = b.refs[:k, j] if b.refs is not None else ds.frames(tb['frame_index'][it])[:, 0]
@@ -762,7 +706,7 @@ def evaluate(method_names, eval_config_names=None, dataset_names=None, metrics=N
         method_names = ['E2VID', 'E2VID+', 'FireNet', 'FireNet+', 'SPADE-E2VID', 'SSL-E2VID', 'ET-Net', 'HyperE2VID']
     eval_config_names = eval_config_names or ['std']
     dataset_names = dataset_names or ['ECD', 'MVSEC', 'HQF']
-    metrics = metrics or ['mse', 'ssim', 'lpips']
+    metrics = metrics or list(DEFAULT_METRICS)
     results = {}
     dataset_configs = get_dataset_configs(dataset_names)
     for eval_config in get_eval_configs(eval_config_names):

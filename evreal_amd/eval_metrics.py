@@ -7,23 +7,20 @@ Frames arrive in batches; gating (start/end time, |ref_ts-img_ts| <= ts_tol_ms, 
 
 Metric plug-ins keep the reference's contract (utils/eval_metrics.py:18-75): a `BaseMetric` subclass with `name`,
 `no_ref`, `calculate(img, ref) -> float | list`, `finish_queue()`, `reset()`.  Three kinds live side by side:
-  * 'mse', 'ssim' and -- when a weights file is available -- 'lpips' run batched on the GPU (evr_metrics / evr_lpips_*);
-  * 'niqe' and 'brisque' (no-reference) run batched on the GPU (evr_niqe_* / evr_brisque_*) when a model file is available,
-    and their scores are booked through the four-frame queue of the reference's pyiqa metrics, so their files hold the
-    same lines;
-  * 'psnr' and 'ms_ssim' (full-reference, closed form: no file needed) run batched on the GPU in fp64 (evr_fr_metrics) and are
-    booked through the same four-frame queue; EVREAL_GPU_FR_METRICS=0 sends the two names to pyiqa instead;
-  * 'piqe' (no-reference, training-free: no file needed) runs batched on the GPU in fp64 (evr_piqe_*) and is booked through
-    the same four-frame queue; EVREAL_GPU_PIQE=0 sends the name to pyiqa instead;
-  * 'gmsd' (full-reference, closed form: no file needed) runs batched on the GPU in fp64 (evr_gmsd) and is booked through the
-    same four-frame queue; EVREAL_GPU_GMSD=0 sends the name to pyiqa instead;
-  * 'lpips-vgg' (full-reference, the VGG-16 backbone of LPIPS) runs batched on the GPU (evr_lpips_vgg_*) when a weights file is
-    available, and is booked through the same four-frame queue;
+  * the GPU metrics of `_SCORERS` below run batched, one launch set per scorer: 'mse', 'ssim' and 'lpips' are booked frame by
+    frame; the others ('lpips-vgg', 'psnr', 'ms_ssim', 'gmsd', 'niqe', 'brisque', 'piqe') through the four-frame queue of the
+    reference's pyiqa metrics, so their files hold the same lines.  'lpips', 'lpips-vgg', 'niqe' and 'brisque' need a weights or
+    model file; 'psnr' / 'ms_ssim', 'piqe' and 'gmsd' need none and have a switch (EVREAL_GPU_FR_METRICS, EVREAL_GPU_PIQE,
+    EVREAL_GPU_GMSD: '0' sends the name to pyiqa instead);
   * anything registered with `register_metric(name, factory)` runs per frame on host arrays, exactly like the reference's
     MseMetric / SsimMetric (clipped float32 [H,W] images in, a float or a list of floats out);
   * any other name is looked up in pyiqa.list_models() when pyiqa is importable (queued in batches of 4 as
     PyIqaMetricFactory does, :100-156); without pyiqa it is reported as "Unknown metric", as the reference does for a
     name it does not know (:203).
+
+Adding a GPU metric: a Python wrapper around its kernels (batched frames in, float64 rows out on the device), ONE `_GpuScorer`
+entry in `_SCORERS` (names and columns, row width, no_ref, booking, handle, size limit, the call), and its tests.  The tracker and
+evaluate()'s chunk loop (evreal_amd/eval.py) are driven by that table and name no metric themselves.
 """
 import math
 import os
@@ -37,6 +34,7 @@ import torch
 from .lpips import LPIPSVGG
 from .prepost import GMSD, FullRefMetrics, Metrics, histogram_equalization
 
+DEFAULT_METRICS = ('mse', 'ssim', 'lpips')      # the reference's default (eval.py:413-445, utils/eval_metrics.py:171)
 GPU_METRICS = ('mse', 'ssim')
 FR_METRICS = ('psnr', 'ms_ssim')                # full-reference, closed form, queued like the reference's pyiqa metrics
 FR_METRICS_ENV = 'EVREAL_GPU_FR_METRICS'        # '0': psnr / ms_ssim go to pyiqa (or are unknown without it)
@@ -54,6 +52,8 @@ def _load_lpips():
     """The reference lets pyiqa download the LPIPS weights; offline they must be supplied as a file."""
     path = os.environ.get(LPIPS_WEIGHTS_ENV, os.path.join('pretrained', 'lpips_alex.pth'))
     if not os.path.exists(path):
+        print(f"lpips: no weights at ${LPIPS_WEIGHTS_ENV} or pretrained/lpips_alex.pth (pyiqa downloads them; "
+              "offline they must be provided) -> falling back to pyiqa if it is installed")
         return None
     from .lpips import LPIPS
     return LPIPS(torch.load(path, map_location='cpu', weights_only=False))
@@ -63,6 +63,8 @@ def _load_lpips_vgg():
     """As _load_lpips: made where pyiqa exists by torch.save(pyiqa.create_metric('lpips-vgg').net.state_dict(), path)."""
     path = os.environ.get(LPIPS_VGG_WEIGHTS_ENV, os.path.join('pretrained', 'lpips_vgg.pth'))
     if not os.path.exists(path):
+        print(f"lpips-vgg: no weights at ${LPIPS_VGG_WEIGHTS_ENV} or pretrained/lpips_vgg.pth (pyiqa downloads them; "
+              "offline they must be provided) -> falling back to pyiqa if it is installed")
         return None
     return LPIPSVGG(torch.load(path, map_location='cpu', weights_only=False))
 
@@ -123,6 +125,12 @@ def _load_brisque():
     model = load_brisque_model(*found)
     print(f"brisque: model {found[0]} ({model['source']})")
     return BRISQUE(model)
+
+
+def _load_piqe():
+    """PIQE has no model file: the object is its workspace."""
+    from .nriqa import PIQE
+    return PIQE()
 
 
 class BaseMetric:
@@ -300,12 +308,72 @@ def pyiqa_metric_factory():
     return _pyiqa_factory
 
 
+class _GpuScorer:
+    """One GPU launch set and everything the tracker and evaluate()'s chunk loop need to know about it:
+    columns: {metric name: column of the output row}; width: doubles per frame; no_ref: takes no reference frames;
+    queued: booked with QueuedGpuMetric (else GpuMetric); before_registry: resolved ahead of register_metric's names (else after
+    them); enabled(): the environment switch (None: available when the handle exists); handle(tracker): the callable, made at
+    the first request; too_small(name, H, W): why `name` is not defined on H x W frames, or None;
+    run(handle, img, ref, names, out): the rows of `img` [n,H,W] (and `ref`) into out [n,width], on the current stream -- `names`
+    are the wanted ones of `columns`; the other columns hold anything."""
+
+    def __init__(self, columns, width, handle, run, no_ref=False, queued=True, before_registry=False, enabled=None, too_small=None):
+        self.columns, self.width, self.handle, self.run = columns, width, handle, run
+        self.no_ref, self.queued, self.before_registry, self.enabled = no_ref, queued, before_registry, enabled
+        self.too_small = too_small or (lambda name, H, W: None)
+
+    def available(self, tracker):
+        return self.enabled() if self.enabled is not None else self.handle(tracker) is not None
+
+    def metric(self, name):
+        return (QueuedGpuMetric if self.queued else GpuMetric)(name, no_ref=self.no_ref)
+
+
+def _run_no_ref(h, img, ref, names, out):
+    h(img, clip=True, out=out[:, 0])
+
+
+# In the order evaluate()'s chunk loop launches them: the reference-needing ones, then the no-reference ones.
+_SCORERS = (
+    _GpuScorer({'mse': 0, 'ssim': 1}, 2, lambda t: t._gpu, queued=False, before_registry=True,
+               run=lambda h, img, ref, names, out: out.copy_(h(img, ref, mse='mse' in names, ssim='ssim' in names, clip=True))),
+    _GpuScorer({'lpips': 0}, 1, lambda t: t._lpips_model(), queued=False, before_registry=True,
+               run=lambda h, img, ref, names, out: out[:, 0].copy_(h(img, ref, clip=True))),
+    # one launch set for both; ms_ssim needs five scales of an 11x11 window
+    _GpuScorer({'psnr': 0, 'ms_ssim': 1}, 2, lambda t: t._fr, enabled=gpu_fr_metrics_enabled,
+               too_small=lambda name, H, W: FullRefMetrics.too_small(H, W) if name == 'ms_ssim' else None,
+               run=lambda h, img, ref, names, out: h(img, ref, psnr='psnr' in names, ms_ssim='ms_ssim' in names, clip=True, out=out)),
+    _GpuScorer({'gmsd': 0}, 2, lambda t: t._gmsd, enabled=gpu_gmsd_enabled,           # (column 1: the mean GMS)
+               too_small=lambda name, H, W: GMSD.too_small(H, W),
+               run=lambda h, img, ref, names, out: h(img, ref, clip=True, out=out)),
+    _GpuScorer({'lpips-vgg': 0}, 1, lambda t: t._cached('_lpips_vgg_cache'), before_registry=True,
+               too_small=lambda name, H, W: LPIPSVGG.too_small(H, W),
+               run=lambda h, img, ref, names, out: h(img, ref, clip=True, out=out[:, 0])),
+    _GpuScorer({'niqe': 0}, 1, lambda t: t._cached('_niqe_cache'), _run_no_ref, no_ref=True, before_registry=True),
+    _GpuScorer({'brisque': 0}, 1, lambda t: t._cached('_brisque_cache'), _run_no_ref, no_ref=True, before_registry=True),
+    _GpuScorer({'piqe': 0}, 1, lambda t: t._cached('_piqe_cache'), _run_no_ref, no_ref=True, enabled=gpu_piqe_enabled),
+)
+_SCORER_OF = {name: s for s in _SCORERS for name in s.columns}
+
+
+def chunk_scorers(tracker, names, H, W):
+    """-> [(scorer, handle, the names it serves)] for a frame loop that computes `names` (of wants_precomputed()) for whole chunks of
+    H x W frames itself.  A name that is not defined on frames of this size is left out (the tracker prints the exception and
+    resets the metric, as the reference does for a metric that raises); a scorer left without a name is left out altogether."""
+    found = []
+    for s in _SCORERS:
+        served = [name for name in s.columns if name in names and s.too_small(name, H, W) is None]
+        if served:
+            found.append((s, s.handle(tracker), served))
+    return found
+
+
 class EvalMetricsTracker:
     def __init__(self, save_images=False, save_processed_images=False, output_dir=None, hist_eq='none',
                  quan_eval_metric_names=None, quan_eval_start_time=0, quan_eval_end_time=float('inf'),
                  quan_eval_ts_tol_ms=float('inf'), has_reference_frames=False, color=False):
         if quan_eval_metric_names is None:
-            quan_eval_metric_names = ['mse', 'ssim', 'lpips']
+            quan_eval_metric_names = list(DEFAULT_METRICS)
         if hist_eq not in ('none', 'global', 'local', 'clahe'):
             raise ValueError(f"Unrecognized histogram equalization argument: {hist_eq}")
         self.save_images, self.output_dir, self.hist_eq = save_images, output_dir, hist_eq
@@ -318,88 +386,49 @@ class EvalMetricsTracker:
         self.start, self.end, self.tol_ms = quan_eval_start_time, quan_eval_end_time, quan_eval_ts_tol_ms
         self.has_reference_frames, self.color = has_reference_frames, color
         self.quan_eval_indices = []
-        self.metrics = []
-        for name in quan_eval_metric_names:
-            if name in GPU_METRICS:
-                self.metrics.append(GpuMetric(name))
-            elif name == 'lpips' and self._lpips_model() is not None:
-                self.metrics.append(GpuMetric(name))
-            elif name == 'lpips-vgg' and self._lpips_vgg_model() is not None:
-                self.metrics.append(QueuedGpuMetric(name, no_ref=False))
-            elif name == 'niqe' and self._niqe_model() is not None:
-                self.metrics.append(QueuedGpuMetric(name, no_ref=True))
-            elif name == 'brisque' and self._brisque_model() is not None:
-                self.metrics.append(QueuedGpuMetric(name, no_ref=True))
-            elif name in _REGISTRY:
-                self.metrics.append(_REGISTRY[name]())
-            elif name in FR_METRICS and gpu_fr_metrics_enabled():
-                self.metrics.append(QueuedGpuMetric(name, no_ref=False))
-            elif name == 'piqe' and gpu_piqe_enabled():
-                self.metrics.append(QueuedGpuMetric(name, no_ref=True))
-            elif name == 'gmsd' and gpu_gmsd_enabled():
-                self.metrics.append(QueuedGpuMetric(name, no_ref=False))
-            elif name in pyiqa_metric_factory().list_of_metrics:
-                self.metrics.append(pyiqa_metric_factory().get_metric(name))
-            else:
-                print("Unknown metric " + name)     # utils/eval_metrics.py:203
-        if not self.has_reference_frames:
-            self.metrics = [m for m in self.metrics if m.no_ref]
-        self.only_no_ref = all(m.no_ref for m in self.metrics)
         self._gpu = Metrics()
         self._fr = FullRefMetrics()
         self._gmsd = GMSD()
+        self.metrics = [m for m in map(self._resolve, quan_eval_metric_names) if m is not None]
+        if not self.has_reference_frames:
+            self.metrics = [m for m in self.metrics if m.no_ref]
+        self.only_no_ref = all(m.no_ref for m in self.metrics)
         self.reset()
 
+    def _resolve(self, name):
+        """-> the metric object of `name`: this project's GPU metric, a registered plug-in, pyiqa's -- in that order, with the
+        GPU metrics that have a switch after the plug-ins; None (and the reference's line, :203) for a name nobody knows."""
+        s = _SCORER_OF.get(name)
+        if s is not None and s.before_registry and s.available(self):
+            return s.metric(name)
+        if name in _REGISTRY:
+            return _REGISTRY[name]()
+        if s is not None and not s.before_registry and s.available(self):
+            return s.metric(name)
+        if name in pyiqa_metric_factory().list_of_metrics:
+            return pyiqa_metric_factory().get_metric(name)
+        print("Unknown metric " + name)
+        return None
+
+    # One handle per process and name: [loaded, handle or None], filled at the first request of the name (None without a weights
+    # or model file: the name then goes to its other providers).  Tests put stand-ins here, and in _lpips_model.
+    _LOADERS = {'_lpips_cache': _load_lpips, '_lpips_vgg_cache': _load_lpips_vgg, '_niqe_cache': _load_niqe,
+                '_brisque_cache': _load_brisque, '_piqe_cache': _load_piqe}
     _lpips_cache = [False, None]
+    _lpips_vgg_cache = [False, None]
+    _niqe_cache = [False, None]
+    _brisque_cache = [False, None]
+    _piqe_cache = [False, None]
+
+    @classmethod
+    def _cached(cls, cache):
+        if not getattr(cls, cache)[0]:
+            setattr(cls, cache, [True, cls._LOADERS[cache]()])
+        return getattr(cls, cache)[1]
 
     @classmethod
     def _lpips_model(cls):
-        if not cls._lpips_cache[0]:
-            cls._lpips_cache = [True, _load_lpips()]
-            if cls._lpips_cache[1] is None:
-                print(f"lpips: no weights at ${LPIPS_WEIGHTS_ENV} or pretrained/lpips_alex.pth (pyiqa downloads them; "
-                      "offline they must be provided) -> falling back to pyiqa if it is installed")
-        return cls._lpips_cache[1]
-
-    _lpips_vgg_cache = [False, None]
-
-    @classmethod
-    def _lpips_vgg_model(cls):
-        """One LPIPS-VGG handle per process; None without a weights file (then `lpips-vgg` goes to pyiqa, or is unknown)."""
-        if not cls._lpips_vgg_cache[0]:
-            cls._lpips_vgg_cache = [True, _load_lpips_vgg()]
-            if cls._lpips_vgg_cache[1] is None:
-                print(f"lpips-vgg: no weights at ${LPIPS_VGG_WEIGHTS_ENV} or pretrained/lpips_vgg.pth (pyiqa downloads them; "
-                      "offline they must be provided) -> falling back to pyiqa if it is installed")
-        return cls._lpips_vgg_cache[1]
-
-    _niqe_cache = [False, None]
-
-    @classmethod
-    def _niqe_model(cls):
-        """One NIQE model per process; None without a model file (then `niqe` goes to pyiqa, or is unknown)."""
-        if not cls._niqe_cache[0]:
-            cls._niqe_cache = [True, _load_niqe()]
-        return cls._niqe_cache[1]
-
-    _brisque_cache = [False, None]
-
-    @classmethod
-    def _brisque_model(cls):
-        """One BRISQUE model per process; None without a model file (then `brisque` goes to pyiqa, or is unknown)."""
-        if not cls._brisque_cache[0]:
-            cls._brisque_cache = [True, _load_brisque()]
-        return cls._brisque_cache[1]
-
-    _piqe_cache = [None]
-
-    @classmethod
-    def _piqe_model(cls):
-        """One PIQE object (its workspace) per process; there is no model file."""
-        if cls._piqe_cache[0] is None:
-            from .nriqa import PIQE
-            cls._piqe_cache[0] = PIQE()
-        return cls._piqe_cache[0]
+        return cls._cached('_lpips_cache')
 
     # -- files --------------------------------------------------------------------------------
     def reset(self):
@@ -465,9 +494,7 @@ class EvalMetricsTracker:
         file stays empty and its mean is -1.  Decided from the shape, before any launch, and printed once per sequence."""
         if m.name in self._failed:
             return True
-        H, W = int(imgs.shape[-2]), int(imgs.shape[-1])
-        why = (FullRefMetrics.too_small(H, W) if m.name == 'ms_ssim' else GMSD.too_small(H, W) if m.name == 'gmsd'
-               else LPIPSVGG.too_small(H, W) if m.name == 'lpips-vgg' else None)
+        why = _SCORER_OF[m.name].too_small(m.name, int(imgs.shape[-2]), int(imgs.shape[-1]))
         if why is None:
             return False
         print("Exception in metric " + m.get_name() + ": " + why)
@@ -520,26 +547,17 @@ class EvalMetricsTracker:
             isel = imgs[js].contiguous()
             rsel = refs[js].contiguous() if refs is not None else None
         if gpu:
-            want = {m.name for m in gpu}
-            scores = lp = nq = bq = pq = fr = gm = lv = None
-            if not have_pre:
-                if want & set(GPU_METRICS):
-                    scores = self._gpu(isel, rsel, mse='mse' in want, ssim='ssim' in want, clip=True).cpu().numpy()
-                lp = self._lpips_model()(isel, rsel, clip=True).cpu().numpy() if 'lpips' in want else None
-                nq = self._niqe_model()(isel, clip=True).cpu().numpy() if 'niqe' in want else None
-                bq = self._brisque_model()(isel, clip=True).cpu().numpy() if 'brisque' in want else None
-                pq = self._piqe_model()(isel, clip=True).cpu().numpy() if 'piqe' in want else None
-                if want & set(FR_METRICS):
-                    fr = self._fr(isel, rsel, psnr='psnr' in want, ms_ssim='ms_ssim' in want, clip=True).cpu().numpy()
-                gm = self._gmsd(isel, rsel, clip=True).cpu().numpy() if 'gmsd' in want else None
-                lv = self._lpips_vgg_model()(isel, rsel, clip=True).cpu().numpy() if 'lpips-vgg' in want else None
+            if have_pre:
+                cols = {m.name: np.asarray(pre[m.name])[sel] for m in gpu}
+            else:
+                cols = {}
+                for s, handle, names in chunk_scorers(self, [m.name for m in gpu], int(imgs.shape[-2]), int(imgs.shape[-1])):
+                    rows = torch.empty((len(sel), s.width), dtype=torch.float64, device=isel.device)
+                    s.run(handle, isel, rsel, names, rows)
+                    rows = rows.cpu().numpy()
+                    cols.update((name, rows[:, s.columns[name]]) for name in names)
             for m in gpu:
-                if have_pre:
-                    col = np.asarray(pre[m.name])[sel]
-                else:
-                    col = (scores[:, 0] if m.name == 'mse' else scores[:, 1] if m.name == 'ssim' else nq if m.name == 'niqe'
-                           else bq if m.name == 'brisque' else pq if m.name == 'piqe' else fr[:, 0] if m.name == 'psnr'
-                           else fr[:, 1] if m.name == 'ms_ssim' else gm if m.name == 'gmsd' else lv if m.name == 'lpips-vgg' else lp)
+                col = cols[m.name]
                 if isinstance(m, QueuedGpuMetric):
                     self._append(join(self.output_dir, m.name + '.txt'), m.book(self.quan_eval_indices, idxs, col))
                     continue
