@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <vector>
 #include "evreal_hip.h"
 
 namespace evr {
@@ -24,6 +25,15 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
         }                                       \
     } while (0)
 #define EVR_LAUNCH_CHECK() EVR_HIP(hipGetLastError())
+
+namespace evr {
+// a host vector into a device allocation of its own (weights, biases, tables: made once per handle)
+inline int upload(const std::vector<float>& h, float** d) {
+    EVR_HIP(hipMalloc((void**)d, h.size() * sizeof(float) + 64));
+    EVR_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return EVR_OK;
+}
+}  // namespace evr
 
 // wave64 helpers
 __device__ __forceinline__ int evr_lane() { return threadIdx.x & 63; }

@@ -411,6 +411,20 @@ inline int packed_fmt(int mode) { return mode == 3 ? 2 : (mode == 2 ? 1 : (mode 
 inline int pack_weights_for(int mode, std::vector<float>& w) { return mode == 3 ? pack_h2_weights(w) : (mode == 4 ? pack_p6_weights(w) : pack_split_weights(w)); }
 // (A/B switch for the whole-group PACKED stores)
 inline int use_group_store() { const char* e = getenv("EVR_GROUP_STORE"); return e ? atoi(e) : 1; }
+// ---- what the kernels of conv.hip expect of a convolution prepared for `mode` whose weights went through pack_weights_for
+// (tensor exponent e_w): every host that prepares one -- model.cpp, the LPIPS backbones -- takes it from here.
+// Mode 3 accumulates products scaled by 2^(e_w + H2_ACT_EXP), mode 4 by 2^e_w (weights scaled, activations unscaled): the
+// accumulators start at the bias in that scale (exact: a power of two) and the epilogue multiplies by ConvArgs::acc_scale.
+inline int acc_exp(int mode, int e_w) { return mode == 3 ? e_w + H2_ACT_EXP : (mode == 4 ? e_w : 0); }
+inline void prescale_bias(int mode, int e_w, std::vector<float>& bias) {
+    if (const int e = acc_exp(mode, e_w)) for (float& b : bias) b = __builtin_ldexpf(b, e);
+}
+// the mode-derived fields of a ConvArgs whose hm / wm are set
+inline void set_mode_fields(ConvArgs& a, int x3, int e_w) {
+    a.x3 = x3;
+    a.acc_scale = __builtin_ldexpf(1.0f, -acc_exp(x3, e_w));
+    a.mx_sa = 127 - MX_LO_EXP; a.mx_sb = 127 - e_w; a.group_store = use_group_store(); set_fastdiv(a);
+}
 
 // kc: K chunk (16 or 32 channels); wm: waves per block along M (1,2,4); nb: 32-column blocks per wave (1,2,4).
 // `a` is the host copy (grid sizing, validation); `d_args` the same plan resident in device memory (the

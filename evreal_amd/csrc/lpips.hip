@@ -20,6 +20,7 @@
 
 #include <atomic>
 #include "conv.h"
+#include "lpips_host.h"
 #include "packed.h"
 
 using namespace evr;
@@ -308,9 +309,6 @@ __global__ __launch_bounds__(64) void lpips_final_kernel(const double* __restric
 constexpr int SCORE_BLOCKS_MAX = 256;
 static int score_blocks(int n) { int b = 2048 / (n > 0 ? n : 1); return b < 32 ? 32 : (b > SCORE_BLOCKS_MAX ? SCORE_BLOCKS_MAX : b); }
 
-struct Layer { int cin, cout, k, pad; int x3 = 0; int mx_e = 0; std::vector<float> w, b; float* d_w = nullptr; float* d_b = nullptr; float* d_lin = nullptr;
-               float* d_wino = nullptr; };      // (exact-fp32 mode, 3x3 layers: Winograd-domain weights, wino.hip)
-
 }  // namespace
 
 struct evr_lpips {
@@ -319,60 +317,32 @@ struct evr_lpips {
     float* d_wg = nullptr; float* d_wb = nullptr; float* d_b1 = nullptr; float* d_b1in = nullptr;
     float* d_wfrag1 = nullptr; float* d_wbsum = nullptr;     // matrix-core form of conv1 (split mode)
     float* d_lin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    Layer L[4];
+    BackboneConv L[4];
     // shape-dependent.  Buffers are sized for `cap` image pairs at H x W and only ever grow; what depends on the pair count n of a call
-    // (the four ConvArgs with their tile choice) lives in a small cache of plans.  Round 6: the drop-in's chunks change n at every
-    // sequence boundary (a short last chunk, then a full one), and the old one-plan form answered each change with a stream
-    // synchronise + hipFree + hipMalloc of everything -- 16 device-wide stalls in an eight-sequence run.
+    // (the four ConvArgs with their tile choice) lives in the plan cache (lpips_host.h).
     int n = 0, H = 0, W = 0, cap = 0;
     int h[5], w[5];              // feature map sizes of relu1..relu5
-    std::vector<void*> allocs;
+    DeviceAllocs allocs;
     float* feat[5] = {}; float* pool1 = nullptr; float* pool2 = nullptr;
-    struct Plan { int n = 0; unsigned stamp = 0; ConvArgs args[4]; int wm[4], nb[4]; };
-    static constexpr int NPLANS = 8;
-    Plan plans[NPLANS]; unsigned clock = 0; Plan* cur = nullptr;
-    ConvArgs* d_args = nullptr;      // [NPLANS][4]
-    float* kws = nullptr; bool kws_tried = false;
+    PlanCache<4> plans;
+    SplitWorkspace kws;
     double* partials = nullptr; int* d_hw = nullptr;
     void release() {
-        for (void* p : allocs) (void)hipFree(p);
-        allocs.clear(); n = 0; cap = 0; d_args = nullptr; cur = nullptr; kws = nullptr; kws_tried = false;
-        for (auto& pl : plans) pl.n = 0;
+        allocs.release();
+        n = 0; cap = 0; plans.clear(); kws = SplitWorkspace();
     }
     ~evr_lpips() {
         release();
         if (d_wg) (void)hipFree(d_wg); if (d_wb) (void)hipFree(d_wb); if (d_b1) (void)hipFree(d_b1); if (d_b1in) (void)hipFree(d_b1in);
         if (d_wfrag1) (void)hipFree(d_wfrag1); if (d_wbsum) (void)hipFree(d_wbsum);
         for (auto& p : d_lin) if (p) (void)hipFree(p);
-        for (auto& l : L) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_wino) (void)hipFree(l.d_wino); }
+        for (auto& l : L) free_backbone_conv(l);
     }
 };
 
-namespace {
-int up(const std::vector<float>& h, float** d) {
-    EVR_HIP(hipMalloc((void**)d, h.size() * sizeof(float) + 64));
-    EVR_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return EVR_OK;
-}
-template <typename T>
-int dalloc(evr_lpips* m, T** p, size_t count) {
-    EVR_HIP(hipMalloc((void**)p, count * sizeof(T) + 256));
-    m->allocs.push_back((void*)*p);
-    return EVR_OK;
-}
-}  // namespace
-
 extern "C" int evr_lpips_create(const evr_tensor* tensors, int n_tensors, evr_lpips** out) {
     EVR_REQUIRE(tensors && out, "evr_lpips_create: null argument");
-    std::map<std::string, const evr_tensor*> sd;
-    for (int i = 0; i < n_tensors; ++i) if (tensors[i].name) sd[tensors[i].name] = &tensors[i];
-    auto get = [&](const std::string& k, int64_t numel, const evr_tensor** t) -> int {
-        auto it = sd.find(k);
-        if (it == sd.end()) { set_error("LPIPS state_dict is missing '%s'", k.c_str()); return EVR_ERR_MISSING_TENSOR; }
-        int64_t ne = 1; for (int d = 0; d < it->second->ndim; ++d) ne *= it->second->shape[d];
-        if (ne != numel) { set_error("LPIPS tensor '%s' has %lld elements, expected %lld", k.c_str(), (long long)ne, (long long)numel); return EVR_ERR_INVALID; }
-        *t = it->second; return EVR_OK;
-    };
+    const StateDict sd("LPIPS", tensors, n_tensors);
     evr_lpips* m = new evr_lpips();
     int rc = EVR_OK;
     const evr_tensor *w, *b;
@@ -380,30 +350,13 @@ extern "C" int evr_lpips_create(const evr_tensor* tensors, int n_tensors, evr_lp
     const char* names[5] = {"net.slice1.0", "net.slice2.3", "net.slice3.6", "net.slice4.8", "net.slice5.10"};
     const int cin[5] = {3, 64, 192, 384, 256}, cout[5] = {64, 192, 384, 256, 256}, ks[5] = {11, 5, 3, 3, 3};
     do {
-        if ((rc = get(std::string(names[0]) + ".weight", 64 * 3 * 121, &w))) break;
-        if ((rc = get(std::string(names[0]) + ".bias", 64, &b))) break;
-        m->wg.assign((size_t)121 * 64, 0.f); m->wb.assign((size_t)121 * 64, 0.f);
-        m->b1.assign(b->data_host, b->data_host + 64); m->b1in.assign(64, 0.f);
-        {   // scaling layer of LPIPS folded into conv1: x_c = alpha_c * g + beta_c
-            const double shift[3] = {-.030, -.088, -.188}, scale[3] = {.458, .448, .450};
-            for (int co = 0; co < 64; ++co) {
-                double bsum = 0.0;
-                for (int t = 0; t < 121; ++t) {
-                    double g = 0.0, bb = 0.0;
-                    for (int c = 0; c < 3; ++c) {
-                        const double wv = w->data_host[((size_t)co * 3 + c) * 121 + t];
-                        g += wv * (2.0 / scale[c]); bb += wv * ((-1.0 - shift[c]) / scale[c]);
-                    }
-                    m->wg[(size_t)t * 64 + co] = (float)g; m->wb[(size_t)t * 64 + co] = (float)bb;
-                    bsum += bb;
-                }
-                m->b1in[co] = (float)((double)m->b1[co] + bsum);
-            }
-        }
-        if ((rc = up(m->wg, &m->d_wg))) break;
-        if ((rc = up(m->wb, &m->d_wb))) break;
-        if ((rc = up(m->b1, &m->d_b1))) break;
-        if ((rc = up(m->b1in, &m->d_b1in))) break;
+        if ((rc = sd.get(std::string(names[0]) + ".weight", 64 * 3 * 121, &w))) break;
+        if ((rc = sd.get(std::string(names[0]) + ".bias", 64, &b))) break;
+        fold_scaling_layer(w->data_host, b->data_host, 64, 121, m->wg, m->wb, m->b1, m->b1in);
+        if ((rc = upload(m->wg, &m->d_wg))) break;
+        if ((rc = upload(m->wb, &m->d_wb))) break;
+        if ((rc = upload(m->b1, &m->d_b1))) break;
+        if ((rc = upload(m->b1in, &m->d_b1in))) break;
         if (use_split_mode()) {
             // weight fragments of lpips_conv1_mfma_kernel: [slab s][block nb][hi, lo][lane] x 4 dwords, lane (r, h) holding the
             // 8 taps k = 16s + 8h + j of output channel nb*32 + r as bf16 pairs (taps >= 121: zero)
@@ -430,36 +383,16 @@ extern "C" int evr_lpips_create(const evr_tensor* tensors, int n_tensors, evr_lp
                     Pd[i][j] = Pd[i - 1][j] + Pd[i][j - 1] - Pd[i - 1][j - 1] + (double)m->wb[(size_t)((i - 1) * 11 + (j - 1)) * 64 + co];
                 for (int i = 0; i < 12; ++i) for (int j = 0; j < 12; ++j) m->wbsum[(size_t)(i * 12 + j) * 64 + co] = (float)Pd[i][j];
             }
-            if ((rc = up(m->wfrag1, &m->d_wfrag1))) break;
-            if ((rc = up(m->wbsum, &m->d_wbsum))) break;
+            if ((rc = upload(m->wfrag1, &m->d_wfrag1))) break;
+            if ((rc = upload(m->wbsum, &m->d_wbsum))) break;
         }
-        for (int l = 1; l < 5 && !rc; ++l) {
-            Layer& L = m->L[l - 1];
-            L.cin = cin[l]; L.cout = cout[l]; L.k = ks[l]; L.pad = ks[l] / 2;
-            const int taps = L.k * L.k;
-            if ((rc = get(std::string(names[l]) + ".weight", (int64_t)cout[l] * cin[l] * taps, &w))) break;
-            if ((rc = get(std::string(names[l]) + ".bias", cout[l], &b))) break;
-            L.w.assign((size_t)cout[l] * taps * cin[l], 0.f); L.b.assign(b->data_host, b->data_host + cout[l]);
-            for (int co = 0; co < cout[l]; ++co) for (int ci = 0; ci < cin[l]; ++ci) for (int t = 0; t < taps; ++t)
-                L.w[((size_t)co * taps + t) * cin[l] + ci] = w->data_host[((size_t)co * cin[l] + ci) * taps + t];
-            L.x3 = arith_mode();          // conv2..conv5 run on the same implicit-GEMM family as the networks, in their mode
-            if (L.x3 == 4) L.x3 = 2;      // (P6 tensors have no 4-channel writer -- the max pools, conv1's epilogue: LPIPS keeps the fp8 form)
-            // exact-fp32 mode: conv3..conv5 (3x3 stride 1) also get their Winograd-domain weights (model.cpp finish_conv; EVR_WINO=0: never)
-            if (L.x3 == 0 && L.k == 3 && wino_enabled() && L.cin % 16 == 0 && L.cout % 64 == 0) {
-                std::vector<float> u;
-                wino_pack_weights(L.w, L.cout, L.cin, 0, u);
-                if ((rc = up(u, &L.d_wino))) break;
-            }
-            if (L.x3) L.mx_e = pack_weights_for(L.x3, L.w);
-            if (L.x3 == 3) for (float& bv : L.b) bv = std::ldexp(bv, L.mx_e + H2_ACT_EXP);      // (model.cpp finish_conv)
-            if ((rc = up(L.w, &L.d_w))) break;
-            if ((rc = up(L.b, &L.d_b))) break;
-        }
+        // conv2..conv5 run on the same implicit-GEMM family as the networks, in their mode
+        for (int l = 1; l < 5 && !rc; ++l) rc = prepare_backbone_conv(sd, names[l], cin[l], cout[l], ks[l], backbone_mode(), &m->L[l - 1]);
         if (rc) break;
         for (int l = 0; l < 5 && !rc; ++l) {
-            if ((rc = get("lin" + std::to_string(l) + ".model.1.weight", cout[l], &w))) break;
+            if ((rc = sd.get("lin" + std::to_string(l) + ".model.1.weight", cout[l], &w))) break;
             std::vector<float> lw(w->data_host, w->data_host + cout[l]);
-            rc = up(lw, &m->d_lin[l]);
+            rc = upload(lw, &m->d_lin[l]);
         }
     } while (0);
     if (rc) { delete m; return rc; }
@@ -484,43 +417,23 @@ static int lpips_buffers(evr_lpips* m, int cap, int H, int W, hipStream_t stream
     EVR_REQUIRE(hp2 >= 1 && wp2 >= 1, "evr_lpips: image %dx%d too small for AlexNet", W, H);
     const int C[5] = {64, 192, 384, 256, 256};
     int rc;
-    for (int l = 0; l < 5; ++l) if ((rc = dalloc(m, &m->feat[l], (size_t)n2 * m->h[l] * m->w[l] * C[l]))) return rc;
-    if ((rc = dalloc(m, &m->pool1, (size_t)n2 * hp1 * wp1 * 64))) return rc;
-    if ((rc = dalloc(m, &m->pool2, (size_t)n2 * hp2 * wp2 * 192))) return rc;
-    if ((rc = dalloc(m, &m->partials, (size_t)5 * cap * SCORE_BLOCKS_MAX))) return rc;
-    if ((rc = dalloc(m, &m->d_hw, 8))) return rc;
-    if ((rc = dalloc(m, &m->d_args, (size_t)evr_lpips::NPLANS * 4))) return rc;
+    for (int l = 0; l < 5; ++l) if ((rc = m->allocs.alloc(&m->feat[l], (size_t)n2 * m->h[l] * m->w[l] * C[l]))) return rc;
+    if ((rc = m->allocs.alloc(&m->pool1, (size_t)n2 * hp1 * wp1 * 64))) return rc;
+    if ((rc = m->allocs.alloc(&m->pool2, (size_t)n2 * hp2 * wp2 * 192))) return rc;
+    if ((rc = m->allocs.alloc(&m->partials, (size_t)5 * cap * SCORE_BLOCKS_MAX))) return rc;
+    if ((rc = m->allocs.alloc(&m->d_hw, 8))) return rc;
+    if ((rc = m->allocs.alloc(&m->plans.d_args, (size_t)m->plans.NPLANS * 4))) return rc;
     int hw[5]; for (int l = 0; l < 5; ++l) hw[l] = m->h[l] * m->w[l];
     EVR_HIP(hipMemcpy(m->d_hw, hw, sizeof(hw), hipMemcpyHostToDevice));
     return EVR_OK;
 }
 
-// the plan of n image pairs inside the current buffers: cached, or built into the least recently used slot (its ConvArgs go to the
-// device in stream order, behind whatever launch still reads the slot's previous contents)
-static int lpips_plan(evr_lpips* m, int n, hipStream_t stream) {
-    evr_lpips::Plan* pl = nullptr;
-    for (auto& c : m->plans) if (c.n == n) pl = &c;
-    if (pl) { pl->stamp = ++m->clock; m->cur = pl; m->n = n; return EVR_OK; }
-    for (auto& c : m->plans) {
-        if (c.n == 0) { pl = &c; break; }
-        if (!pl || c.stamp < pl->stamp) pl = &c;
-    }
-    pl->n = 0;
-    const int n2 = 2 * n;
-    const int hp1 = m->h[1], wp1 = m->w[1], hp2 = m->h[2], wp2 = m->w[2];
+// the plan of n image pairs inside the current buffers (PlanCache::get fills a slot with this)
+static void lpips_fill_plan(evr_lpips* m, PlanCache<4>::Plan& pl, int n) {
     const float* ins[4] = {m->pool1, m->pool2, m->feat[2], m->feat[3]};
-    const int hin[4] = {hp1, hp2, hp2, hp2}, win[4] = {wp1, wp2, wp2, wp2};
     for (int i = 0; i < 4; ++i) {
-        Layer& L = m->L[i];
-        ConvArgs& a = pl->args[i];
-        memset(&a, 0, sizeof(a));
-        a.in0 = ins[i]; a.c0 = L.cin; a.in_mode = IN_SINGLE; a.n = n2; a.hin = hin[i]; a.win = win[i];
-        a.hm = hin[i]; a.wm = win[i]; a.stride = 1; a.os = 1; a.hout = hin[i]; a.wout = win[i];
-        a.tp.ntaps = L.k * L.k; a.tp.ngroups = 1; a.tp.grp_cols = L.cout;
-        for (int ky = 0; ky < L.k; ++ky) for (int kx = 0; kx < L.k; ++kx) a.tp.set_tap(ky * L.k + kx, ky - L.pad, kx - L.pad, 1);
-        a.wgt = L.d_w; a.bias = L.d_b; a.cout = L.cout; a.n_valid = L.cout; a.out = m->feat[i + 1]; a.cout_total = L.cout;
-        a.epi = EPI_BIAS_RELU; a.x3 = L.x3;
-        a.wgt_wino = L.d_wino; set_wino_grid(a);
+        ConvArgs& a = pl.args[i];
+        fill_backbone_conv(a, m->L[i], ins[i], m->feat[i + 1], 2 * n, m->h[i + 1], m->w[i + 1]);      // (pool1 / pool2 / feat1..feat4)
         {   // conv2 (5x5) on the band kernel with 8 KB of LDS padding (two blocks per CU instead of three); EVR_LPIPS_BAND5=<KB> sets the
             // padding, EVR_LPIPS_BAND5=-1 keeps the implicit GEMM (the default until the evaluation stream moved behind the residual
             // blocks: beside the ConvLSTM layers its LDS footprint cost more than the kernel gained; now +0.7 .. 1.0 %, profiles/r03_env_ab.txt)
@@ -528,27 +441,9 @@ static int lpips_plan(evr_lpips* m, int n, hipStream_t stream) {
             const int kb = e ? atoi(e) : 8;
             a.no_band5 = kb < 0 ? 1 : 0; a.band_lds_pad = kb < 0 ? 0 : kb * 1024;
         }
-        a.acc_scale = (L.x3 == 3) ? std::ldexp(1.0f, -(L.mx_e + H2_ACT_EXP)) : 1.0f;
-        a.in_packed = a.out_packed = L.x3 ? 1 : 0;      // pool1 / pool2 / feat1..feat4 are PACKED (H2 in mode 3) in the split modes
-        a.mx_sa = 127 - MX_LO_EXP; a.mx_sb = 127 - L.mx_e; a.group_store = use_group_store(); set_fastdiv(a);
-        pick_conv_tile(a, 32, &pl->wm[i], &pl->nb[i]);
+        pick_conv_tile(a, 32, &pl.wm[i], &pl.nb[i]);
     }
-    {   // split-K partial sums of conv3..conv5 at small batches (conv.h KSPLIT_WS_BYTES): this handle's own -- it runs on the evaluation
-        // stream beside a model's launches
-        // (only when a conv of this plan can split -- a split arithmetic and <= 192 tiles of 128 pixels -- and a failed allocation
-        // degrades to "never split" instead of failing the plan: ADVICE r5)
-        bool may_split = false;
-        for (int i = 1; i < 4; ++i) if (pl->args[i].x3 && (int64_t)n2 * pl->args[i].hm * pl->args[i].wm <= 192LL * 128) may_split = true;
-        if (may_split && !m->kws && !m->kws_tried) {
-            m->kws_tried = true;
-            if (hipMalloc((void**)&m->kws, KSPLIT_WS_BYTES) != hipSuccess) { (void)hipGetLastError(); m->kws = nullptr; }
-            else m->allocs.push_back((void*)m->kws);
-        }
-        for (int i = 0; i < 4; ++i) pl->args[i].ksplit_ws = may_split ? m->kws : nullptr;
-    }
-    EVR_HIP(hipMemcpyAsync(m->d_args + 4 * (pl - m->plans), pl->args, 4 * sizeof(ConvArgs), hipMemcpyHostToDevice, stream));
-    pl->n = n; pl->stamp = ++m->clock; m->cur = pl; m->n = n;
-    return EVR_OK;
+    attach_split_workspace(m->kws, m->allocs, pl.args, 4, 1);      // (conv3..conv5 are the ones that may split)
 }
 
 extern "C" int evr_lpips_forward(evr_lpips* m, const float* img, const float* ref, int n, int H, int W, int clip, double* out,
@@ -557,9 +452,11 @@ extern "C" int evr_lpips_forward(evr_lpips* m, const float* img, const float* re
     EVR_REQUIRE(m && img && ref && out && n >= 1 && H >= 1 && W >= 1, "evr_lpips_forward: bad argument");
     int rc;
     if (m->H != H || m->W != W || n > m->cap) if ((rc = lpips_buffers(m, n, H, W, stream))) { m->release(); m->H = m->W = 0; return rc; }      // (a half-built set of buffers must not look like capacity)
-    if (!m->cur || m->cur->n != n) if ((rc = lpips_plan(m, n, stream))) return rc;
-    const evr_lpips::Plan& P = *m->cur;
-    ConvArgs* const d_args = m->d_args + 4 * (m->cur - m->plans);
+    PlanCache<4>::Plan* plan = nullptr;
+    if ((rc = m->plans.get(n, stream, [m](PlanCache<4>::Plan& pl, int np) { lpips_fill_plan(m, pl, np); }, &plan))) return rc;
+    m->n = n;
+    const PlanCache<4>::Plan& P = *plan;
+    ConvArgs* const d_args = m->plans.device_args(plan);
     const int n2 = 2 * n;
     Conv1Args c1{};
     c1.img = img; c1.ref = ref; c1.n = n; c1.H = H; c1.W = W; c1.h1 = m->h[0]; c1.w1 = m->w[0]; c1.clip = clip;

@@ -4,7 +4,7 @@
 // PARITY UNPINNED: pyiqa and torchvision are neither in the reference tree nor installed, and the VGG + linear-head weights are
 // downloaded at run time (unobtainable offline).  The arithmetic below follows the published algorithm (Zhang et al. 2018;
 // richzhang/PerceptualSimilarity v0.1 with net='vgg', as wrapped by pyiqa): x <- 2g-1; (x-shift)/scale per channel (the constants
-// of lpips.hip); torchvision vgg16.features with taps after relu1_2, relu2_2, relu3_3, relu4_3, relu5_3; MaxPool2d(2, 2) in floor
+// of lpips_host.h); torchvision vgg16.features with taps after relu1_2, relu2_2, relu3_3, relu4_3, relu5_3; MaxPool2d(2, 2) in floor
 // mode as the first operation of slices 2-5; unit-normalise every pixel's feature vector, f/(|f| + 1e-10); squared difference;
 // non-negative 1x1 "lin" weights; spatial mean; sum over the five layers.  Conventions that stay unpinned until
 // tests/test_lpips_vgg_pins.py has run where pyiqa exists -- recalled from the published code, not read from it: the state-dict
@@ -13,7 +13,7 @@
 // Scores agree with the restatement tests/lpips_vgg_ref.py on any weights, and with pyiqa only once its weights are supplied.
 //
 // Layers: conv1_1 (3->64) is a direct VALU kernel on the gray input (the three input channels are affine in the same gray value);
-// the other twelve 3x3 convolutions run on the convolution kernels of conv.hip exactly as lpips.hip drives its conv3..conv5 (split
+// the other twelve 3x3 convolutions run on the convolution kernels of conv.hip through the set-up both backbones share (lpips_host.h; split
 // arithmetic: every activation tensor is PACKED / H2; fp32 mode: PLAIN, Winograd where eligible); one streaming kernel per tap
 // layer scores it and writes the 2x2 max pool of both images' features -- the 64-channel full-resolution tensor is read once.
 //
@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "conv.h"
+#include "lpips_host.h"
 #include "packed.h"
 
 using namespace evr;
@@ -280,8 +281,6 @@ int score_blocks(int n, int nwin, int C) {
     return want < 1 ? 1 : want;
 }
 
-struct Layer { int cin, cout; int x3 = 0; int mx_e = 0; std::vector<float> w, b; float* d_w = nullptr; float* d_b = nullptr; float* d_wino = nullptr; };
-
 }  // namespace
 
 struct evr_lpips_vgg {
@@ -289,47 +288,32 @@ struct evr_lpips_vgg {
     float* d_wg = nullptr; float* d_wb = nullptr; float* d_b1 = nullptr; float* d_b1in = nullptr;
     float* d_lin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     unsigned* d_sat = nullptr;       // range guard of the packed formats (packed.h sat_note): every producer of this handle counts here
-    Layer L[NCONV];
-    int mode = 0;                    // arithmetic of the twelve convolutions (arith_mode(), mode 4 as mode 2)
+    BackboneConv L[NCONV];
+    int mode = 0;                    // arithmetic of the twelve convolutions (lpips_host.h backbone_mode)
     int max_pairs = 0;               // constructor argument: pairs per pass (0: from ACT_BUDGET_BYTES)
     // shape-dependent.  Buffers are sized for `cap` pairs per pass at H x W and only ever grow; what depends on the pair count of
-    // a pass (the twelve ConvArgs with their tile choice) lives in a small cache of plans, as in lpips.hip.
+    // a pass (the twelve ConvArgs with their tile choice) lives in the plan cache (lpips_host.h).
     int n = 0, H = 0, W = 0, cap = 0;      // n: pairs of the last call (evr_lpips_vgg_flops)
     int h[5], w[5];                  // feature map sizes of the five levels
-    std::vector<void*> allocs;
+    DeviceAllocs allocs;
     float* act[2] = {nullptr, nullptr};
-    struct Plan { int n = 0; unsigned stamp = 0; ConvArgs args[NCONV]; int wm[NCONV], nb[NCONV]; };
-    static constexpr int NPLANS = 8;
-    Plan plans[NPLANS]; unsigned clock = 0;
-    ConvArgs* d_args = nullptr;      // [NPLANS][NCONV]
-    float* kws = nullptr; bool kws_tried = false;
+    PlanCache<NCONV> plans;
+    SplitWorkspace kws;
     double* partials = nullptr;      // [5][cap][SCORE_BLOCKS_MAX]
     void release() {
-        for (void* p : allocs) (void)hipFree(p);
-        allocs.clear(); cap = 0; d_args = nullptr; kws = nullptr; kws_tried = false; act[0] = act[1] = nullptr; partials = nullptr;
-        for (auto& pl : plans) pl.n = 0;
+        allocs.release();
+        cap = 0; plans.clear(); kws = SplitWorkspace(); act[0] = act[1] = nullptr; partials = nullptr;
     }
     ~evr_lpips_vgg() {
         release();
         if (d_wg) (void)hipFree(d_wg); if (d_wb) (void)hipFree(d_wb); if (d_b1) (void)hipFree(d_b1); if (d_b1in) (void)hipFree(d_b1in);
         if (d_sat) (void)hipFree(d_sat);
         for (auto& p : d_lin) if (p) (void)hipFree(p);
-        for (auto& l : L) { if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_wino) (void)hipFree(l.d_wino); }
+        for (auto& l : L) free_backbone_conv(l);
     }
 };
 
 namespace {
-int up(const std::vector<float>& h, float** d) {
-    EVR_HIP(hipMalloc((void**)d, h.size() * sizeof(float) + 64));
-    EVR_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return EVR_OK;
-}
-template <typename T>
-int dalloc(evr_lpips_vgg* m, T** p, size_t count) {
-    EVR_HIP(hipMalloc((void**)p, count * sizeof(T) + 256));
-    m->allocs.push_back((void*)*p);
-    return EVR_OK;
-}
 // pairs per pass at H x W
 int pass_pairs(const evr_lpips_vgg* m, int H, int W) {
     const int64_t per_pair = (int64_t)2 * H * W * 64 * 4;      // one buffer, one pair
@@ -341,75 +325,29 @@ int pass_pairs(const evr_lpips_vgg* m, int H, int W) {
 
 extern "C" int evr_lpips_vgg_create(const evr_tensor* tensors, int n_tensors, int max_pairs, evr_lpips_vgg** out) {
     EVR_REQUIRE(tensors && out && max_pairs >= 0, "evr_lpips_vgg_create: bad argument");
-    std::map<std::string, const evr_tensor*> sd;
-    for (int i = 0; i < n_tensors; ++i) if (tensors[i].name) sd[tensors[i].name] = &tensors[i];
-    auto get = [&](const std::string& k, int64_t numel, const evr_tensor** t) -> int {
-        auto it = sd.find(k);
-        if (it == sd.end()) { set_error("LPIPS-VGG state_dict is missing '%s'", k.c_str()); return EVR_ERR_MISSING_TENSOR; }
-        int64_t ne = 1; for (int d = 0; d < it->second->ndim; ++d) ne *= it->second->shape[d];
-        if (ne != numel) { set_error("LPIPS-VGG tensor '%s' has %lld elements, expected %lld", k.c_str(), (long long)ne, (long long)numel); return EVR_ERR_INVALID; }
-        *t = it->second; return EVR_OK;
-    };
+    const StateDict sd("LPIPS-VGG", tensors, n_tensors);
     evr_lpips_vgg* m = new evr_lpips_vgg();
     m->max_pairs = max_pairs;
-    m->mode = arith_mode();
-    if (m->mode == 4) m->mode = 2;      // (P6 tensors have no 4-channel writer -- the pools: as lpips.hip, the fp8 form)
+    m->mode = backbone_mode();
     int rc = EVR_OK;
     const evr_tensor *w, *b;
     // torchvision vgg16.features indices inside pyiqa's slices (conv1_1 first)
     const char* names[NCONV + 1] = {"net.slice1.0", "net.slice1.2", "net.slice2.5", "net.slice2.7", "net.slice3.10", "net.slice3.12", "net.slice3.14",
                                     "net.slice4.17", "net.slice4.19", "net.slice4.21", "net.slice5.24", "net.slice5.26", "net.slice5.28"};
     do {
-        if ((rc = get(std::string(names[0]) + ".weight", 64 * 3 * 9, &w))) break;
-        if ((rc = get(std::string(names[0]) + ".bias", 64, &b))) break;
-        m->wg.assign((size_t)9 * 64, 0.f); m->wb.assign((size_t)9 * 64, 0.f);
-        m->b1.assign(b->data_host, b->data_host + 64); m->b1in.assign(64, 0.f);
-        {   // scaling layer of LPIPS folded into conv1_1: x_c = alpha_c * g + beta_c
-            const double shift[3] = {-.030, -.088, -.188}, scale[3] = {.458, .448, .450};
-            for (int co = 0; co < 64; ++co) {
-                double bsum = 0.0;
-                for (int t = 0; t < 9; ++t) {
-                    double g = 0.0, bb = 0.0;
-                    for (int c = 0; c < 3; ++c) {
-                        const double wv = w->data_host[((size_t)co * 3 + c) * 9 + t];
-                        g += wv * (2.0 / scale[c]); bb += wv * ((-1.0 - shift[c]) / scale[c]);
-                    }
-                    m->wg[(size_t)t * 64 + co] = (float)g; m->wb[(size_t)t * 64 + co] = (float)bb;
-                    bsum += bb;
-                }
-                m->b1in[co] = (float)((double)m->b1[co] + bsum);
-            }
-        }
-        if ((rc = up(m->wg, &m->d_wg))) break;
-        if ((rc = up(m->wb, &m->d_wb))) break;
-        if ((rc = up(m->b1, &m->d_b1))) break;
-        if ((rc = up(m->b1in, &m->d_b1in))) break;
-        for (int l = 0; l < NCONV && !rc; ++l) {
-            Layer& L = m->L[l];
-            L.cin = VGG_CIN[l]; L.cout = VGG_COUT[l];
-            if ((rc = get(std::string(names[l + 1]) + ".weight", (int64_t)L.cout * L.cin * 9, &w))) break;
-            if ((rc = get(std::string(names[l + 1]) + ".bias", L.cout, &b))) break;
-            L.w.assign((size_t)L.cout * 9 * L.cin, 0.f); L.b.assign(b->data_host, b->data_host + L.cout);
-            for (int co = 0; co < L.cout; ++co) for (int ci = 0; ci < L.cin; ++ci) for (int t = 0; t < 9; ++t)
-                L.w[((size_t)co * 9 + t) * L.cin + ci] = w->data_host[((size_t)co * L.cin + ci) * 9 + t];
-            L.x3 = m->mode;
-            // exact-fp32 mode: the Winograd-domain weights too (model.cpp finish_conv; EVR_WINO=0: never)
-            if (L.x3 == 0 && wino_enabled() && L.cin % 16 == 0 && L.cout % 64 == 0) {
-                std::vector<float> u;
-                wino_pack_weights(L.w, L.cout, L.cin, 0, u);
-                if ((rc = up(u, &L.d_wino))) break;
-            }
-            if (L.x3) L.mx_e = pack_weights_for(L.x3, L.w);
-            if (L.x3 == 3) for (float& bv : L.b) bv = std::ldexp(bv, L.mx_e + H2_ACT_EXP);      // (model.cpp finish_conv)
-            if ((rc = up(L.w, &L.d_w))) break;
-            if ((rc = up(L.b, &L.d_b))) break;
-            std::vector<float>().swap(L.w);      // (the packed host copy -- 9 MB for a 512 x 512 layer -- is not needed again)
-        }
+        if ((rc = sd.get(std::string(names[0]) + ".weight", 64 * 3 * 9, &w))) break;
+        if ((rc = sd.get(std::string(names[0]) + ".bias", 64, &b))) break;
+        fold_scaling_layer(w->data_host, b->data_host, 64, 9, m->wg, m->wb, m->b1, m->b1in);
+        if ((rc = upload(m->wg, &m->d_wg))) break;
+        if ((rc = upload(m->wb, &m->d_wb))) break;
+        if ((rc = upload(m->b1, &m->d_b1))) break;
+        if ((rc = upload(m->b1in, &m->d_b1in))) break;
+        for (int l = 0; l < NCONV && !rc; ++l) rc = prepare_backbone_conv(sd, names[l + 1], VGG_CIN[l], VGG_COUT[l], 3, m->mode, &m->L[l]);
         if (rc) break;
         for (int l = 0; l < 5 && !rc; ++l) {
-            if ((rc = get("lin" + std::to_string(l) + ".model.1.weight", TAP_C[l], &w))) break;
+            if ((rc = sd.get("lin" + std::to_string(l) + ".model.1.weight", TAP_C[l], &w))) break;
             std::vector<float> lw(w->data_host, w->data_host + TAP_C[l]);
-            rc = up(lw, &m->d_lin[l]);
+            rc = upload(lw, &m->d_lin[l]);
         }
         if (rc) break;
         if (hipMalloc((void**)&m->d_sat, 64) != hipSuccess) { rc = hip_fail(hipGetLastError(), "hipMalloc(sat)", __FILE__, __LINE__); break; }
@@ -431,9 +369,9 @@ static int vgg_buffers(evr_lpips_vgg* m, int cap, int H, int W, hipStream_t stre
     for (int l = 1; l < 5; ++l) { m->h[l] = m->h[l - 1] / 2; m->w[l] = m->w[l - 1] / 2; }
     int rc;
     const size_t act = (size_t)2 * cap * H * W * 64;      // the largest layer: relu1_1 / relu1_2 (every later one is at most half of it)
-    for (int i = 0; i < 2; ++i) if ((rc = dalloc(m, &m->act[i], act))) return rc;
-    if ((rc = dalloc(m, &m->partials, (size_t)5 * cap * SCORE_BLOCKS_MAX))) return rc;
-    if ((rc = dalloc(m, &m->d_args, (size_t)evr_lpips_vgg::NPLANS * NCONV))) return rc;
+    for (int i = 0; i < 2; ++i) if ((rc = m->allocs.alloc(&m->act[i], act))) return rc;
+    if ((rc = m->allocs.alloc(&m->partials, (size_t)5 * cap * SCORE_BLOCKS_MAX))) return rc;
+    if ((rc = m->allocs.alloc(&m->plans.d_args, (size_t)m->plans.NPLANS * NCONV))) return rc;
     return EVR_OK;
 }
 
@@ -443,48 +381,16 @@ static int conv_src(int i) {
     return (1 + i + VGG_LEVEL[i]) & 1 ? 0 : 1;
 }
 
-// the plan of n pairs inside the current buffers: cached, or built into the least recently used slot (its ConvArgs go to the
-// device in stream order, behind whatever launch still reads the slot's previous contents)
-static int vgg_plan(evr_lpips_vgg* m, int n, hipStream_t stream, evr_lpips_vgg::Plan** out) {
-    evr_lpips_vgg::Plan* pl = nullptr;
-    for (auto& c : m->plans) if (c.n == n) pl = &c;
-    if (pl) { pl->stamp = ++m->clock; *out = pl; return EVR_OK; }
-    for (auto& c : m->plans) {
-        if (c.n == 0) { pl = &c; break; }
-        if (!pl || c.stamp < pl->stamp) pl = &c;
-    }
-    pl->n = 0;
-    const int n2 = 2 * n;
-    bool may_split = false;
+// the plan of n pairs inside the current buffers (PlanCache::get fills a slot with this)
+static void vgg_fill_plan(evr_lpips_vgg* m, PlanCache<NCONV>::Plan& pl, int n) {
     for (int i = 0; i < NCONV; ++i) {
-        Layer& L = m->L[i];
-        ConvArgs& a = pl->args[i];
-        const int lv = VGG_LEVEL[i], hh = m->h[lv], ww = m->w[lv], src = conv_src(i);
-        memset(&a, 0, sizeof(a));
-        a.in0 = m->act[src]; a.c0 = L.cin; a.in_mode = IN_SINGLE; a.n = n2; a.hin = hh; a.win = ww;
-        a.hm = hh; a.wm = ww; a.stride = 1; a.os = 1; a.hout = hh; a.wout = ww;
-        a.tp.ntaps = 9; a.tp.ngroups = 1; a.tp.grp_cols = L.cout;
-        for (int ky = 0; ky < 3; ++ky) for (int kx = 0; kx < 3; ++kx) a.tp.set_tap(ky * 3 + kx, ky - 1, kx - 1, 1);
-        a.wgt = L.d_w; a.bias = L.d_b; a.cout = L.cout; a.n_valid = L.cout; a.out = m->act[src ^ 1]; a.cout_total = L.cout;
-        a.epi = EPI_BIAS_RELU; a.x3 = L.x3;
-        a.wgt_wino = L.d_wino; set_wino_grid(a);
-        a.acc_scale = (L.x3 == 3) ? std::ldexp(1.0f, -(L.mx_e + H2_ACT_EXP)) : 1.0f;
-        a.in_packed = a.out_packed = L.x3 ? 1 : 0;
-        a.mx_sa = 127 - MX_LO_EXP; a.mx_sb = 127 - L.mx_e; a.group_store = use_group_store(); set_fastdiv(a);
+        ConvArgs& a = pl.args[i];
+        const int lv = VGG_LEVEL[i], src = conv_src(i);
+        fill_backbone_conv(a, m->L[i], m->act[src], m->act[src ^ 1], 2 * n, m->h[lv], m->w[lv]);
         a.sat = m->d_sat;
-        pick_conv_tile(a, 32, &pl->wm[i], &pl->nb[i]);
-        if (a.x3 && (int64_t)n2 * a.hm * a.wm <= 192LL * 128) may_split = true;      // (conv.h KSPLIT_WS_BYTES; as lpips_plan)
+        pick_conv_tile(a, 32, &pl.wm[i], &pl.nb[i]);
     }
-    // split-K partial sums at small batches: this handle's own; a failed allocation degrades to "never split"
-    if (may_split && !m->kws && !m->kws_tried) {
-        m->kws_tried = true;
-        if (hipMalloc((void**)&m->kws, KSPLIT_WS_BYTES) != hipSuccess) { (void)hipGetLastError(); m->kws = nullptr; }
-        else m->allocs.push_back((void*)m->kws);
-    }
-    for (int i = 0; i < NCONV; ++i) pl->args[i].ksplit_ws = may_split ? m->kws : nullptr;
-    EVR_HIP(hipMemcpyAsync(m->d_args + NCONV * (pl - m->plans), pl->args, NCONV * sizeof(ConvArgs), hipMemcpyHostToDevice, stream));
-    pl->n = n; pl->stamp = ++m->clock; *out = pl;
-    return EVR_OK;
+    attach_split_workspace(m->kws, m->allocs, pl.args, NCONV, 0);
 }
 
 template <int FMT>
@@ -498,9 +404,9 @@ static int launch_conv1_1(const Conv11Args& c, hipStream_t stream) {
 // one pass: np pairs starting at img / ref, scores to out[0..np) (and out_layers[0..5 np))
 static int vgg_pass(evr_lpips_vgg* m, const float* img, const float* ref, int np, int clip, double* out, double* out_layers, hipStream_t stream) {
     int rc;
-    evr_lpips_vgg::Plan* P = nullptr;
-    if ((rc = vgg_plan(m, np, stream, &P))) return rc;
-    ConvArgs* const d_args = m->d_args + NCONV * (P - m->plans);
+    PlanCache<NCONV>::Plan* P = nullptr;
+    if ((rc = m->plans.get(np, stream, [m](PlanCache<NCONV>::Plan& pl, int n) { vgg_fill_plan(m, pl, n); }, &P))) return rc;
+    ConvArgs* const d_args = m->plans.device_args(P);
     const int fmt = packed_fmt(m->mode);
     Conv11Args c1{};
     c1.img = img; c1.ref = ref; c1.n = np; c1.H = m->H; c1.W = m->W; c1.clip = clip;

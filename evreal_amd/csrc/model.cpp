@@ -212,12 +212,6 @@ int make_affine(const evr_model* m, const std::string& bias_name, const std::str
     return EVR_OK;
 }
 
-int upload(const std::vector<float>& h, float** d) {
-    EVR_HIP(hipMalloc((void**)d, h.size() * sizeof(float) + 64));
-    EVR_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return EVR_OK;
-}
-
 int round_up(int v, int a) { return (v + a - 1) / a * a; }
 
 // Conv2d weight [cout, cin, k, k] -> [n_gemm][k*k][cin]; row_of(co) gives the GEMM row of output channel co.
@@ -416,10 +410,7 @@ int finish_conv(evr_model* m, Conv& c) {
         if ((rc = upload(u, &c.d_wino))) return rc;
     }
     if (c.x3) c.mx_e = pack_weights_for(c.x3, c.w);
-    // mode 3 accumulates products scaled by 2^(e_w + H2_ACT_EXP): the accumulators start at the bias in that scale (exact:
-    // a power of two) and the epilogue multiplies by ConvArgs::acc_scale
-    if (c.x3 == 3) for (float& b : c.b) b = std::ldexp(b, c.mx_e + H2_ACT_EXP);
-    if (c.x3 == 4) for (float& b : c.b) b = std::ldexp(b, c.mx_e);      // (mode 4: weights scaled by 2^e_w, activations unscaled)
+    prescale_bias(c.x3, c.mx_e, c.b);      // (the accumulators start at the bias in the mode's product scale: conv.h acc_exp)
     if ((rc = upload(c.w, &c.d_w))) return rc;
     if ((rc = upload(c.b, &c.d_b))) return rc;
     m->convs.push_back(std::move(c));
@@ -910,9 +901,8 @@ void plan_conv(evr_model* m, int ci, int n, int hin, int win, const ConvIO& io, 
         a.wgt = c.d_w; a.bias = c.d_b; a.cout = c.n_gemm; a.n_valid = c.n_valid;
         a.out = io.out[p]; a.cout_total = cout_total;
         a.epi = c.epi; a.residual = io.residual[p]; a.post_add = io.post_add[p];
-        a.state = io.state[p]; a.aux0 = io.aux0[p]; a.hidden = c.hidden; a.x3 = c.x3;
-        a.acc_scale = (c.x3 == 3) ? std::ldexp(1.0f, -(c.mx_e + H2_ACT_EXP)) : (c.x3 == 4 ? std::ldexp(1.0f, -c.mx_e) : 1.0f);
-        a.mx_sa = 127 - MX_LO_EXP; a.mx_sb = 127 - c.mx_e; a.group_store = use_group_store(); set_fastdiv(a);
+        a.state = io.state[p]; a.aux0 = io.aux0[p]; a.hidden = c.hidden;
+        set_mode_fields(a, c.x3, c.mx_e);
         a.wgt2 = c.d_w2; a.prog = c.d_prog; a.prog_steps = c.prog_steps;
         a.wgt_wino = c.d_wino; a.wino_s2d = c.wino_s2d; set_wino_grid(a);
         a.sat = m->d_sat ? m->d_sat + ci : nullptr;

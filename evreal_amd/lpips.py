@@ -23,52 +23,63 @@ def _tensor_table(state_dict):
     return tensors, keep
 
 
-class LPIPS:
-    def __init__(self, state_dict):
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        tensors, self._keep = _tensor_table(state_dict)
-        h = ctypes.c_void_p()
-        _lib.check(self.lib.evr_lpips_create(tensors, len(tensors), ctypes.byref(h)), 'evr_lpips_create')
-        self.handle = h
+class _Backbone:
+    """What the two LPIPS handles share: `_entry` is the prefix of the backbone's C entry points."""
+    _entry = None
 
-    def __call__(self, img, ref, clip=True, out=None):
-        """img, ref: cuda fp32 [n,H,W] in [0,1] -> double [n] on device."""
-        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dim() == 3
-        img = img.contiguous(); ref = ref.contiguous()
-        n, H, W = img.shape
-        if out is None:
-            out = torch.empty(n, dtype=torch.float64, device=img.device)
-        _lib.check(self.lib.evr_lpips_forward(self.handle, _lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0,
-                                              _lib.ptr(out), _lib.stream_ptr()), 'evr_lpips_forward')
-        return out
-
-    def flops(self):
-        return float(self.lib.evr_lpips_flops(self.handle))
-
-    def __del__(self):
-        try:
-            if self.handle is not None:
-                self.lib.evr_lpips_destroy(self.handle); self.handle = None
-        except Exception:
-            pass
-
-
-class LPIPSVGG:
-    """pyiqa.create_metric('lpips-vgg') stand-in on the GPU (evr_lpips_vgg_*): same call shape as LPIPS.
-
-    max_pairs: frame pairs per pass (0: as many as keep the handle's two activation buffers within 1 GiB); a call with more pairs
-    runs in passes."""
-    MIN_SIDE = 16           # four floor-mode 2x2 pools must leave one pixel
-
-    def __init__(self, state_dict, max_pairs=0):
+    def _create(self, state_dict, *args):
         _lib.require_gpu()
         self.lib = _lib.load()
         tensors, self._keep = _tensor_table(state_dict)
         h = ctypes.c_void_p()
         self.handle = None
-        _lib.check(self.lib.evr_lpips_vgg_create(tensors, len(tensors), int(max_pairs), ctypes.byref(h)), 'evr_lpips_vgg_create')
+        _lib.check(getattr(self.lib, self._entry + '_create')(tensors, len(tensors), *args, ctypes.byref(h)), self._entry + '_create')
         self.handle = h
+
+    @staticmethod
+    def _inputs(img, ref, out):
+        """-> the frames contiguous, and `out` or a new double [n] for the scores."""
+        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dim() == 3
+        if out is None:
+            out = torch.empty(img.shape[0], dtype=torch.float64, device=img.device)
+        return img.contiguous(), ref.contiguous(), out
+
+    def flops(self):
+        return float(getattr(self.lib, self._entry + '_flops')(self.handle))
+
+    def __del__(self):
+        try:
+            if self.handle is not None:
+                getattr(self.lib, self._entry + '_destroy')(self.handle); self.handle = None
+        except Exception:
+            pass
+
+
+class LPIPS(_Backbone):
+    _entry = 'evr_lpips'
+
+    def __init__(self, state_dict):
+        self._create(state_dict)
+
+    def __call__(self, img, ref, clip=True, out=None):
+        """img, ref: cuda fp32 [n,H,W] in [0,1] -> double [n] on device."""
+        img, ref, out = self._inputs(img, ref, out)
+        n, H, W = img.shape
+        _lib.check(self.lib.evr_lpips_forward(self.handle, _lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0,
+                                              _lib.ptr(out), _lib.stream_ptr()), 'evr_lpips_forward')
+        return out
+
+
+class LPIPSVGG(_Backbone):
+    """pyiqa.create_metric('lpips-vgg') stand-in on the GPU (evr_lpips_vgg_*): same call shape as LPIPS.
+
+    max_pairs: frame pairs per pass (0: as many as keep the handle's two activation buffers within 1 GiB); a call with more pairs
+    runs in passes."""
+    _entry = 'evr_lpips_vgg'
+    MIN_SIDE = 16           # four floor-mode 2x2 pools must leave one pixel
+
+    def __init__(self, state_dict, max_pairs=0):
+        self._create(state_dict, int(max_pairs))
 
     @classmethod
     def too_small(cls, H, W):
@@ -79,14 +90,11 @@ class LPIPSVGG:
                 f"got {H}x{W}")
 
     def _forward(self, img, ref, clip, out, layers):
-        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dim() == 3
+        img, ref, out = self._inputs(img, ref, out)
         assert img.dtype == ref.dtype == torch.float32
-        img = img.contiguous(); ref = ref.contiguous()
         n, H, W = img.shape
         if self.too_small(H, W):
             raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
-        if out is None:
-            out = torch.empty(n, dtype=torch.float64, device=img.device)
         assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n
         _lib.check(self.lib.evr_lpips_vgg_forward(self.handle, _lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0,
                                                   _lib.ptr(out), _lib.ptr(layers), _lib.stream_ptr()), 'evr_lpips_vgg_forward')
@@ -108,13 +116,3 @@ class LPIPSVGG:
         c = ctypes.c_int64(0)
         _lib.check(self.lib.evr_lpips_vgg_saturation(self.handle, ctypes.byref(c), _lib.stream_ptr()), 'evr_lpips_vgg_saturation')
         return int(c.value)
-
-    def flops(self):
-        return float(self.lib.evr_lpips_vgg_flops(self.handle))
-
-    def __del__(self):
-        try:
-            if self.handle is not None:
-                self.lib.evr_lpips_vgg_destroy(self.handle); self.handle = None
-        except Exception:
-            pass

@@ -10,8 +10,8 @@ inputs in [0,1] -> 2x-1 -> (x - shift)/scale -> AlexNet relu1..relu5 -> channel-
 import torch
 import torch.nn.functional as F
 
-SHIFT = torch.tensor([-.030, -.088, -.188]).view(1, 3, 1, 1)
-SCALE = torch.tensor([.458, .448, .450]).view(1, 3, 1, 1)
+SHIFT = (-.030, -.088, -.188)
+SCALE = (.458, .448, .450)
 CONVS = [("net.slice1.0", 4, 2), ("net.slice2.3", 1, 2), ("net.slice3.6", 1, 1), ("net.slice4.8", 1, 1),
          ("net.slice5.10", 1, 1)]
 
@@ -27,10 +27,11 @@ def features(sd, x):
     return outs
 
 
-def lpips(sd, img, ref):
-    """img, ref: float32 [n,H,W] in [0,1] (gray).  Returns [n] float64 scores."""
-    sd = {k: torch.as_tensor(v).float() for k, v in sd.items()}
-    prep = lambda a: ((2 * torch.as_tensor(a).float().unsqueeze(1).repeat(1, 3, 1, 1) - 1) - SHIFT) / SCALE
+def lpips(sd, img, ref, dtype=torch.float32):
+    """img, ref: float32 [n,H,W] in [0,1] (gray).  Returns [n] float64 scores of the arithmetic carried out in `dtype`."""
+    sd = {k: torch.as_tensor(v).to(dtype) for k, v in sd.items()}
+    shift, scale = (torch.tensor(c, dtype=dtype).view(1, 3, 1, 1) for c in (SHIFT, SCALE))
+    prep = lambda a: ((2 * torch.as_tensor(a).to(dtype).unsqueeze(1).repeat(1, 3, 1, 1) - 1) - shift) / scale
     f0, f1 = features(sd, prep(img)), features(sd, prep(ref))
     total = torch.zeros(len(img), dtype=torch.float64)
     for l, (a, b) in enumerate(zip(f0, f1)):
