@@ -106,7 +106,7 @@ struct ConvArgs {
     int band_lds_pad;         // conv_bandk_kernel: extra dynamic LDS bytes per block (caps the blocks per CU; host-side only)
     int no_band5;             // keep a 5x5 stride-1 convolution on the implicit GEMM (LPIPS conv2: on the evaluation stream the band form's
                               //   three 51-KB blocks per CU crowd the reconstruction stream's work-groups out: 6.0k vs 6.8k frames/s)
-    float* ksplit_ws;         // split-K partial sums (conv.hip launch_band / launch_band_prog): KSPLIT_WS_BYTES of device memory owned by the
+    float* ksplit_ws;         // split-K partial sums (conv_route.cpp route_band / route_band_prog): KSPLIT_WS_BYTES of device memory owned by the
                               //   handle whose launches use it (evr_model per shape, evr_lpips per plan) -- launches of ONE handle are ordered
                               //   on one stream, so they can share it; null: never split.  Host-side only.
     // Winograd F(2x2, 3x3) form of a 3x3 stride-1 convolution in the exact-fp32 mode (wino.hip): transform-domain weights in the

@@ -44,10 +44,10 @@
 //   grid        1-D, remapped so every XCD (private L2) walks a contiguous range of tiles with the N
 //               tile fastest: an A tile is reused from L2 across its N tiles and neighbouring M tiles
 #include "conv.h"
+#include "conv_route.h"
 #include "packed.h"
 #include <atomic>
-#include <cstdlib>
-#include <cstring>
+#include <initializer_list>
 
 // This file is compiled once per split arithmetic (build.py): EVR_ARITH = 2 -- f16 + MX-fp8 on PACKED tensors, plus the
 // exact-fp32 kernels -- EVR_ARITH = 3 -- three f16 products on H2 tensors -- and EVR_ARITH = 4 -- f16 + MX-fp6 on P6 tensors, the
@@ -1155,93 +1155,6 @@ __global__ __launch_bounds__(256, (KSMAX > 4) ? 1 : 2) void conv_ksplit_epi4_ker
 #endif
 }
 
-// the epilogue launch of a split-K convolution (ks runs per tile)
-constexpr int KSPLIT_RUNS_MAX = 8;      // what conv_ksplit_epi4_kernel<..., 8> sums; ksplit_cap clamps EVR_KSPLIT / EVR_KSPLIT_SMALL to it
-template <bool LSTM, bool GROUPED>
-static void launch_ksplit_epilogue(const ConvArgs* d_args, float* img, int total, int ks, const float* kws, hipStream_t stream) {
-    static const int wide = getenv("EVR_KSPLIT_EPI4") ? atoi(getenv("EVR_KSPLIT_EPI4")) : 1;      // (A/B: 0 = one block per tile)
-    constexpr bool can4 = !(LSTM && ARITH == 4);      // (P6 tensors are written as whole 16-channel groups: the ConvLSTM quad form has no writer)
-    if constexpr (can4) if (wide) {
-        if (ks <= 4) { hipLaunchKernelGGL((conv_ksplit_epi4_kernel<LSTM, GROUPED, 4>), dim3(total * 4), dim3(256), 0, stream, d_args, img, ks, kws); return; }
-        if (ks <= KSPLIT_RUNS_MAX) { hipLaunchKernelGGL((conv_ksplit_epi4_kernel<LSTM, GROUPED, 8>), dim3(total * 4), dim3(256), 0, stream, d_args, img, ks, kws); return; }
-        // (more runs than the wide form sums -- ksplit_cap never lets that happen -- fall through to the any-count epilogue)
-    }
-    hipLaunchKernelGGL((conv_ksplit_epilogue_kernel<LSTM, GROUPED>), dim3(total), dim3(256), 0, stream, d_args, img, ks, kws);
-}
-
-// most runs per tile: 4, and 8 for launches of at most 64 tiles (the residual convolutions and dec0 of ONE sequence: 24 / 48 tiles --
-// eight runs still leave slots free).  Measured on one box, three runs each, +-0.1 %: a flat cap of 8 is +1.1 % at one sequence (2183 vs
-// 2159 frames/s) and -1.0 % at four (5 runs for the 92-tile residual convolutions and enc2.rec: the 8-run epilogue kernel holds one block
-// per CU); caps of 5 / 6: -3 % at one sequence; 5-6 runs for 65-102 tiles with a six-run epilogue kernel at two blocks per CU: 2206 vs 2245 at
-// one sequence, equal at four.  EVR_KSPLIT sets the general cap, EVR_KSPLIT_SMALL the one for <= 64 tiles.
-// Both switches are clamped to KSPLIT_RUNS_MAX = 8: conv_ksplit_epi4_kernel<..., 8> sums at most eight partial sets (with
-// EVR_KSPLIT=16 the main kernel wrote sixteen and the epilogue silently summed the first eight).
-static int ksplit_cap(int total, int ks_max) {
-    static const int ks_small = getenv("EVR_KSPLIT_SMALL") ? atoi(getenv("EVR_KSPLIT_SMALL")) : (getenv("EVR_KSPLIT") ? 0 : 8);
-    const int cap = (total <= 64 && ks_small > ks_max) ? ks_small : ks_max;
-    return cap > KSPLIT_RUNS_MAX ? KSPLIT_RUNS_MAX : cap;
-}
-// workspace of the split-K launches: ConvArgs::ksplit_ws, KSPLIT_WS_BYTES owned by the handle (model / LPIPS) whose plan this is --
-// allocated with the plan, freed with it, never touched in the launch path (no hipMalloc / synchronisation here: a step can be
-// captured into a hipGraph, and two devices or two handles never share partial sums)
-static float* ksplit_workspace(const ConvArgs& a, size_t bytes) { return (a.ksplit_ws && bytes <= KSPLIT_WS_BYTES) ? a.ksplit_ws : nullptr; }
-
-template <int WM, int RING, bool LSTM, bool GROUPED = false, bool OVL = false, int PHASES = 0>
-static int launch_band(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream, float* img) {
-    const int M = a.n * a.hm * a.wm;
-    const int tmv = OVL ? 32 * WM - 2 : 32 * WM;
-    const int mtiles = (M + tmv - 1) / tmv;
-    const int total = mtiles * (a.cout / 128);
-    // split K when the launch leaves most of the 512 resident slots empty (small batches; the deep layers: a 346x260 sequence is 12
-    // 128-pixel tiles at the bottom of the UNet) and K is long enough to cut: runs of >= 1 input-channel chunk, at most 4, never more
-    // blocks than slots.  (A cost model that also split launches of 200-1000 tiles into more than one round measured slower: 1487 vs
-    // 1599 frames/s at one sequence, 4098 vs 4356 at eight -- the partial accumulators are 64 KB per block each way.)
-    int ks = 1;
-    if constexpr (WM == 4 && !OVL) {
-        static const int ks_max = getenv("EVR_KSPLIT") ? atoi(getenv("EVR_KSPLIT")) : 4;      // (0 / 1: never)
-        const int nchunks = (a.c0 + (a.in_mode == IN_CAT ? a.c1 : 0)) / 32;
-        if (ks_max > 1 && total <= 192 && nchunks >= 2 && !a.pred_w) {
-            ks = 512 / total;
-            if (ks > nchunks) ks = nchunks;
-            if (ks > ksplit_cap(total, ks_max)) ks = ksplit_cap(total, ks_max);
-            if (ks < 2) ks = 1;
-        }
-    }
-    float* kws = nullptr;
-    if (ks > 1) {
-        kws = ksplit_workspace(a, (size_t)total * ks * 4 * 16 * 64 * sizeof(float4));
-        if (!kws) ks = 1;
-    }
-    // (round 5: the 3-slot weight ring -- tiles requested TWO steps ahead, 84 KB of LDS -- for the split launches, which have one
-    // block per CU and nobody to hide a DMA latency behind: 2095 vs 2206 frames/s at one sequence, 3856 vs 3944 at four.  Not kept.)
-    if (ks > 1) hipLaunchKernelGGL((conv3x3_band_kernel<WM, RING, LSTM, GROUPED, OVL, PHASES, true>), dim3(total * ks), dim3(64 * WM), 0, stream, d_args, img, ks, kws);
-    else hipLaunchKernelGGL((conv3x3_band_kernel<WM, RING, LSTM, GROUPED, OVL, PHASES, false>), dim3(total), dim3(64 * WM), 0, stream, d_args, img, 1, (float*)nullptr);
-    EVR_LAUNCH_CHECK();
-    if (ks > 1) {
-        launch_ksplit_epilogue<LSTM, GROUPED>(d_args, img, total, ks, (const float*)kws, stream);
-        EVR_LAUNCH_CHECK();
-    }
-    return EVR_OK;
-}
-
-// the band kernel takes: split arithmetic on PACKED inputs, 3x3 taps in row-major order, stride 1 on the input's own grid,
-// N a multiple of 128, and enough pixels to fill the chip with 256-pixel tiles
-static bool band_eligible(const ConvArgs& a, int kc) {
-    static const bool off = getenv("EVR_NO_BAND") != nullptr;
-    if (off) return false;
-    if (!(a.x3 && a.in_packed && kc == 32 && a.tp.ntaps == 9 && a.stride == 1)) return false;
-    if (a.hm != a.hin || a.wm != a.win || a.cout % 128 != 0) return false;
-    if (a.tp.ngroups == 1) { if (a.os != 1 || a.hout != a.hm || a.wout != a.wm) return false; }
-    else if (a.os != 2 || a.hout != 2 * a.hm || a.wout != 2 * a.wm || a.epi == EPI_LSTM) return false;     // transposed conv
-    for (int t = 0; t < 9; ++t)
-        if (a.tp.tap[t] != (((t / 3 - 1) & 0xffff) | ((t % 3 - 1) * 65536))) return false;
-    const int64_t M = (int64_t)a.n * a.hm * a.wm;
-    // (round 3: no fill threshold any more -- for launches that do not fill the chip the band form still beats the implicit GEMM,
-    // whose 9-fold A re-fetch is the cost either way: +16-17 % end to end at 1 / 4 / 8 / 16 sequences.  EVR_BAND_MIN restores one.)
-    static const int min_blocks = getenv("EVR_BAND_MIN") ? atoi(getenv("EVR_BAND_MIN")) : 1;
-    return ((M + 127) / 128) * (a.cout / 128) >= min_blocks;     // blocks of the default 128-pixel tiles
-}
-
 // ---------------------------------------------------------------------------------------------------
 // Band kernel for the 5x5 (and narrow 3x3) stride-1 'same' convolutions (UpsampleConvLayer decoders of the E2VID+ / SSL-E2VID / HyperE2VID /
 // ET-Net layouts, submodules.py:69-97; LPIPS conv2) in the split arithmetics on PACKED / H2 inputs.
@@ -1401,35 +1314,6 @@ __global__ __launch_bounds__(256, (NB == 4) ? 2 : 3) void conv_bandk_kernel(cons
 #endif
 }
 
-template <int KW, int NB>
-static int launch_bandk(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream, float* img) {
-    const int M = a.n * a.hm * a.wm;
-    const int total = ((M + 127) / 128) * (a.cout / (32 * NB));
-    // (a.band_lds_pad: extra dynamic LDS per block -- caps the blocks a CU holds, for launches that share the chip with another stream)
-    hipLaunchKernelGGL((conv_bandk_kernel<KW, NB>), dim3(total), dim3(256), (size_t)a.band_lds_pad, stream, d_args, img);
-    EVR_LAUNCH_CHECK();
-    return EVR_OK;
-}
-
-// split arithmetic on PACKED inputs, kw x kw taps in row-major order, stride 1 on the input's own grid; every epilogue but the
-// ConvLSTM one (which needs 128-column tiles: conv3x3_band_kernel / conv3x3_wide_kernel).  kw = 5: the upsample-conv decoders;
-// kw = 3: the 3x3 layers whose N is not a multiple of 128 (ConvGRU layouts, HyperE2VID's bases_net, FireNet padded to 32 channels)
-static bool bandk_eligible(const ConvArgs& a, int kc, int kw) {
-    static const bool off = getenv("EVR_NO_BAND") != nullptr || (getenv("EVR_BAND5") && atoi(getenv("EVR_BAND5")) == 0);
-    if (off) return false;
-    if (!(a.x3 && a.in_packed && kc == 32 && a.tp.ntaps == kw * kw && a.stride == 1 && a.tp.ngroups == 1) || a.no_band5) return false;
-    if (a.hm != a.hin || a.wm != a.win || a.os != 1 || a.hout != a.hm || a.wout != a.wm || a.cout % 32 != 0) return false;
-    if (a.epi == EPI_LSTM) return false;
-    if (kw == 3 && a.cout % 128 == 0) return false;       // the 128-column kernels take those
-    for (int t = 0; t < kw * kw; ++t)
-        if (a.tp.tap[t] != (((t / kw - kw / 2) & 0xffff) | ((t % kw - kw / 2) * 65536))) return false;
-    const int nb = (a.cout % 128 == 0) ? 4 : (a.cout % 64 == 0) ? 2 : 1;
-    if (a.pred_w && a.cout != 32 * nb) return false;      // a fused prediction needs a single N tile
-    const int64_t M = (int64_t)a.n * a.hm * a.wm;
-    static const int min_blocks = getenv("EVR_BAND_MIN") ? atoi(getenv("EVR_BAND_MIN")) : (getenv("EVR_BAND5_MIN") ? atoi(getenv("EVR_BAND5_MIN")) : 1);
-    return ((M + 127) / 128) * (a.cout / (32 * nb)) >= min_blocks;
-}
-
 #if EVR_ARITH == 3
 // ---------------------------------------------------------------------------------------------------
 // FireNet's 3x3 layers (16 channels; ConvGRU gates over cat(x, h), residual-block convs) in the three-f16-product arithmetic.
@@ -1457,7 +1341,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_kernel(const ConvArgs* __r
     // = 4.7 MB on the whole chip -- at ~2 us per round trip that is the 2.2 TB/s the kernel measured (0.27 of the roof).
     // NBUF = 4 (two-source layers: the ConvGRU gates; 74 KB, two blocks per CU) or 2 (one-source layers: the residual convolutions,
     // whose 9 weight tiles leave room for FOUR blocks per CU at 37 KB -- they are bound by per-tile latency, not by bytes: 4.2 us per
-    // 128-pixel tile and block for 0.4 us of MFMAs); the LDS is sized per launch (launch_c16).
+    // 128-pixel tile and block for 0.4 us of MFMAs); the LDS is sized per launch (conv_route.cpp route_c16_tile).
     constexpr int DIST = NBUF - 1;
     extern __shared__ __attribute__((aligned(16))) float4 lds[];   // [band ring | weights (9 or 18 tiles) | a zero row]
     (void)MAX_TC;
@@ -1595,42 +1479,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_kernel(const ConvArgs* __r
         mt += mstep;
     }
 #endif
-}
-
-template <int NB>
-static int launch_c16(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream, float* img) {
-    const int M = a.n * a.hm * a.wm;
-    const int mtiles = (M + 127) / 128, ntiles_n = a.cout / (32 * NB);
-    const int nsrc = (a.in_mode == IN_CAT && a.c1) ? 2 : 1;
-    static const int c16_blocks = getenv("EVR_C16_BLOCKS") ? atoi(getenv("EVR_C16_BLOCKS")) : 3;      // (A/B: blocks per CU of the one-source form)
-    // SHIPPED DEFAULTS: two band buffers and three blocks per CU for every layer.  One-source layers (residual convolutions): measured
-    // 3 > 4 > 2 blocks (157 / 183 / 189 us); two-source layers (ConvGRU z|r gates, 32 real columns; the candidate convolution, <= 16
-    // real columns = half the weight rows): three blocks with two buffers beat the ring of four at two blocks (273 vs 312-320 us,
-    // 265 vs 308-381).  EVR_C16_ZR / EVR_C16_OUT=<nbuf>,<blocks> select the ring of four (nbuf = 4, 70 KB) for A/B runs.
-    const bool half_w = NB == 1 && a.n_valid <= 16;
-    static const int out_nbuf = [] { const char* e = getenv("EVR_C16_OUT"); return e ? atoi(e) : 2; }();
-    static const int out_blocks = [] { const char* e = getenv("EVR_C16_OUT"); const char* c = e ? strchr(e, ',') : nullptr; return c ? atoi(c + 1) : 3; }();
-    static const int zr_nbuf = [] { const char* e = getenv("EVR_C16_ZR"); return e ? atoi(e) : 2; }();      // (the z|r gate launches: <nbuf>,<blocks>)
-    static const int zr_blocks = [] { const char* e = getenv("EVR_C16_ZR"); const char* c = e ? strchr(e, ',') : nullptr; return c ? atoi(c + 1) : 3; }();
-    const int nbuf = nsrc == 1 ? 2 : (half_w ? (out_nbuf == 4 ? 4 : 2) : (zr_nbuf == 4 ? 4 : 2));
-    const int wrows = half_w ? 16 : 32 * NB;
-    const size_t lds_bytes = ((size_t)nbuf * (128 + 2) * 4 + (size_t)9 * nsrc * wrows * 4 + 4) * sizeof(float4);
-    int per_cu = nsrc == 1 ? (c16_blocks > 0 ? c16_blocks : 3) : (half_w ? (out_blocks > 0 ? out_blocks : 3) : (zr_blocks > 0 ? zr_blocks : 3));
-    int per_n = 256 * per_cu;                             // persistent: the resident blocks walk the M tiles
-    if (per_n > mtiles) per_n = mtiles;
-    // the LDS-size attribute is per device (the ring-of-four forms need 70 KB): remember it per (device, NB)
-    static std::atomic<unsigned> attr_done[64];
-    int dev = 0;
-    EVR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_done[dev].load(std::memory_order_relaxed)) {
-        EVR_HIP(hipFuncSetAttribute((const void*)conv3x3_c16_kernel<NB, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        EVR_HIP(hipFuncSetAttribute((const void*)conv3x3_c16_kernel<NB, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if (dev >= 0 && dev < 64) attr_done[dev].store(1, std::memory_order_relaxed);
-    }
-    if (nbuf == 2) hipLaunchKernelGGL((conv3x3_c16_kernel<NB, 2>), dim3((unsigned)(per_n * ntiles_n)), dim3(256), lds_bytes, stream, d_args, img);
-    else hipLaunchKernelGGL((conv3x3_c16_kernel<NB, 4>), dim3((unsigned)(per_n * ntiles_n)), dim3(256), lds_bytes, stream, d_args, img);
-    EVR_LAUNCH_CHECK();
-    return EVR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1818,85 +1666,6 @@ __global__ __launch_bounds__(256 * RPB, (RPB == 1 ? 3 : 2)) void conv3x3_c16_row
 #endif
 }
 
-// rows per segment: about two items per resident block, even, at least 8 (the halo rows are fetched once more per segment)
-static void c16_rows_plan(const ConvArgs& a, int blocks, int* rseg, int* nseg, int* nstrips) {
-    const int H = a.hin, W = a.win;
-    *nstrips = (W + 127) / 128;
-    int want = (2 * blocks + a.n * *nstrips - 1) / (a.n * *nstrips);
-    if (want < 1) want = 1;
-    int rs = (H + want - 1) / want;
-    rs = (rs + 1) & ~1;
-    if (rs < 8) rs = 8;
-    *rseg = rs; *nseg = (H + rs - 1) / rs;
-}
-
-// EVR_C16_ROWS: 0 = the tile kernel everywhere, 2 = the row kernel whatever the size
-static int c16_rows_mode() {
-    static const int v = getenv("EVR_C16_ROWS") ? atoi(getenv("EVR_C16_ROWS")) : 1;
-    return v;
-}
-static bool c16_rows_eligible(const ConvArgs& a) {
-    if (c16_rows_mode() <= 0) return false;
-    if ((int64_t)a.n * a.hin * a.win >= (1LL << 26)) return false;      // (32-bit byte offsets of 64-B pixels)
-    if ((a.epi == EPI_GRU_ZR || a.epi == EPI_GRU_OUT) && a.hidden != 16) return false;      // (gru_prefetch16)
-    // (a small batch has too few (strip, segment) items to fill the chip: the tile kernel's 128-pixel tiles stay; EVR_C16_ROWS=2
-    // lifts the threshold -- the parity tests' small shapes)
-    return c16_rows_mode() >= 2 || (int64_t)a.n * ((a.win + 127) / 128) * ((a.hin + 7) / 8) >= 1024;
-}
-
-template <int NB, int RPB, int NSRC, bool HALFW>
-static int launch_c16_rows_t(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream, float* img, int per_cu) {
-    constexpr int NBUF = 2 * RPB + 2;
-    constexpr int wrows = HALFW ? 16 : 32 * NB;
-    const size_t lds_bytes = ((size_t)NSRC * NBUF * (128 + 2) * 4 + (size_t)9 * NSRC * wrows * 4 + 4 + 8 * NB) * sizeof(float4);
-    const int ntiles_n = a.cout / (32 * NB);
-    int rseg, nseg, nstrips;
-    c16_rows_plan(a, 256 * per_cu, &rseg, &nseg, &nstrips);
-    int64_t items = (int64_t)a.n * nseg * nstrips;
-    int blocks = 256 * per_cu;
-    if (blocks > items) blocks = (int)items;
-    static std::atomic<unsigned> attr_done[64];
-    int dev = 0;
-    EVR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_done[dev].load(std::memory_order_relaxed)) {
-        EVR_HIP(hipFuncSetAttribute((const void*)conv3x3_c16_rows_kernel<NB, RPB, NSRC, HALFW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if (dev >= 0 && dev < 64) attr_done[dev].store(1, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL((conv3x3_c16_rows_kernel<NB, RPB, NSRC, HALFW>), dim3((unsigned)(blocks * ntiles_n)), dim3(256 * RPB), lds_bytes, stream,
-                       d_args, img, rseg, nseg, nstrips);
-    EVR_LAUNCH_CHECK();
-    return EVR_OK;
-}
-
-template <int NB>
-static int launch_c16_rows(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream, float* img) {
-    const int nsrc = (a.in_mode == IN_CAT && a.c1) ? 2 : 1;
-    const bool half_w = NB == 1 && a.n_valid <= 16;
-    // rows per step and blocks per CU: EVR_C16_ROWS_1=<rows>,<blocks> for the one-source layers, EVR_C16_ROWS_2 for the two-source ones
-    // (A/B).  LDS: one source, 1 row = 4 x 8.3 + 18 (9) KB -> three blocks; two sources, 2 rows = 12 x 8.3 + 36 (18) KB -> one block of 8 waves
-    static const int r1 = [] { const char* e = getenv("EVR_C16_ROWS_1"); return e ? atoi(e) : 1; }();
-    static const int b1 = [] { const char* e = getenv("EVR_C16_ROWS_1"); const char* c = e ? strchr(e, ',') : nullptr; return c ? atoi(c + 1) : 0; }();
-    static const int r2 = [] { const char* e = getenv("EVR_C16_ROWS_2"); return e ? atoi(e) : 2; }();
-    static const int b2 = [] { const char* e = getenv("EVR_C16_ROWS_2"); const char* c = e ? strchr(e, ',') : nullptr; return c ? atoi(c + 1) : 0; }();
-    const int rows = nsrc == 1 ? r1 : 2, bl = nsrc == 1 ? b1 : b2;      // (two sources: always two rows per step -- one row per step leaves four waves on the CU)
-    (void)r2;
-    const int per_cu = bl > 0 ? bl : (rows == 2 ? 1 : (nsrc == 1 ? 3 : 1));
-    if (rows == 2) {
-        if (nsrc == 1) return half_w ? launch_c16_rows_t<NB, 2, 1, true>(a, d_args, stream, img, per_cu) : launch_c16_rows_t<NB, 2, 1, false>(a, d_args, stream, img, per_cu);
-        return half_w ? launch_c16_rows_t<NB, 2, 2, true>(a, d_args, stream, img, per_cu) : launch_c16_rows_t<NB, 2, 2, false>(a, d_args, stream, img, per_cu);
-    }
-    return half_w ? launch_c16_rows_t<NB, 1, 1, true>(a, d_args, stream, img, per_cu) : launch_c16_rows_t<NB, 1, 1, false>(a, d_args, stream, img, per_cu);
-}
-
-static bool c16_eligible(const ConvArgs& a, int kc) {
-    if (!(a.x3 == 3 && a.in_packed && kc == 16 && a.tp.ntaps == 9 && a.stride == 1 && a.tp.ngroups == 1)) return false;
-    if (a.c0 != 16 || !(a.in_mode == IN_SINGLE || a.c1 == 16)) return false;
-    if (a.hm != a.hin || a.wm != a.win || a.os != 1 || a.hout != a.hm || a.wout != a.wm || a.cout != 32) return false;      // (one N tile of 32 columns: every FireNet layer)
-    if (a.epi == EPI_LSTM) return false;
-    for (int t = 0; t < 9; ++t)
-        if (a.tp.tap[t] != (((t / 3 - 1) & 0xffff) | ((t % 3 - 1) * 65536))) return false;
-    return true;
-}
 #endif   // EVR_ARITH == 3
 
 // ---------------------------------------------------------------------------------------------------
@@ -2225,15 +1994,6 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide_kernel(const ConvArg
         }
     }
 #endif
-}
-
-template <bool LSTM, int WN, bool GROUPED = false, int PHASES = 0>
-static int launch_wide(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream, float* img) {
-    const int M = a.n * a.hm * a.wm;
-    const int total = ((M + 255) / 256) * (a.cout / (128 * WN));
-    hipLaunchKernelGGL((conv3x3_wide_kernel<LSTM, WN, GROUPED, PHASES>), dim3(total), dim3(256 * WN), 0, stream, d_args, img);
-    EVR_LAUNCH_CHECK();
-    return EVR_OK;
 }
 
 #if EVR_ARITH == 3
@@ -2633,19 +2393,6 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
 
 static std::atomic<int64_t> g_wide16_alt_launches{0}, g_wide16_tail_launches{0};
 
-template <int WN, bool ALT = false>
-static int launch_wide16(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream) {
-    // the trimmed prologue / epilogue (TAIL, above the kernel); EVR_WIDE16_TAIL=0: the tile's fixed part as it was
-    static const int tail = getenv("EVR_WIDE16_TAIL") ? atoi(getenv("EVR_WIDE16_TAIL")) : 1;
-    const int M = a.n * a.hm * a.wm;
-    const int total = ((M + 255) / 256) * (a.cout / (128 * WN));
-    if (tail) hipLaunchKernelGGL((conv3x3_wide16_kernel<WN, ALT, true>), dim3(total), dim3(256 * WN), 0, stream, d_args);
-    else hipLaunchKernelGGL((conv3x3_wide16_kernel<WN, ALT, false>), dim3(total), dim3(256 * WN), 0, stream, d_args);
-    EVR_LAUNCH_CHECK();
-    if (ALT) g_wide16_alt_launches.fetch_add(1, std::memory_order_relaxed);
-    if (tail) g_wide16_tail_launches.fetch_add(1, std::memory_order_relaxed);
-    return EVR_OK;
-}
 #endif   // EVR_ARITH == 3
 
 // ---------------------------------------------------------------------------------------------------
@@ -2842,7 +2589,7 @@ __global__ __launch_bounds__(256, 2) void conv_band_prog_kernel(const ConvArgs* 
 // (33.8 KB) + the 2-slot weight ring: 66 KB (NB = 4) / 50 KB (NB = 2) -> two / three blocks per CU.  The band is refetched behind
 // the last step that reads it (barrier, request, wait, barrier -- the other block's MFMAs cover it), so the program's "request the
 // next band now" bits are read at the band's FIRST step (where they sit) and honoured at its LAST.  Plain epilogues only, and no
-// split K: this form is for launches that fill the chip (launch_band_prog).
+// split K: this form is for launches that fill the chip (conv_route.cpp route_band_prog).
 template <int NB>
 __global__ __launch_bounds__(256, 2) void conv_band_prog_wide_kernel(const ConvArgs* __restrict__ ap, float* __restrict__ img_out) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -3025,75 +2772,6 @@ __global__ __launch_bounds__(256, 2) void conv_band_prog_wide_kernel(const ConvA
 #endif
 }
 
-template <int NB>
-static int launch_band_prog(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream, float* img) {
-    const int M = a.n * a.hm * a.wm;
-    const int total = ((M + 127) / 128) * (a.cout / (32 * NB));
-    int ks = 1;
-    if constexpr (NB == 4) {      // split K for under-filled launches (launch_band's rule; runs are whole bands of the step program)
-        static const int ks_max = getenv("EVR_KSPLIT") ? atoi(getenv("EVR_KSPLIT")) : 4;
-        const int nbands = a.prog_steps / 2;      // (>= 2 steps per band on average: an upper bound that keeps every run non-empty)
-        if (ks_max > 1 && total <= 192 && nbands >= 4) {
-            ks = 512 / total;
-            if (ks > nbands / 2) ks = nbands / 2;
-            if (ks > ksplit_cap(total, ks_max)) ks = ksplit_cap(total, ks_max);
-            if (ks < 2) ks = 1;
-        }
-    }
-    {   // 256-pixel tiles once a launch has enough of them to fill the chip (two or three blocks per CU; EVR_PROG_WIDE=0: never)
-        static const int pw_on = getenv("EVR_PROG_WIDE") ? atoi(getenv("EVR_PROG_WIDE")) : 1;
-        static const int pw_min = getenv("EVR_PROG_WIDE_MIN") ? atoi(getenv("EVR_PROG_WIDE_MIN")) : 600;
-        const int total2 = ((M + 255) / 256) * (a.cout / (32 * NB));
-        if (pw_on && total2 >= pw_min && ks == 1) {
-            hipLaunchKernelGGL((conv_band_prog_wide_kernel<NB>), dim3(total2), dim3(256), 0, stream, d_args, img);
-            EVR_LAUNCH_CHECK();
-            return EVR_OK;
-        }
-    }
-    float* kws = nullptr;
-    if (ks > 1) { kws = ksplit_workspace(a, (size_t)total * ks * 4 * 16 * 64 * sizeof(float4)); if (!kws) ks = 1; }
-    if constexpr (NB == 4) {
-        if (ks > 1) {
-            hipLaunchKernelGGL((conv_band_prog_kernel<NB, true>), dim3(total * ks), dim3(256), 0, stream, d_args, img, ks, kws);
-            EVR_LAUNCH_CHECK();
-            launch_ksplit_epilogue<false, false>(d_args, img, total, ks, (const float*)kws, stream);
-            EVR_LAUNCH_CHECK();
-            return EVR_OK;
-        }
-    }
-    hipLaunchKernelGGL((conv_band_prog_kernel<NB, false>), dim3(total), dim3(256), 0, stream, d_args, img, 1, (float*)nullptr);
-    EVR_LAUNCH_CHECK();
-    return EVR_OK;
-}
-
-static bool band_prog_eligible(const ConvArgs& a, int kc) {
-    static const bool off = getenv("EVR_NO_BAND") != nullptr;
-    if (off || !a.prog || !a.wgt2) return false;
-    if (!(a.x3 && a.in_packed && kc == 32 && a.tp.ngroups == 1 && a.tp.ntaps == 25 && a.stride == 2 && a.os == 1)) return false;
-    if (a.in_mode != IN_SINGLE || a.hin != 2 * a.hm || a.win != 2 * a.wm || a.hout != a.hm || a.wout != a.wm) return false;
-    if (a.cout % 64 != 0 || a.pred_w) return false;
-    // measured (64 sequences of 352x264): 64 columns (enc0) 595 -> 510 us with three bf16 products; at 128/256 columns the
-    // band form only tied the implicit GEMM then, but with 2/3 of the matrix cycles the implicit GEMM's 25-fold A re-fetch
-    // (64 B/clk/CU from L2) is the limit: 420/378 -> 395/360 us.  EVR_BAND_PROG_ALL=0 restores the implicit GEMM there.
-    static const bool all = getenv("EVR_BAND_PROG_ALL") ? atoi(getenv("EVR_BAND_PROG_ALL")) != 0 : true;
-    if (a.cout % 128 == 0 && !all) return false;
-    const int nb = (a.cout % 128 == 0) ? 4 : 2;
-    const int64_t M = (int64_t)a.n * a.hm * a.wm;
-    static const int min_blocks = getenv("EVR_BAND_MIN") ? atoi(getenv("EVR_BAND_MIN")) : 1;
-    return ((M + 127) / 128) * (a.cout / (32 * nb)) >= min_blocks;
-}
-
-template <int KC, int WM, int NB, bool LSTM, bool GROUPED, bool REGSTAGE = false, int X3 = 0>
-static int launch_t(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream, float* img) {
-    const int M = a.n * a.hm * a.wm;
-    const int mtiles = (M + 32 * WM - 1) / (32 * WM);
-    const int ntiles = a.cout / (32 * NB);
-    const int total = mtiles * ntiles;
-    hipLaunchKernelGGL((conv_igemm_kernel<KC, WM, NB, LSTM, GROUPED, REGSTAGE, X3>), dim3(total), dim3(64 * WM), 0, stream, d_args, img);
-    EVR_LAUNCH_CHECK();
-    return EVR_OK;
-}
-
 }  // namespace EVR_ANS
 using namespace EVR_ANS;
 #if EVR_ARITH == 3
@@ -3101,7 +2779,61 @@ int64_t conv_wide16_alt_launches() { return g_wide16_alt_launches.load(std::memo
 int64_t conv_wide16_tail_launches() { return g_wide16_tail_launches.load(std::memory_order_relaxed); }
 #endif
 
+// one launch with the route's grid, block and dynamic LDS
+template <typename... P, typename... A>
+static int launch_routed(void (*kernel)(P...), const ConvRoute& r, hipStream_t stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(r.grid), dim3(r.block), r.lds, stream, args...);
+    EVR_LAUNCH_CHECK();
+    return EVR_OK;
+}
+// the epilogue launch of a split-K convolution (r.ks runs per tile)
+template <bool LSTM, bool GROUPED>
+static int launch_ksplit_epilogue(const ConvRoute& r, const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream, float* img) {
+    const float* kws = a.ksplit_ws;
+    constexpr bool can4 = !(LSTM && ARITH == 4);      // (P6 tensors are written as whole 16-channel groups: the ConvLSTM quad form has no writer)
+    if constexpr (can4) {
+        if (r.epi_sum == 4) { hipLaunchKernelGGL((conv_ksplit_epi4_kernel<LSTM, GROUPED, 4>), dim3(r.epi_grid), dim3(256), 0, stream, d_args, img, r.ks, kws); EVR_LAUNCH_CHECK(); return EVR_OK; }
+        if (r.epi_sum == 8) { hipLaunchKernelGGL((conv_ksplit_epi4_kernel<LSTM, GROUPED, 8>), dim3(r.epi_grid), dim3(256), 0, stream, d_args, img, r.ks, kws); EVR_LAUNCH_CHECK(); return EVR_OK; }
+    }
+    hipLaunchKernelGGL((conv_ksplit_epilogue_kernel<LSTM, GROUPED>), dim3(r.epi_grid), dim3(256), 0, stream, d_args, img, r.ks, kws);
+    EVR_LAUNCH_CHECK();
+    return EVR_OK;
+}
+template <bool LSTM, bool GROUPED, int PHASES>
+static int launch_band(const ConvRoute& r, const ConvArgs& a, const ConvArgs* d_args, hipStream_t stream, float* img) {
+    const int e = r.ks > 1 ? launch_routed(conv3x3_band_kernel<4, 2, LSTM, GROUPED, false, PHASES, true>, r, stream, d_args, img, r.ks, a.ksplit_ws)
+                           : launch_routed(conv3x3_band_kernel<4, 2, LSTM, GROUPED, false, PHASES, false>, r, stream, d_args, img, 1, (float*)nullptr);
+    if (e || r.ks == 1) return e;
+    return launch_ksplit_epilogue<LSTM, GROUPED>(r, a, d_args, stream, img);
+}
+#if EVR_ARITH == 3
+// the LDS-size attribute is per device (the ring-of-four forms need 70 KB): remember it per (device, kernel)
+static int c16_lds_attribute(std::initializer_list<const void*> kernels, std::atomic<unsigned>* attr_done) {
+    int dev = 0;
+    EVR_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !attr_done[dev].load(std::memory_order_relaxed)) {
+        for (const void* kernel : kernels) EVR_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        if (dev >= 0 && dev < 64) attr_done[dev].store(1, std::memory_order_relaxed);
+    }
+    return EVR_OK;
+}
+template <int RPB, int NSRC, bool HALFW>
+static int launch_c16_rows(const ConvRoute& r, const ConvArgs* d_args, hipStream_t stream, float* img) {
+    static std::atomic<unsigned> attr_done[64];
+    if (const int e = c16_lds_attribute({(const void*)conv3x3_c16_rows_kernel<1, RPB, NSRC, HALFW>}, attr_done)) return e;
+    return launch_routed(conv3x3_c16_rows_kernel<1, RPB, NSRC, HALFW>, r, stream, d_args, img, r.rseg, r.nseg, r.nstrips);
+}
+template <int WN, bool ALT, bool TAIL>
+static int launch_wide16(const ConvRoute& r, const ConvArgs* d_args, hipStream_t stream) {
+    if (const int e = launch_routed(conv3x3_wide16_kernel<WN, ALT, TAIL>, r, stream, d_args)) return e;
+    if (ALT) g_wide16_alt_launches.fetch_add(1, std::memory_order_relaxed);
+    if (TAIL) g_wide16_tail_launches.fetch_add(1, std::memory_order_relaxed);
+    return EVR_OK;
+}
+#endif
+
 int EVR_LAUNCH_NAME(const ConvArgs& a, const ConvArgs* d_args, int kc, int wm, int nb, hipStream_t stream, float* img) {
+    // ---- 1. is the plan legal?
     EVR_REQUIRE(!a.pred_w || (a.cout == 32 * nb && img), "conv_igemm: fused prediction needs a single N tile and an image pointer");
     EVR_REQUIRE(a.tp.grp_cols % 32 == 0 && a.tp.ngroups <= MAX_PHASES &&
                 (a.tp.inter ? (a.tp.ngroups == 4 && a.tp.grp_cols == 32 && a.cout % 128 == 0 && !a.pred_w) : a.tp.ngroups * a.tp.grp_cols == a.cout),
@@ -3110,177 +2842,122 @@ int EVR_LAUNCH_NAME(const ConvArgs& a, const ConvArgs* d_args, int kc, int wm, i
     EVR_REQUIRE(a.c0 % kc == 0 && (a.in_mode != IN_CAT || a.c1 % kc == 0), "conv_igemm: channels %d/%d not multiples of %d", a.c0, a.c1, kc);
     EVR_REQUIRE(a.epi != EPI_LSTM || nb == 4, "conv_igemm: the LSTM epilogue needs nb == 4");
     EVR_REQUIRE((int64_t)a.n * a.hm * a.wm < (1LL << 31), "conv_igemm: M too large");
-#if EVR_ARITH == 3
-    if (c16_eligible(a, kc)) {
+    if (ARITH == 3 && conv_c16_eligible(a, kc)) {      // (FireNet's 16-channel layers answer to their own, shorter list)
         EVR_REQUIRE(a.acc_scale > 0.f && a.div_hw_sh < 32, "conv3x3_c16: plan without accumulator scale / fastdiv");
-        if (c16_rows_eligible(a)) return launch_c16_rows<1>(a, d_args, stream, img);
-        return launch_c16<1>(a, d_args, stream, img);
-    }
-#endif
-    EVR_REQUIRE(!a.x3 || kc == 32, "conv_igemm: the split path needs 32-channel chunks");
-    EVR_REQUIRE(a.n_valid % 4 == 0 && a.cout_total % 4 == 0, "conv_igemm: output channels %d/%d not multiples of 4 (16-B epilogue accesses)", a.n_valid, a.cout_total);
-    EVR_REQUIRE(a.epi != EPI_LSTM || (a.os == 1 && a.hout == a.hm && a.wout == a.wm && a.hidden % 32 == 0),
-                "conv_igemm: the ConvLSTM epilogue writes the state grid itself (stride 1, hidden %% 32 == 0)");
-    EVR_REQUIRE((a.epi != EPI_GRU_ZR && a.epi != EPI_GRU_OUT) || a.hidden % 4 == 0, "conv_igemm: ConvGRU hidden %d not a multiple of 4", a.hidden);
-    const bool packed_io = a.in_packed || a.out_packed || a.res_packed || a.padd_packed || a.state_packed;
-    EVR_REQUIRE(!packed_io || a.x3, "conv_igemm: PACKED tensors need the split mode");
-    EVR_REQUIRE(!a.x3 || a.in_packed, "conv_igemm: the split kernels take PACKED inputs");
-    EVR_REQUIRE(a.x3 != 2 || (a.mx_sa > 0 && a.mx_sb > 0), "conv_igemm: split mode without block scales");
-    EVR_REQUIRE(a.x3 != 3 || a.acc_scale > 0.f, "conv_igemm: three-product mode without the accumulator scale");
-    EVR_REQUIRE(a.x3 == 0 || a.x3 == 2 || a.x3 == 3 || a.x3 == 4, "conv_igemm: unknown arithmetic mode %d", a.x3);
+    } else {
+        EVR_REQUIRE(!a.x3 || kc == 32, "conv_igemm: the split path needs 32-channel chunks");
+        EVR_REQUIRE(a.n_valid % 4 == 0 && a.cout_total % 4 == 0, "conv_igemm: output channels %d/%d not multiples of 4 (16-B epilogue accesses)", a.n_valid, a.cout_total);
+        EVR_REQUIRE(a.epi != EPI_LSTM || (a.os == 1 && a.hout == a.hm && a.wout == a.wm && a.hidden % 32 == 0),
+                    "conv_igemm: the ConvLSTM epilogue writes the state grid itself (stride 1, hidden %% 32 == 0)");
+        EVR_REQUIRE((a.epi != EPI_GRU_ZR && a.epi != EPI_GRU_OUT) || a.hidden % 4 == 0, "conv_igemm: ConvGRU hidden %d not a multiple of 4", a.hidden);
+        const bool packed_io = a.in_packed || a.out_packed || a.res_packed || a.padd_packed || a.state_packed;
+        EVR_REQUIRE(!packed_io || a.x3, "conv_igemm: PACKED tensors need the split mode");
+        EVR_REQUIRE(!a.x3 || a.in_packed, "conv_igemm: the split kernels take PACKED inputs");
+        EVR_REQUIRE(a.x3 != 2 || (a.mx_sa > 0 && a.mx_sb > 0), "conv_igemm: split mode without block scales");
+        EVR_REQUIRE(a.x3 != 3 || a.acc_scale > 0.f, "conv_igemm: three-product mode without the accumulator scale");
+        EVR_REQUIRE(a.x3 == 0 || a.x3 == 2 || a.x3 == 3 || a.x3 == 4, "conv_igemm: unknown arithmetic mode %d", a.x3);
 #if EVR_ARITH == 3
-    EVR_REQUIRE(a.x3 == 3, "conv_igemm: this object carries the three-f16-product kernels only (mode %d requested)", a.x3);
+        EVR_REQUIRE(a.x3 == 3, "conv_igemm: this object carries the three-f16-product kernels only (mode %d requested)", a.x3);
 #elif EVR_ARITH == 4
-    EVR_REQUIRE(a.x3 == 4, "conv_igemm: this object carries the f16 + fp6 kernels only (mode %d requested)", a.x3);
-    EVR_REQUIRE(a.acc_scale > 0.f, "conv_igemm: f16 + fp6 mode without the accumulator scale");
-    // P6 tensors have a scale per 16-channel group: they are written as whole groups only
-    EVR_REQUIRE(a.group_store && a.epi != EPI_GRU_ZR && a.epi != EPI_GRU_OUT && a.epi != EPI_BIAS_TANH && !(a.pred_w && a.out && a.out_packed),
-                "conv_igemm: the f16 + fp6 mode writes whole 64-B groups only (epilogue %d)", a.epi);
-    EVR_REQUIRE(!a.out_packed || (a.n_valid % 16 == 0 && a.cout_total % 16 == 0), "conv_igemm: P6 output needs channel counts that are multiples of 16");
+        EVR_REQUIRE(a.x3 == 4, "conv_igemm: this object carries the f16 + fp6 kernels only (mode %d requested)", a.x3);
+        EVR_REQUIRE(a.acc_scale > 0.f, "conv_igemm: f16 + fp6 mode without the accumulator scale");
+        // P6 tensors have a scale per 16-channel group: they are written as whole groups only
+        EVR_REQUIRE(a.group_store && a.epi != EPI_GRU_ZR && a.epi != EPI_GRU_OUT && a.epi != EPI_BIAS_TANH && !(a.pred_w && a.out && a.out_packed),
+                    "conv_igemm: the f16 + fp6 mode writes whole 64-B groups only (epilogue %d)", a.epi);
+        EVR_REQUIRE(!a.out_packed || (a.n_valid % 16 == 0 && a.cout_total % 16 == 0), "conv_igemm: P6 output needs channel counts that are multiples of 16");
 #else
-    EVR_REQUIRE(a.x3 != 3 && a.x3 != 4, "conv_igemm: the three-f16-product / f16 + fp6 kernels live in the other objects");
+        EVR_REQUIRE(a.x3 != 3 && a.x3 != 4, "conv_igemm: the three-f16-product / f16 + fp6 kernels live in the other objects");
 #endif
-    EVR_REQUIRE(a.div_hw_sh < 32 && a.div_w_sh < 32 && (a.div_hw_mul || (unsigned)(a.hm * a.wm) == (1u << a.div_hw_sh)) && (a.div_w_mul || (unsigned)a.wm == (1u << a.div_w_sh)),
-                "conv_igemm: plan without set_fastdiv()");
-    EVR_REQUIRE(!a.out_packed || (a.n_valid % 8 == 0 && a.cout_total % 8 == 0), "conv_igemm: PACKED output needs channel counts that are multiples of 8");
-    const int mode = a.x3 ? 2 : 0;
-    if (band_prog_eligible(a, kc)) {
-        if (a.cout % 128 == 0) return launch_band_prog<4>(a, d_args, stream, img);
-        return launch_band_prog<2>(a, d_args, stream, img);
+        EVR_REQUIRE(a.div_hw_sh < 32 && a.div_w_sh < 32 && (a.div_hw_mul || (unsigned)(a.hm * a.wm) == (1u << a.div_hw_sh)) && (a.div_w_mul || (unsigned)a.wm == (1u << a.div_w_sh)),
+                    "conv_igemm: plan without set_fastdiv()");
+        EVR_REQUIRE(!a.out_packed || (a.n_valid % 8 == 0 && a.cout_total % 8 == 0), "conv_igemm: PACKED output needs channel counts that are multiples of 8");
     }
-    if (bandk_eligible(a, kc, 5)) {
-        if (a.cout % 128 == 0) return launch_bandk<5, 4>(a, d_args, stream, img);
-        if (a.cout % 64 == 0) return launch_bandk<5, 2>(a, d_args, stream, img);
-        return launch_bandk<5, 1>(a, d_args, stream, img);
-    }
-    if (bandk_eligible(a, kc, 3)) {
-        if (a.cout % 64 == 0) return launch_bandk<3, 2>(a, d_args, stream, img);
-        return launch_bandk<3, 1>(a, d_args, stream, img);
-    }
-    if (band_eligible(a, kc)) {
-        // 128 x 128 tiles: 4 waves x 2-slot ring, two blocks per CU (one block's epilogue and barrier bubbles hide under the
-        // other's MFMAs).  The 8-wave and overlapped-tile / 3-slot-ring configurations of earlier rounds measured slower
-        // (profiles/r02_tile_variants.txt) and are gone: with the zero row their 80 KiB no longer leave two blocks per CU.
-        // 256-pixel block tiles when N allows and there are enough of them to fill the chip (EVR_WIDE=0: never)
-        static const int wide = getenv("EVR_WIDE") ? atoi(getenv("EVR_WIDE")) : 1;
-        static const int wide_min = getenv("EVR_WIDE_MIN") ? atoi(getenv("EVR_WIDE_MIN")) : 600;   // (round 5: 600 tiles, was 1024 -- +2 % at 8 / 16 / 32 sequences, equal at 4 and 64; 300: -1 % at 16 / 32.  Tests lower it)
-        // two 256 x 128 blocks per CU (one band buffer each) while K is short, one 256 x 256 block otherwise: measured
-        // 1486 / 1449 / 1405 us against 1585 / 1489 / 1401 us for 128 / 256 / 512 input channels (EVR_WIDE=2 / 3 force one)
-        // (round 8, the 256 x 256 form on its skewed loop, 64 sequences, two-stream step, us per launch enc0 / enc1 / enc2.rec: this rule
-        // 1885 / 1822 / 1708 and 1925 / 1850 / 1703, EVR_WIDE=3 1855 / 1803 / 1696 and 1879 / 1810 / 1706, EVR_WIDE=3 on the lock-step
-        // loop 1991 / 1904 / 1790 and 2040 / 1953 / 1849.  The 256 x 256 form now leads on the short-K layers too, by 1-2 %; the rule
-        // stays until the tile-count thresholds below, taken on the lock-step loop, are measured again at 4 - 32 sequences)
-        // (round 9, measured again on the skewed loop with the trimmed tail, us per launch twin / 256 x 256, single-stream step,
-        // profiles/r09_layer_times.txt: enc0.rec -- 128 input channels -- 5808 tiles 1852 / 1822, 2904 tiles 902 / 915, 1452 tiles 471 / 454,
-        // 726 tiles 240 / 235; enc1.rec -- 256 channels -- 2904 tiles 1841 / 1800, 1452 tiles 890 / 852, 726 tiles 447 / 422.  From the
-        // 256 x 256 form's own threshold on the short-K layers take it too, with one exception that keeps the twin form: 128 channels and
-        // a last round of 256 blocks less than half full (2904 = 11.34 rounds), which the twin form's 512 half-width slots finish in
-        // finer pieces.  Below that threshold, and with an explicit EVR_WIDE_MIN, the rule is what it was)
-        const int64_t wide_tiles = (((int64_t)a.n * a.hm * a.wm + 255) / 256) * (a.cout / 256);
-        const bool ragged = wide_tiles % 256 != 0 && wide_tiles % 256 < 128;
-        static const bool wide_min_set = getenv("EVR_WIDE_MIN") != nullptr;
-        const bool short_k_twin = wide_min_set || wide_tiles < wide_min || (a.c0 + a.c1 <= 128 && ragged);
-        const bool twin = (wide == 2) || (wide == 1 && a.c0 + a.c1 <= 256 && short_k_twin);
-        // (the twin form already pays from ~1.4 rounds of its 512 slots on: per-layer times at 4 / 8 sequences, enc0.rec 144 -> 138 us
-        // with 726 twin tiles, enc1.rec 262 -> 249 us with 728; below one round it loses -- enc1.rec 136 -> 151 us with 364 tiles -- and
-        // the 256 x 256 form loses up to its own threshold: enc2.rec 256 -> 279 us at 8 sequences.  Explicit EVR_WIDE_MIN: one threshold)
-        static const int wide_min_twin = getenv("EVR_WIDE_MIN") ? wide_min : 350;
-        const bool wide_ok = wide && a.tp.ngroups == 1 && a.cout % 256 == 0 && !a.pred_w &&
-                             (((int64_t)a.n * a.hm * a.wm + 255) / 256) * (a.cout / 256) >= (twin ? wide_min_twin : wide_min);
-        if (wide_ok && a.epi == EPI_LSTM) {
+    // ---- 2. which kernel, with which grid?
+    const ConvRoute r = conv_route(a, kc, wm, nb, conv_knobs());
+    // ---- 3. launch it (a route to a kernel this object does not carry falls out of its case to the message at the end).
+    // The cases name the kernels in the order the dispatch always did: the kernels are instantiated in that order, and the
+    // compiler's output for some of them depends on it (eight kernels of the mode-4 object come out different otherwise)
+    switch (r.family) {
+    case CONV_NONE:
+        EVR_REQUIRE(r.err != ROUTE_LSTM_KC, "conv_igemm: ConvLSTM needs 32-channel chunks");
+        if (r.err == ROUTE_NO_GROUPED) { set_error("conv_igemm: no grouped kernel for kc=%d wm=%d nb=%d", kc, wm, nb); return EVR_ERR_UNSUPPORTED; }
+        break;
 #if EVR_ARITH == 3
-            // the same tiles on 16x16x32 MFMAs (conv3x3_wide16_kernel); EVR_MFMA16=0: the 32x32x16 form
-            static const int mfma16 = getenv("EVR_MFMA16") ? atoi(getenv("EVR_MFMA16")) : 1;
-            // the 256 x 256 form runs its skewed loop (wave halves alternate load and MFMA); EVR_WIDE16_ALT=0: the lock-step loop
-            static const int alt = getenv("EVR_WIDE16_ALT") ? atoi(getenv("EVR_WIDE16_ALT")) : 1;
-            if (mfma16) return twin ? launch_wide16<1>(a, d_args, stream) : (alt ? launch_wide16<2, true>(a, d_args, stream) : launch_wide16<2>(a, d_args, stream));
+    case CONV_C16_ROWS:
+        if (r.rpb == 2 && r.nsrc == 1) return r.halfw ? launch_c16_rows<2, 1, true>(r, d_args, stream, img) : launch_c16_rows<2, 1, false>(r, d_args, stream, img);
+        if (r.rpb == 2) return r.halfw ? launch_c16_rows<2, 2, true>(r, d_args, stream, img) : launch_c16_rows<2, 2, false>(r, d_args, stream, img);
+        return r.halfw ? launch_c16_rows<1, 1, true>(r, d_args, stream, img) : launch_c16_rows<1, 1, false>(r, d_args, stream, img);
+    case CONV_C16_TILE: {
+        static std::atomic<unsigned> attr_done[64];
+        if (const int e = c16_lds_attribute({(const void*)conv3x3_c16_kernel<1, 2>, (const void*)conv3x3_c16_kernel<1, 4>}, attr_done)) return e;
+        if (r.nbuf == 2) return launch_routed(conv3x3_c16_kernel<1, 2>, r, stream, d_args, img);
+        return launch_routed(conv3x3_c16_kernel<1, 4>, r, stream, d_args, img);
+    }
 #endif
-            return twin ? launch_wide<true, 1>(a, d_args, stream, img) : launch_wide<true, 2>(a, d_args, stream, img);
-        }
-        // plain 3x3 layers (residual blocks): the twin form once a launch has enough 256 x 128 tiles (not at 64 sequences of
-        // 346x260: 726 tiles for 512 slots; from 128 sequences or 640x480 up)
-        // (their own threshold: at 64 sequences the residual convolutions are 726 such tiles -- 1.42 rounds of 512 slots -- and run
-        // 281 us on this form against 258 us on the 128 x 128 tiles; the ConvLSTM threshold above went down to 600 in round 5)
-        static const int wide_min_plain = getenv("EVR_WIDE_MIN_PLAIN") ? atoi(getenv("EVR_WIDE_MIN_PLAIN")) : (wide_min > 1024 ? wide_min : (getenv("EVR_WIDE_MIN") ? wide_min : 1024));
-        if (wide && a.tp.ngroups == 1 && a.cout % 128 == 0 && !a.pred_w &&
-            (a.epi == EPI_BIAS || a.epi == EPI_BIAS_RELU || a.epi == EPI_RESIDUAL_RELU) &&
-            (((int64_t)a.n * a.hm * a.wm + 255) / 256) * (a.cout / 128) >= wide_min_plain)
-            return launch_wide<false, 1>(a, d_args, stream, img);
-        if (a.epi == EPI_LSTM) {
-            return launch_band<4, 2, true>(a, d_args, stream, img);
-        }
-        if (a.tp.ngroups > 1) {
-            {
-                // does the tap/phase connectivity follow the k5 s2 p2 rule the PHASES variants compile in?
-                bool rule = a.tp.ngroups == 4;
-                for (int t = 0; t < 9 && rule; ++t) {
-                    int want = 0;
-                    for (int g = 0; g < 4; ++g) if (!((g >> 1) == 1 && t / 3 == 0) && !((g & 1) == 1 && t % 3 == 0)) want |= 1 << g;
-                    rule = a.tp.tap_groups[t] == want;
-                }
-                for (int g = 0; g < 4 && rule; ++g) rule = a.tp.grp_ofy[g] == (g >> 1) && a.tp.grp_ofx[g] == (g & 1);
-                // 256 x 128 tiles, two blocks per CU (the twin form of conv3x3_wide_kernel), once there are enough of them:
-                // half the LDS-DMA bytes per MFMA cycle of the 128 x 128 tiles (EVR_WIDE_DEC=0: never)
-                static const int wide_dec = getenv("EVR_WIDE_DEC") ? atoi(getenv("EVR_WIDE_DEC")) : 1;
-                // (dec2 -- 32 output channels, 18 steps -- gains from 363 such tiles on: 49 -> 39 us at 4 sequences; dec1 at 364 loses, 83 -> 92 us)
-                static const int wide_min_dec32 = getenv("EVR_WIDE_MIN") ? wide_min : 350;
-                const bool twin_ok = wide_dec && rule && (((int64_t)a.n * a.hm * a.wm + 255) / 256) * (a.cout / 128) >= (a.tp.grp_cols == 32 ? wide_min_dec32 : wide_min) &&
-                                     (a.epi == EPI_BIAS || a.epi == EPI_BIAS_RELU) && (!a.pred_w || a.tp.grp_cols == 32);   // (a fused
-                // prediction must close inside one 32-column block: the epilogue runs block by block)
-                if (twin_ok && a.tp.grp_cols == 32) return launch_wide<false, 1, true, 1>(a, d_args, stream, img);
-                if (twin_ok && a.tp.grp_cols == 64) return launch_wide<false, 1, true, 2>(a, d_args, stream, img);
-                if (twin_ok && a.tp.grp_cols % 128 == 0) return launch_wide<false, 1, true, 0>(a, d_args, stream, img);
-                if (rule && a.tp.grp_cols == 32) return launch_band<4, 2, false, true, false, 1>(a, d_args, stream, img);
-                if (rule && a.tp.grp_cols == 64) return launch_band<4, 2, false, true, false, 2>(a, d_args, stream, img);
-                return launch_band<4, 2, false, true>(a, d_args, stream, img);
+    case CONV_BAND_PROG: case CONV_BAND_PROG_WIDE: case CONV_BAND_PROG_KSPLIT:
+        if (r.nb == 4) {
+            if (r.family == CONV_BAND_PROG_WIDE) return launch_routed(conv_band_prog_wide_kernel<4>, r, stream, d_args, img);
+            if (r.family == CONV_BAND_PROG_KSPLIT) {
+                if (const int e = launch_routed(conv_band_prog_kernel<4, true>, r, stream, d_args, img, r.ks, a.ksplit_ws)) return e;
+                return launch_ksplit_epilogue<false, false>(r, a, d_args, stream, img);
             }
-            return launch_band<4, 2, false, true>(a, d_args, stream, img);
+            return launch_routed(conv_band_prog_kernel<4, false>, r, stream, d_args, img, 1, (float*)nullptr);
         }
-        return launch_band<4, 2, false>(a, d_args, stream, img);
-    }
-    if (a.epi == EPI_LSTM) {
-        EVR_REQUIRE(kc == 32, "conv_igemm: ConvLSTM needs 32-channel chunks");
-        if (mode == 2) {
-            if (wm == 8) return launch_t<32, 8, 4, true, false, true, 2>(a, d_args, stream, img);
-            if (wm == 4) return launch_t<32, 4, 4, true, false, true, 2>(a, d_args, stream, img);
-            if (wm == 2) return launch_t<32, 2, 4, true, false, false, 2>(a, d_args, stream, img);
-            return launch_t<32, 1, 4, true, false, false, 2>(a, d_args, stream, img);
-        }
-#if EVR_ARITH == 2
-        if (wm == 8) return launch_t<32, 8, 4, true, false>(a, d_args, stream, img);
-        // register staging measured +1..4 % over LDS-DMA for this kernel (EVR_LSTM_DMA=1 selects the DMA loader)
-        if (wm == 4 && !getenv("EVR_LSTM_DMA")) return launch_t<32, 4, 4, true, false, true>(a, d_args, stream, img);
-        if (wm == 4) return launch_t<32, 4, 4, true, false>(a, d_args, stream, img);
-        if (wm == 2) return launch_t<32, 2, 4, true, false>(a, d_args, stream, img);
-        return launch_t<32, 1, 4, true, false>(a, d_args, stream, img);
+        if (r.family == CONV_BAND_PROG_WIDE) return launch_routed(conv_band_prog_wide_kernel<2>, r, stream, d_args, img);
+        return launch_routed(conv_band_prog_kernel<2, false>, r, stream, d_args, img, 1, (float*)nullptr);
+    case CONV_BANDK:
+        if (r.kw == 5 && r.nb == 4) return launch_routed(conv_bandk_kernel<5, 4>, r, stream, d_args, img);
+        if (r.kw == 5 && r.nb == 2) return launch_routed(conv_bandk_kernel<5, 2>, r, stream, d_args, img);
+        if (r.kw == 5) return launch_routed(conv_bandk_kernel<5, 1>, r, stream, d_args, img);
+        if (r.nb == 2) return launch_routed(conv_bandk_kernel<3, 2>, r, stream, d_args, img);
+        return launch_routed(conv_bandk_kernel<3, 1>, r, stream, d_args, img);
+#if EVR_ARITH == 3
+    case CONV_WIDE16:
+        if (r.wn == 1) return r.tail ? launch_wide16<1, false, true>(r, d_args, stream) : launch_wide16<1, false, false>(r, d_args, stream);
+        if (r.alt) return r.tail ? launch_wide16<2, true, true>(r, d_args, stream) : launch_wide16<2, true, false>(r, d_args, stream);
+        return r.tail ? launch_wide16<2, false, true>(r, d_args, stream) : launch_wide16<2, false, false>(r, d_args, stream);
 #endif
+    case CONV_WIDE: case CONV_BAND: {      // the 3x3 band layers: ConvLSTM gates, plain layers, transposed decoders -- 256-pixel tiles or 128
+        const bool wide = r.family == CONV_WIDE;
+        if (wide && r.lstm) return r.wn == 1 ? launch_routed(conv3x3_wide_kernel<true, 1>, r, stream, d_args, img) : launch_routed(conv3x3_wide_kernel<true, 2>, r, stream, d_args, img);
+        if (wide && !r.grouped) return launch_routed(conv3x3_wide_kernel<false, 1>, r, stream, d_args, img);
+        if (r.lstm) return launch_band<true, false, 0>(r, a, d_args, stream, img);
+        if (wide && r.phases == 1) return launch_routed(conv3x3_wide_kernel<false, 1, true, 1>, r, stream, d_args, img);
+        if (wide && r.phases == 2) return launch_routed(conv3x3_wide_kernel<false, 1, true, 2>, r, stream, d_args, img);
+        if (wide) return launch_routed(conv3x3_wide_kernel<false, 1, true, 0>, r, stream, d_args, img);
+        if (r.grouped && r.phases == 1) return launch_band<false, true, 1>(r, a, d_args, stream, img);
+        if (r.grouped && r.phases == 2) return launch_band<false, true, 2>(r, a, d_args, stream, img);
+        if (r.grouped) return launch_band<false, true, 0>(r, a, d_args, stream, img);
+        return launch_band<false, false, 0>(r, a, d_args, stream, img);
     }
-    if (a.tp.ngroups > 1) {   // transposed conv: column groups = sub-pixel phases
+    case CONV_IGEMM:
+#define EVR_CASE(KC_, WM_, NB_, LSTM_, GROUPED_, REGSTAGE_, X3_)                                                                        \
+    if (r.kc == KC_ && r.wm == WM_ && r.nb == NB_ && r.lstm == LSTM_ && r.grouped == GROUPED_ && r.regstage == REGSTAGE_ && r.x3 == X3_) \
+        return launch_routed(conv_igemm_kernel<KC_, WM_, NB_, LSTM_, GROUPED_, REGSTAGE_, X3_>, r, stream, d_args, img);
 #if EVR_ARITH == 2
-#define EVR_CASEG(WM_, NB_) if (kc == 32 && wm == WM_ && nb == NB_) { if (mode == 2) return launch_t<32, WM_, NB_, false, true, false, 2>(a, d_args, stream, img); return launch_t<32, WM_, NB_, false, true>(a, d_args, stream, img); }
+#define EVR_CASE0(KC_, WM_, NB_, LSTM_, GROUPED_, REGSTAGE_) EVR_CASE(KC_, WM_, NB_, LSTM_, GROUPED_, REGSTAGE_, 0)      // the exact-fp32 kernels: this object only
 #else
-#define EVR_CASEG(WM_, NB_) if (kc == 32 && wm == WM_ && nb == NB_) { return launch_t<32, WM_, NB_, false, true, false, 2>(a, d_args, stream, img); }
+#define EVR_CASE0(KC_, WM_, NB_, LSTM_, GROUPED_, REGSTAGE_)
 #endif
+        EVR_CASE(32, 8, 4, true, false, true, 2) EVR_CASE(32, 4, 4, true, false, true, 2) EVR_CASE(32, 2, 4, true, false, false, 2) EVR_CASE(32, 1, 4, true, false, false, 2)
+        EVR_CASE0(32, 8, 4, true, false, false) EVR_CASE0(32, 4, 4, true, false, true) EVR_CASE0(32, 4, 4, true, false, false)
+        EVR_CASE0(32, 2, 4, true, false, false) EVR_CASE0(32, 1, 4, true, false, false)
+#define EVR_CASEG(WM_, NB_) EVR_CASE(32, WM_, NB_, false, true, false, 2) EVR_CASE0(32, WM_, NB_, false, true, false)      // transposed conv: column groups = sub-pixel phases
         EVR_CASEG(4, 4) EVR_CASEG(2, 4) EVR_CASEG(1, 4) EVR_CASEG(4, 2) EVR_CASEG(2, 2) EVR_CASEG(1, 2)
         EVR_CASEG(4, 1) EVR_CASEG(2, 1) EVR_CASEG(1, 1)
 #undef EVR_CASEG
-        set_error("conv_igemm: no grouped kernel for kc=%d wm=%d nb=%d", kc, wm, nb);
-        return EVR_ERR_UNSUPPORTED;
-    }
-    if (mode != 0) {
-#define EVR_CASEX(WM_, NB_) if (wm == WM_ && nb == NB_) return launch_t<32, WM_, NB_, false, false, false, 2>(a, d_args, stream, img);
+#define EVR_CASEX(WM_, NB_) EVR_CASE(32, WM_, NB_, false, false, false, 2)
         EVR_CASEX(4, 4) EVR_CASEX(2, 4) EVR_CASEX(1, 4) EVR_CASEX(4, 2) EVR_CASEX(2, 2) EVR_CASEX(1, 2)
         EVR_CASEX(4, 1) EVR_CASEX(2, 1) EVR_CASEX(1, 1)
 #undef EVR_CASEX
-    }
-#if EVR_ARITH == 2
-#define EVR_CASE(KC_, WM_, NB_) if (kc == KC_ && wm == WM_ && nb == NB_) return launch_t<KC_, WM_, NB_, false, false>(a, d_args, stream, img);
-    EVR_CASE(32, 4, 4) EVR_CASE(32, 2, 4) EVR_CASE(32, 1, 4)
-    EVR_CASE(32, 4, 2) EVR_CASE(32, 2, 2) EVR_CASE(32, 1, 2)
-    EVR_CASE(32, 4, 1) EVR_CASE(32, 2, 1) EVR_CASE(32, 1, 1)
-    EVR_CASE(16, 4, 1) EVR_CASE(16, 2, 1) EVR_CASE(16, 1, 1)
+        EVR_CASE0(32, 4, 4, false, false, false) EVR_CASE0(32, 2, 4, false, false, false) EVR_CASE0(32, 1, 4, false, false, false)
+        EVR_CASE0(32, 4, 2, false, false, false) EVR_CASE0(32, 2, 2, false, false, false) EVR_CASE0(32, 1, 2, false, false, false)
+        EVR_CASE0(32, 4, 1, false, false, false) EVR_CASE0(32, 2, 1, false, false, false) EVR_CASE0(32, 1, 1, false, false, false)
+        EVR_CASE0(16, 4, 1, false, false, false) EVR_CASE0(16, 2, 1, false, false, false) EVR_CASE0(16, 1, 1, false, false, false)
+#undef EVR_CASE0
 #undef EVR_CASE
-#endif
+        break;
+    }
     set_error("conv_igemm: no kernel for kc=%d wm=%d nb=%d", kc, wm, nb);
     return EVR_ERR_UNSUPPORTED;
 }

@@ -2,6 +2,7 @@
 // matrix-core forms), the standalone prediction layer, HyperE2VID's context / dynamic-filter kernels, bilinear upsample,
 // skip-sum, format conversion -- and the dispatcher over conv.hip's three compilations (ConvArgs::x3).
 #include "conv.h"
+#include "conv_route.h"
 #include "packed.h"
 #include <cstdlib>
 
@@ -48,7 +49,7 @@ void pick_conv_tile(const ConvArgs& a, int kc, int* wm, int* nb) {
         best = 4;
         while (best > 1 && ((M + 32 * best - 1) / (32 * best)) * ntiles < 512) best >>= 1;
     }
-    if (a.epi == EPI_LSTM && getenv("EVR_LSTM_WM8")) best = 8;   // experiment: 256x128 block tile
+    if (a.epi == EPI_LSTM && conv_knobs().lstm_wm8) best = 8;   // experiment: 256x128 block tile
     *wm = best; *nb = n_b;
 }
 
