@@ -1,5 +1,5 @@
-// Host set-up shared by the two LPIPS backbones (lpips.hip: AlexNet, lpips_vgg.hip: VGG-16): the state-dict lookup, the fold of
-// the LPIPS scaling layer into a one-channel first convolution, a backbone convolution prepared for the kernels of conv.hip and
+// Host set-up shared by the backbone metrics (lpips.hip: AlexNet, lpips_vgg.hip and dists.hip: VGG-16): the state-dict lookup, the fold of
+// the input scaling into a one-channel first convolution, a backbone convolution prepared for the kernels of conv.hip and
 // its ConvArgs, the per-pair-count plan cache, the split-K workspace and the device allocations of a handle.  Host code only;
 // every kernel stays in its backbone's file.
 #pragma once
@@ -43,13 +43,12 @@ struct DeviceAllocs {
     }
 };
 
-// The scaling layer of LPIPS folded into a first convolution (w [cout][3][taps], OIHW) that reads the gray frame: the three input
-// channels are x_c = ((2g-1) - shift_c)/scale_c = alpha_c * g + beta_c, so wg = sum_c w alpha_c and wb = sum_c w beta_c (both
-// [taps][cout], fp64 sums rounded once) make it a one-channel convolution plus the wb term where the window is inside the image;
-// b1in = bias + sum_t wb[t] is the bias of a window that lies wholly inside.
-inline void fold_scaling_layer(const float* w, const float* bias, int cout, int taps, std::vector<float>& wg, std::vector<float>& wb,
-                               std::vector<float>& b1, std::vector<float>& b1in) {
-    const double shift[3] = {-.030, -.088, -.188}, scale[3] = {.458, .448, .450};
+// An input scaling folded into a first convolution (w [cout][3][taps], OIHW) that reads the gray frame: the three input channels
+// are x_c = a_c * g + b_c, so wg = sum_c w a_c and wb = sum_c w b_c (both [taps][cout], fp64 sums rounded once) make it a
+// one-channel convolution plus the wb term where the window is inside the image; b1in = bias + sum_t wb[t] is the bias of a window
+// that lies wholly inside.
+inline void fold_scaling_layer(const float* w, const float* bias, int cout, int taps, const double (&a)[3], const double (&b)[3],
+                               std::vector<float>& wg, std::vector<float>& wb, std::vector<float>& b1, std::vector<float>& b1in) {
     wg.assign((size_t)taps * cout, 0.f); wb.assign((size_t)taps * cout, 0.f);
     b1.assign(bias, bias + cout); b1in.assign(cout, 0.f);
     for (int co = 0; co < cout; ++co) {
@@ -58,13 +57,21 @@ inline void fold_scaling_layer(const float* w, const float* bias, int cout, int 
             double g = 0.0, bb = 0.0;
             for (int c = 0; c < 3; ++c) {
                 const double wv = w[((size_t)co * 3 + c) * taps + t];
-                g += wv * (2.0 / scale[c]); bb += wv * ((-1.0 - shift[c]) / scale[c]);
+                g += wv * a[c]; bb += wv * b[c];
             }
             wg[(size_t)t * cout + co] = (float)g; wb[(size_t)t * cout + co] = (float)bb;
             bsum += bb;
         }
         b1in[co] = (float)((double)b1[co] + bsum);
     }
+}
+// The scaling layer of LPIPS: x_c = ((2g-1) - shift_c)/scale_c
+inline void fold_scaling_layer(const float* w, const float* bias, int cout, int taps, std::vector<float>& wg, std::vector<float>& wb,
+                               std::vector<float>& b1, std::vector<float>& b1in) {
+    const double shift[3] = {-.030, -.088, -.188}, scale[3] = {.458, .448, .450};
+    double a[3], b[3];
+    for (int c = 0; c < 3; ++c) { a[c] = 2.0 / scale[c]; b[c] = (-1.0 - shift[c]) / scale[c]; }
+    fold_scaling_layer(w, bias, cout, taps, a, b, wg, wb, b1, b1in);
 }
 
 // arithmetic of the backbone convolutions: the networks' mode, except that P6 tensors (mode 4) have no 4-channel writer -- the

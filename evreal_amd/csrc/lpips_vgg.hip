@@ -12,7 +12,7 @@
 // and lin{0..4}.model.1.weight (64, 128, 256, 512, 512 elements), and the pool positions (torchvision indices 4, 9, 16, 23).
 // Scores agree with the restatement tests/lpips_vgg_ref.py on any weights, and with pyiqa only once its weights are supplied.
 //
-// Layers: conv1_1 (3->64) is a direct VALU kernel on the gray input (the three input channels are affine in the same gray value);
+// Layers: conv1_1 (3->64) is a direct VALU kernel on the gray input (vgg_backbone.h, shared with dists.hip; the three input channels are affine in the same gray value);
 // the other twelve 3x3 convolutions run on the convolution kernels of conv.hip through the set-up both backbones share (lpips_host.h; split
 // arithmetic: every activation tensor is PACKED / H2; fp32 mode: PLAIN, Winograd where eligible); one streaming kernel per tap
 // layer scores it and writes the 2x2 max pool of both images' features -- the 64-channel full-resolution tensor is read once.
@@ -29,6 +29,7 @@
 #include "conv.h"
 #include "lpips_host.h"
 #include "packed.h"
+#include "vgg_backbone.h"
 
 using namespace evr;
 
@@ -40,119 +41,8 @@ constexpr size_t ACT_BUDGET_BYTES = (size_t)1 << 30;      // both activation buf
 // a frame whose single pair does not fit (H*W >= 2^22) is refused
 constexpr int64_t ACT_BUFFER_MAX_BYTES = (int64_t)1 << 31;
 constexpr int MIN_SIDE = 16;                               // four floor-mode 2x2 pools must leave one pixel
-constexpr int NCONV = 12;                                  // convolutions on conv.hip (conv1_2 .. conv5_3)
-constexpr int VGG_CIN[NCONV] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
-constexpr int VGG_COUT[NCONV] = {64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
-constexpr int VGG_LEVEL[NCONV] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4};      // resolution level: H >> level (floor at every pool)
-constexpr int TAP_C[5] = {64, 128, 256, 512, 512};
-
-// ---- conv1_1: gray [n2,H,W] -> [n2,H,W,64], 3x3 pad 1, relu ---------------------------------------------------------
-// x_c = ((2g-1) - shift_c)/scale_c = alpha_c*g + beta_c inside the image and 0 where the convolution pads, so
-//   sum_c sum_t w[co][c][t] x_c[t] = sum_t inside[t] * (wg[t][co]*g[t] + wb[t][co])
-// with wg = sum_c w*alpha_c, wb = sum_c w*beta_c folded on the host in fp64: a ONE-channel 3x3 convolution plus, for pixels on
-// the image border, the wb term under the inside mask; interior pixels take sum_t wb[t] from the bias.
-// A thread owns 16 consecutive channels (one 64-B group of the output row: four 16-B stores in every format) of two pixels in
-// a row; the 2 x 9 x 64 folded weights sit in LDS (a lane reads the 16-B slots of its group: four distinct addresses per wave).
-struct Conv11Args {
-    const float* img; const float* ref;   // [n,H,W] each; batch index >= n reads ref
-    int n, H, W, clip;
-    const float* wg;                       // [9][64]
-    const float* wb;                       // [9][64]
-    const float* bias;                     // [64]
-    const float* bias_in;                  // [64] bias + sum_t wb[t]  (interior pixels)
-    float* out;
-    unsigned* sat;
-};
-
-constexpr int C11_PX = 2;      // pixels per thread (four: 172 registers, two waves per SIMD)
-template <int FMT>
-__global__ __launch_bounds__(256) void vgg_conv1_1_kernel(const Conv11Args a) {
-    constexpr int PX = C11_PX;
-    __shared__ __attribute__((aligned(16))) float s_w[2 * 9 * 64];      // wg | wb
-    for (int i = threadIdx.x; i < 2 * 9 * 64; i += 256) s_w[i] = i < 576 ? a.wg[i] : a.wb[i - 576];
-    __syncthreads();
-    const int wq = (a.W + PX - 1) / PX;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)2 * a.n * a.H * wq * 4) return;
-    const int g = (int)(i & 3); int64_t p = i >> 2;
-    const int x0 = (int)(p % wq) * PX; p /= wq;
-    const int y = (int)(p % a.H);
-    const int b = (int)(p / a.H);
-    const float* src = (b < a.n ? a.img + (int64_t)b * a.H * a.W : a.ref + (int64_t)(b - a.n) * a.H * a.W);
-    // the 3 x (PX + 2) gray window of the thread's pixels (0 outside the image); inside mask = rowm x colm
-    float gv[3][PX + 2], rowm[3], colm[PX + 2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) rowm[r] = (unsigned)(y + r - 1) < (unsigned)a.H ? 1.f : 0.f;
-#pragma unroll
-    for (int c = 0; c < PX + 2; ++c) colm[c] = (unsigned)(x0 + c - 1) < (unsigned)a.W ? 1.f : 0.f;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < PX + 2; ++c) {
-            const int yy = y + r - 1, xx = x0 + c - 1;
-            float v = 0.f;
-            if ((unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W) {
-                v = src[(int64_t)yy * a.W + xx];
-                if (a.clip) v = fminf(fmaxf(v, 0.f), 1.f);
-            }
-            gv[r][c] = v;
-        }
-    const bool interior = y >= 1 && y + 1 < a.H && x0 >= 1 && x0 + PX < a.W;      // every tap of the thread's pixels is inside
-    float acc[PX][16];
-    {
-        const float4* bp = (const float4*)((interior ? a.bias_in : a.bias) + 16 * g);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 bv = bp[q];
-#pragma unroll
-            for (int px = 0; px < PX; ++px) { acc[px][4 * q] = bv.x; acc[px][4 * q + 1] = bv.y; acc[px][4 * q + 2] = bv.z; acc[px][4 * q + 3] = bv.w; }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        const int ky = t / 3, kx = t % 3;
-        float w[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 wv = *(const float4*)(s_w + t * 64 + 16 * g + 4 * q);
-            w[4 * q] = wv.x; w[4 * q + 1] = wv.y; w[4 * q + 2] = wv.z; w[4 * q + 3] = wv.w;
-        }
-#pragma unroll
-        for (int px = 0; px < PX; ++px)
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc[px][k] = fmaf(gv[ky][px + kx], w[k], acc[px][k]);
-        if (!interior) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 wv = *(const float4*)(s_w + 576 + t * 64 + 16 * g + 4 * q);
-                w[4 * q] = wv.x; w[4 * q + 1] = wv.y; w[4 * q + 2] = wv.z; w[4 * q + 3] = wv.w;
-            }
-#pragma unroll
-            for (int px = 0; px < PX; ++px) {
-                const float mk = rowm[ky] * colm[px + kx];
-#pragma unroll
-                for (int k = 0; k < 16; ++k) acc[px][k] = fmaf(mk, w[k], acc[px][k]);
-            }
-        }
-    }
-#pragma unroll
-    for (int px = 0; px < PX; ++px) {
-        if (x0 + px >= a.W) continue;
-        float* o = a.out + (((int64_t)b * a.H + y) * a.W + x0 + px) * 64;
-        float v[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) v[k] = fmaxf(acc[px][k], 0.f);
-        if constexpr (FMT == 0) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) *(float4*)(o + 16 * g + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-        } else {
-#if defined(__HIP_DEVICE_COMPILE__)
-            sat_check16<FMT>(a.sat, v);
-            store16_fmt<FMT>(o, 0u, 16 * g, v);
-#endif
-        }
-    }
-}
+constexpr int NCONV = VGG_NCONV;      // (the tables of the trunk and conv1_1: vgg_backbone.h)
+constexpr const int* TAP_C = VGG_TAP_C;
 
 // ---- one tap layer: LPIPS partial sums + the 2x2 max pool of both images' features -------------------------------------
 // feat: [2n, h, w, C] (first n = img, last n = ref) in format `fmt`; pooled: [2n, h/2, w/2, C] in the same format, or null
@@ -375,30 +265,16 @@ static int vgg_buffers(evr_lpips_vgg* m, int cap, int H, int W, hipStream_t stre
     return EVR_OK;
 }
 
-// input / output buffer of convolution i (0 = conv1_2): conv1_1 writes act[0]; every convolution and every pool flips
-static int conv_src(int i) {
-    // ops in order: conv1_1 (-> 0), then per convolution one flip, plus one flip per pool in front of it
-    return (1 + i + VGG_LEVEL[i]) & 1 ? 0 : 1;
-}
-
 // the plan of n pairs inside the current buffers (PlanCache::get fills a slot with this)
 static void vgg_fill_plan(evr_lpips_vgg* m, PlanCache<NCONV>::Plan& pl, int n) {
     for (int i = 0; i < NCONV; ++i) {
         ConvArgs& a = pl.args[i];
-        const int lv = VGG_LEVEL[i], src = conv_src(i);
+        const int lv = VGG_LEVEL[i], src = vgg_conv_src(i);
         fill_backbone_conv(a, m->L[i], m->act[src], m->act[src ^ 1], 2 * n, m->h[lv], m->w[lv]);
         a.sat = m->d_sat;
         pick_conv_tile(a, 32, &pl.wm[i], &pl.nb[i]);
     }
     attach_split_workspace(m->kws, m->allocs, pl.args, NCONV, 0);
-}
-
-template <int FMT>
-static int launch_conv1_1(const Conv11Args& c, hipStream_t stream) {
-    const int64_t total = (int64_t)2 * c.n * c.H * ((c.W + C11_PX - 1) / C11_PX) * 4;
-    hipLaunchKernelGGL(vgg_conv1_1_kernel<FMT>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, c);
-    EVR_LAUNCH_CHECK();
-    return EVR_OK;
 }
 
 // one pass: np pairs starting at img / ref, scores to out[0..np) (and out_layers[0..5 np))
@@ -411,14 +287,14 @@ static int vgg_pass(evr_lpips_vgg* m, const float* img, const float* ref, int np
     Conv11Args c1{};
     c1.img = img; c1.ref = ref; c1.n = np; c1.H = m->H; c1.W = m->W; c1.clip = clip;
     c1.wg = m->d_wg; c1.wb = m->d_wb; c1.bias = m->d_b1; c1.bias_in = m->d_b1in; c1.out = m->act[0]; c1.sat = m->d_sat;
-    if ((rc = fmt == 2 ? launch_conv1_1<2>(c1, stream) : fmt == 1 ? launch_conv1_1<1>(c1, stream) : launch_conv1_1<0>(c1, stream))) return rc;
+    if ((rc = launch_conv1_1_fmt(fmt, c1, stream))) return rc;
     FinalArgs fa{};
     int ci = 0;
     for (int l = 0; l < 5; ++l) {
         for (; ci < NCONV && VGG_LEVEL[ci] == l; ++ci)
             if ((rc = launch_conv_igemm(P->args[ci], d_args + ci, 32, P->wm[ci], P->nb[ci], stream))) return rc;
         // the tap layer sits where the level's last convolution wrote it; its pool goes to the other buffer
-        const int src = conv_src(ci - 1) ^ 1;
+        const int src = vgg_conv_src(ci - 1) ^ 1;
         TapArgs t{};
         t.feat = m->act[src]; t.pooled = l < 4 ? m->act[src ^ 1] : nullptr; t.lin = m->d_lin[l];
         t.n = np; t.h = m->h[l]; t.w = m->w[l]; t.C = TAP_C[l]; t.fmt = fmt;

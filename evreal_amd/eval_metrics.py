@@ -8,8 +8,8 @@ Frames arrive in batches; gating (start/end time, |ref_ts-img_ts| <= ts_tol_ms, 
 Metric plug-ins keep the reference's contract (utils/eval_metrics.py:18-75): a `BaseMetric` subclass with `name`,
 `no_ref`, `calculate(img, ref) -> float | list`, `finish_queue()`, `reset()`.  Three kinds live side by side:
   * the GPU metrics of `_SCORERS` below run batched, one launch set per scorer: 'mse', 'ssim' and 'lpips' are booked frame by
-    frame; the others ('lpips-vgg', 'psnr', 'ms_ssim', 'gmsd', 'niqe', 'brisque', 'piqe') through the four-frame queue of the
-    reference's pyiqa metrics, so their files hold the same lines.  'lpips', 'lpips-vgg', 'niqe' and 'brisque' need a weights or
+    frame; the others ('lpips-vgg', 'dists', 'psnr', 'ms_ssim', 'gmsd', 'niqe', 'brisque', 'piqe') through the four-frame queue of the
+    reference's pyiqa metrics, so their files hold the same lines.  'lpips', 'lpips-vgg', 'dists', 'niqe' and 'brisque' need a weights or
     model file; 'psnr' / 'ms_ssim', 'piqe' and 'gmsd' need none and have a switch (EVREAL_GPU_FR_METRICS, EVREAL_GPU_PIQE,
     EVREAL_GPU_GMSD: '0' sends the name to pyiqa instead);
   * anything registered with `register_metric(name, factory)` runs per frame on host arrays, exactly like the reference's
@@ -31,7 +31,7 @@ from os.path import join
 import numpy as np
 import torch
 
-from .lpips import LPIPSVGG
+from .lpips import DISTS, LPIPSVGG
 from .prepost import GMSD, FullRefMetrics, Metrics, histogram_equalization
 
 DEFAULT_METRICS = ('mse', 'ssim', 'lpips')      # the reference's default (eval.py:413-445, utils/eval_metrics.py:171)
@@ -42,6 +42,7 @@ PIQE_ENV = 'EVREAL_GPU_PIQE'                    # '0': piqe goes to pyiqa (or is
 GMSD_ENV = 'EVREAL_GPU_GMSD'                    # '0': gmsd goes to pyiqa (or is unknown without it)
 LPIPS_WEIGHTS_ENV = 'EVREAL_LPIPS_WEIGHTS'      # path to a pyiqa/lpips AlexNet-v0.1 state_dict (torch.save'd)
 LPIPS_VGG_WEIGHTS_ENV = 'EVREAL_LPIPS_VGG_WEIGHTS'      # path to a pyiqa lpips-vgg (VGG-16, v0.1) state_dict (torch.save'd)
+DISTS_WEIGHTS_ENV = 'EVREAL_DISTS_WEIGHTS'      # path to a pyiqa dists state_dict (torch.save'd)
 NIQE_MODEL_ENV = 'EVREAL_NIQE_MODEL'            # path to a NIQE pristine model (.mat of the MATLAB release, or .npz)
 NIQE_MODEL_FILES = (os.path.join('pretrained', 'niqe_modelparameters.mat'), os.path.join('pretrained', 'niqe_model.npz'))
 BRISQUE_MODEL_ENV = 'EVREAL_BRISQUE_MODEL'      # path to a BRISQUE model (.npz, or a libsvm text model such as allmodel)
@@ -67,6 +68,16 @@ def _load_lpips_vgg():
               "offline they must be provided) -> falling back to pyiqa if it is installed")
         return None
     return LPIPSVGG(torch.load(path, map_location='cpu', weights_only=False))
+
+
+def _load_dists():
+    """As _load_lpips: made where pyiqa exists by torch.save(pyiqa.create_metric('dists').net.state_dict(), path)."""
+    path = os.environ.get(DISTS_WEIGHTS_ENV, os.path.join('pretrained', 'dists.pth'))
+    if not os.path.exists(path):
+        print(f"dists: no weights at ${DISTS_WEIGHTS_ENV} or pretrained/dists.pth (pyiqa downloads them; "
+              "offline they must be provided) -> falling back to pyiqa if it is installed")
+        return None
+    return DISTS(torch.load(path, map_location='cpu', weights_only=False))
 
 
 def gpu_fr_metrics_enabled():
@@ -349,6 +360,9 @@ _SCORERS = (
     _GpuScorer({'lpips-vgg': 0}, 1, lambda t: t._cached('_lpips_vgg_cache'), before_registry=True,
                too_small=lambda name, H, W: LPIPSVGG.too_small(H, W),
                run=lambda h, img, ref, names, out: h(img, ref, clip=True, out=out[:, 0])),
+    _GpuScorer({'dists': 0}, 1, lambda t: t._cached('_dists_cache'), before_registry=True,
+               too_small=lambda name, H, W: DISTS.too_small(H, W),
+               run=lambda h, img, ref, names, out: h(img, ref, clip=True, out=out[:, 0])),
     _GpuScorer({'niqe': 0}, 1, lambda t: t._cached('_niqe_cache'), _run_no_ref, no_ref=True, before_registry=True),
     _GpuScorer({'brisque': 0}, 1, lambda t: t._cached('_brisque_cache'), _run_no_ref, no_ref=True, before_registry=True),
     _GpuScorer({'piqe': 0}, 1, lambda t: t._cached('_piqe_cache'), _run_no_ref, no_ref=True, enabled=gpu_piqe_enabled),
@@ -412,10 +426,12 @@ class EvalMetricsTracker:
 
     # One handle per process and name: [loaded, handle or None], filled at the first request of the name (None without a weights
     # or model file: the name then goes to its other providers).  Tests put stand-ins here, and in _lpips_model.
-    _LOADERS = {'_lpips_cache': _load_lpips, '_lpips_vgg_cache': _load_lpips_vgg, '_niqe_cache': _load_niqe,
+    _LOADERS = {'_lpips_cache': _load_lpips, '_lpips_vgg_cache': _load_lpips_vgg, '_dists_cache': _load_dists,
+                '_niqe_cache': _load_niqe,
                 '_brisque_cache': _load_brisque, '_piqe_cache': _load_piqe}
     _lpips_cache = [False, None]
     _lpips_vgg_cache = [False, None]
+    _dists_cache = [False, None]
     _niqe_cache = [False, None]
     _brisque_cache = [False, None]
     _piqe_cache = [False, None]
@@ -489,7 +505,7 @@ class EvalMetricsTracker:
         return [m.name for m in self.metrics if getattr(m, 'on_gpu', False)]
 
     def _shape_refused(self, m, imgs):
-        """A GPU metric that is not defined on frames of this size (ms_ssim below 161 pixels a side, gmsd below 2, lpips-vgg below 16) ends like a metric that
+        """A GPU metric that is not defined on frames of this size (ms_ssim below 161 pixels a side, gmsd below 2, lpips-vgg and dists below 16) ends like a metric that
         raises on every frame in the reference (utils/eval_metrics.py:233-242: the exception is printed, the metric reset): its
         file stays empty and its mean is -1.  Decided from the shape, before any launch, and printed once per sequence."""
         if m.name in self._failed:
@@ -678,7 +694,8 @@ class EvalMetricsTracker:
         """eval_metrics.py:225-228: flush the queued metrics; then wait for this tracker's files.  wait_png=False (the drop-in's
         sequence loops): the native writers keep working on this tracker's last frames while the next sequence starts; the caller
         owes a wait_all_pngs() before it reports the dataset (evreal_amd.eval does it per dataset) -- 3 ms per 160-frame sequence."""
-        self._warn_lpips_vgg_range()
+        self._warn_backbone_range('lpips-vgg', self._lpips_vgg_cache)
+        self._warn_backbone_range('dists', self._dists_cache)
         for m in self.metrics:
             if isinstance(m, QueuedGpuMetric):
                 m.finish_queue()
@@ -701,19 +718,20 @@ class EvalMetricsTracker:
             self._wait_native()                              # ... and a native writer's failure here
         self._close_files()
 
-    def _warn_lpips_vgg_range(self):
-        """One line per sequence when an activation of the VGG trunk left the exact range of the arithmetic mode's packed format
-        (the handle's counter, read and cleared here: it is shared by the trackers of a process, so sequences evaluated in lock-step
-        report together with the first of them that finishes).  The scores are kept; EVR_ARITH=fp32 computes them without a limit."""
+    def _warn_backbone_range(self, name, cache):
+        """One line per sequence when an activation of the VGG trunk of `name` ('lpips-vgg', 'dists') left the exact range of the
+        arithmetic mode's packed format (the handle's counter, read and cleared here: it is shared by the trackers of a process, so
+        sequences evaluated in lock-step report together with the first of them that finishes).  The scores are kept;
+        EVR_ARITH=fp32 computes them without a limit."""
         # (only this project's GPU metric: the same name served by pyiqa or by register_metric has no handle)
-        if not any(m.name == 'lpips-vgg' and getattr(m, 'on_gpu', False) for m in self.metrics):
+        if not any(m.name == name and getattr(m, 'on_gpu', False) for m in self.metrics):
             return
-        model = self._lpips_vgg_cache[1]
-        if model is None or 'lpips-vgg' in self._failed or not self.quan_eval_indices:
+        model = cache[1]
+        if model is None or name in self._failed or not self.quan_eval_indices:
             return
         count = model.saturation()
         if count:
-            print(f"WARNING: lpips-vgg: {count} activation runs left the exact range of the packed format in {self.output_dir} "
+            print(f"WARNING: {name}: {count} activation runs left the exact range of the packed format in {self.output_dir} "
                   "(scores kept; EVR_ARITH=fp32 evaluates without the limit)")
 
     @classmethod

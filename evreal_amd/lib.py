@@ -87,6 +87,11 @@ SYMBOLS = {
     'evr_lpips_vgg_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'evr_lpips_vgg_flops': (c_double, [c_void_p]),
     'evr_lpips_vgg_saturation': (c_int, [c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    'evr_dists_create': (c_int, [ctypes.POINTER(Tensor), c_int, c_int, ctypes.POINTER(c_void_p)]),
+    'evr_dists_destroy': (c_int, [c_void_p]),
+    'evr_dists_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'evr_dists_flops': (c_double, [c_void_p]),
+    'evr_dists_saturation': (c_int, [c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     'evr_niqe_create': (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
     'evr_niqe_destroy': (c_int, [c_void_p]),
     'evr_niqe_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),

@@ -24,7 +24,7 @@ def _tensor_table(state_dict):
 
 
 class _Backbone:
-    """What the two LPIPS handles share: `_entry` is the prefix of the backbone's C entry points."""
+    """What the backbone handles (LPIPS, LPIPSVGG, DISTS) share: `_entry` is the prefix of the backbone's C entry points."""
     _entry = None
 
     def _create(self, state_dict, *args):
@@ -115,4 +115,51 @@ class LPIPSVGG(_Backbone):
         cleared); waits for the current stream."""
         c = ctypes.c_int64(0)
         _lib.check(self.lib.evr_lpips_vgg_saturation(self.handle, ctypes.byref(c), _lib.stream_ptr()), 'evr_lpips_vgg_saturation')
+        return int(c.value)
+
+
+class DISTS(_Backbone):
+    """pyiqa.create_metric('dists') stand-in on the GPU (evr_dists_*): same call shape as LPIPSVGG, on the same VGG-16 trunk.
+
+    max_pairs: frame pairs per pass (0: as many as keep the handle's two activation buffers within 1 GiB); a call with more pairs
+    runs in passes."""
+    _entry = 'evr_dists'
+    MIN_SIDE = 16           # the backbone's kernels run down to the 1x1 maps of a 16x16 frame (pyiqa would accept smaller frames)
+
+    def __init__(self, state_dict, max_pairs=0):
+        self._create(state_dict, int(max_pairs))
+
+    @classmethod
+    def too_small(cls, H, W):
+        """The message of the exception `dists` raises on frames of this size, or None where it is defined."""
+        if min(H, W) >= cls.MIN_SIDE:
+            return None
+        return f"dists needs frames of at least {cls.MIN_SIDE}x{cls.MIN_SIDE} pixels on this VGG-16 trunk, got {H}x{W}"
+
+    def _forward(self, img, ref, clip, out, stages):
+        img, ref, out = self._inputs(img, ref, out)
+        assert img.dtype == ref.dtype == torch.float32
+        n, H, W = img.shape
+        if self.too_small(H, W):
+            raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n
+        _lib.check(self.lib.evr_dists_forward(self.handle, _lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0,
+                                              _lib.ptr(out), _lib.ptr(stages), _lib.stream_ptr()), 'evr_dists_forward')
+        return out
+
+    def __call__(self, img, ref, clip=True, out=None):
+        """img, ref: cuda fp32 [n,H,W] in [0,1] -> double [n] on device: 1 - (D1 + D2)."""
+        return self._forward(img, ref, clip, out, None)
+
+    def stages(self, img, ref, clip=True):
+        """-> double [n,6,2]: the structure ([..., 0]) and texture ([..., 1]) distances of the six feature sets -- the input, relu1_2,
+        relu2_2, relu3_3, relu4_3, relu5_3; their sum is the score up to rounding."""
+        stages = torch.empty((img.shape[0], 6, 2), dtype=torch.float64, device=img.device)
+        self._forward(img, ref, clip, None, stages)
+        return stages
+
+    def saturation(self):
+        """As LPIPSVGG.saturation()."""
+        c = ctypes.c_int64(0)
+        _lib.check(self.lib.evr_dists_saturation(self.handle, ctypes.byref(c), _lib.stream_ptr()), 'evr_dists_saturation')
         return int(c.value)

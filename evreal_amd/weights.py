@@ -241,6 +241,39 @@ def synth_lpips_vgg_state_dict(seed=0):
     return sd
 
 
+def dists_schema():
+    """State dict of pyiqa's DISTS: the thirteen 3x3 convolutions of torchvision's vgg16.features under their indices there, grouped
+    into the five stages that end at relu1_2, relu2_2, relu3_3, relu4_3, relu5_3, + alpha and beta over the 3 + 64 + 128 + 256 + 512 +
+    512 = 1475 channels of the six feature sets.  (The published state dict also carries the buffers mean, std and the pools'
+    filters; the first two are optional here, the filters are ignored.)  The names are recalled from the published code and stay
+    unpinned until tests/test_dists_pins.py has run."""
+    s = OrderedDict()
+    for name, co, ci in [("stage1.0", 64, 3), ("stage1.2", 64, 64), ("stage2.5", 128, 64), ("stage2.7", 128, 128),
+                         ("stage3.10", 256, 128), ("stage3.12", 256, 256), ("stage3.14", 256, 256),
+                         ("stage4.17", 512, 256), ("stage4.19", 512, 512), ("stage4.21", 512, 512),
+                         ("stage5.24", 512, 512), ("stage5.26", 512, 512), ("stage5.28", 512, 512)]:
+        _conv(s, name, co, ci, 3)
+    s['alpha'] = (1, 1475, 1, 1)
+    s['beta'] = (1, 1475, 1, 1)
+    return s
+
+
+def synth_dists_state_dict(seed=0):
+    """Deterministic stand-in for the (offline-unobtainable) DISTS weights: the conv gain of synth_lpips_vgg_state_dict; alpha and
+    beta ~ U(0.05, 1), with the three entries of the input's feature set scaled so that the set carries 5 % of sum(alpha) + sum(beta)
+    (with plain draws its 3 of 1475 channels would vanish below every tolerance)."""
+    sd = synth_state_dict(dists_schema(), seed=seed, gain=float(np.sqrt(2.0)))
+    for k in ('alpha', 'beta'):
+        rng = np.random.default_rng([seed, zlib.crc32(k.encode()), 1])
+        sd[k] = rng.uniform(0.05, 1.0, sd[k].shape).astype(np.float32)
+    rest = float(sd['alpha'][0, 3:].astype(np.float64).sum() + sd['beta'][0, 3:].astype(np.float64).sum())
+    first = float(sd['alpha'][0, :3].astype(np.float64).sum() + sd['beta'][0, :3].astype(np.float64).sum())
+    scale = 0.05 / 0.95 * rest / first
+    for k in ('alpha', 'beta'):
+        sd[k][0, :3] = (sd[k][0, :3].astype(np.float64) * scale).astype(np.float32)
+    return sd
+
+
 def synth_state_dict(schema, seed=0, gain=1.0, fixed=None):
     """Deterministic fp32 numpy weights for a schema.  Each tensor is drawn from its own
     PCG64 stream keyed by (seed, crc32(name)) so adding/removing tensors never shifts the

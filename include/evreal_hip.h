@@ -328,6 +328,27 @@ double evr_lpips_vgg_flops(const evr_lpips_vgg* m);
 int evr_lpips_vgg_saturation(evr_lpips_vgg* m, int64_t* count, evr_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * DISTS (Ding, Ma, Wang, Simoncelli 2020).  Replaces PyIqaMetricFactory.get_metric('dists'), called like 'lpips-vgg' above.
+ * tensors: the metric's state_dict with pyiqa's names: the thirteen convolutions "stage1.{0,2}", "stage2.{5,7}",
+ * "stage3.{10,12,14}", "stage4.{17,19,21}", "stage5.{24,26,28}" (".weight", ".bias"), "alpha" and "beta" (1475 elements each, positive),
+ * optionally "mean" and "std" (3 elements each; else the ImageNet constants); other tensors (the pools' "filter" buffers) are ignored.
+ * img, ref: [n,H,W] in [0,1] (clip: clamp first), H and W at least 16 and H * W below 2^22; out: double [n] = 1 - (D1 + D2);
+ * out_stages: double [n,6,2] or null: [b][k][0] = sum over the channels of feature set k (the input, relu1_2 ... relu5_3) of
+ * (alpha_c / w)(1 - S1_c), [b][k][1] the same with beta and S2 -- every set's structure and texture distance; their sum is out up to
+ * rounding.  PARITY UNPINNED: pyiqa and its downloaded weights are unavailable offline; the names above and the conventions are
+ * recalled from the published code (csrc/dists.hip).
+ * Buffers, passes, max_pairs, the plan cache and evr_dists_saturation: as evr_lpips_vgg_* above.  A pair's score does not depend on
+ * n or on its place in the batch beyond what the convolutions' split-K choice does to their sums.
+ */
+typedef struct evr_dists evr_dists;
+int evr_dists_create(const evr_tensor* tensors, int n_tensors, int max_pairs, evr_dists** out);
+int evr_dists_destroy(evr_dists* m);
+int evr_dists_forward(evr_dists* m, const float* img, const float* ref, int n, int H, int W, int clip,
+                      double* out, double* out_stages, evr_stream_t stream);
+double evr_dists_flops(const evr_dists* m);
+int evr_dists_saturation(evr_dists* m, int64_t* count, evr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * NIQE (Mittal, Soundararajan, Bovik 2013), the no-reference score of `-qm niqe` for datasets without frames
  * (utils/eval_metrics.py:100-156 -> pyiqa), after the published MATLAB release.  Conventions (tests/nriqa_ref.py):
  * u = rint(255 * v) in fp32 (v clamped to [0,1] first when clip != 0), fp64 from there on; the frame is cropped to whole
