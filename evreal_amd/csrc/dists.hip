@@ -18,9 +18,10 @@
 // optional buffers mean and std (used when present), the pools' stageK.N.filter buffers (ignored), and everything above.
 // Scores agree with the restatement tests/dists_ref.py on any weights, and with pyiqa only once its weights are supplied.
 //
-// Layers: the thirteen convolutions are LPIPS-VGG's -- conv1_1 is the direct kernel of vgg_backbone.h on the gray frame with
-// DISTS's normalisation folded in (lpips_host.h fold_scaling_layer), the other twelve run on conv.hip through the set-up of
-// lpips_host.h in the process's arithmetic (activations PACKED / H2 in the split modes, PLAIN in fp32).  New here:
+// Layers: the thirteen convolutions are LPIPS-VGG's, kernels (vgg_backbone.h) and host side (vgg_trunk.h: the handle holds a VggTrunk,
+// here with ceil-mode level sizes) -- conv1_1 is the direct kernel on the gray frame with DISTS's normalisation folded in (lpips_host.h
+// fold_scaling_layer), the other twelve run on conv.hip in the process's arithmetic (activations PACKED / H2 in the split modes, PLAIN
+// in fp32).  This file's own: the state-dict names, mean / std, alpha / beta, the head buffers and
 //   dists_stat_pool_kernel, one launch per stage: the five sums (fx, fy, fx^2, fy^2, fx fy) of every channel and, for stages 1-4,
 //     the L2 pool of both frames into the other ping-pong buffer;
 //   dists_gray_kernel: the five sums of the gray frames themselves (feature set 0: its three channels are equal, so one S1 and one
@@ -31,7 +32,7 @@
 // map's variance and covariance cancel exactly) and are added in an order that depends on the stage's shape only: no atomics, and
 // the block count per pair does not depend on the number of pairs.
 //
-// Memory plan: as lpips_vgg.hip -- features are not kept: two ping-pong activation buffers sized for relu1_2, 2*P*H*W*64*4 B each
+// Memory plan (vgg_trunk.h): as lpips_vgg.hip -- features are not kept: two ping-pong activation buffers sized for relu1_2, 2*P*H*W*64*4 B each
 // for P pairs per pass, P chosen so that both fit ACT_BUDGET_BYTES (at least 1; `max_pairs` at create overrides it); a call with
 // more pairs runs in passes.
 //
@@ -47,20 +48,16 @@
 #include <vector>
 
 #include "conv.h"
-#include "lpips_host.h"
 #include "packed.h"
-#include "vgg_backbone.h"
+#include "vgg_trunk.h"
 
 using namespace evr;
 
 namespace {
 
-constexpr size_t ACT_BUDGET_BYTES = (size_t)1 << 30;      // both activation buffers of a handle together (default pass size)
-constexpr int64_t ACT_BUFFER_MAX_BYTES = (int64_t)1 << 31;      // one buffer (the reasons: lpips_vgg.hip)
 // the backbone's kernels have only ever run down to the 1x1 maps of a 16x16 frame (the published metric accepts smaller frames)
 constexpr int MIN_SIDE = 16;
-constexpr int NCONV = VGG_NCONV;
-constexpr int NSETS = 6;                                  // feature sets: the input, then the five stages
+constexpr int NSETS = 6;                                 // feature sets: the input, then the five stages
 constexpr int NCH = 3 + 64 + 128 + 256 + 512 + 512;       // 1475
 constexpr int STAT_BLOCKS_MAX = 256;                      // work-groups per pair and 256-channel chunk of the statistics kernel
 constexpr int GRAY_BLOCKS_MAX = 32;
@@ -320,62 +317,43 @@ int gray_blocks(int hw) {
 }  // namespace
 
 struct evr_dists {
-    std::vector<float> wg, wb, b1, b1in;
-    float* d_wg = nullptr; float* d_wb = nullptr; float* d_b1 = nullptr; float* d_b1in = nullptr;
+    VggTrunk trunk;
     double* d_ab = nullptr;          // alpha / w [1475] | beta / w [1475]
-    unsigned* d_sat = nullptr;       // range guard of the packed formats (packed.h sat_note): every producer of this handle counts here
-    BackboneConv L[NCONV];
-    int mode = 0;                    // arithmetic of the twelve convolutions (lpips_host.h backbone_mode)
-    int max_pairs = 0;               // constructor argument: pairs per pass (0: from ACT_BUDGET_BYTES)
-    // shape-dependent (as evr_lpips_vgg): buffers sized for `cap` pairs per pass at H x W, plans per pair count in the cache
-    int n = 0, H = 0, W = 0, cap = 0;
-    int h[5], w[5];                  // feature map sizes of the five stages (ceil at every pool)
     int blocks[5], gblocks = 0;      // work-groups per pair of the statistics launches
-    DeviceAllocs allocs;
-    float* act[2] = {nullptr, nullptr};
-    PlanCache<NCONV> plans;
-    SplitWorkspace kws;
+    // of trunk.allocs:
     double* partials[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // [cap][blocks][C][5]
     double* gray = nullptr;          // [cap][gblocks][5]
     double* terms = nullptr;         // [cap][NCHUNK][4]
     void release() {
-        allocs.release();
-        cap = 0; plans.clear(); kws = SplitWorkspace(); act[0] = act[1] = nullptr; gray = nullptr; terms = nullptr;
+        trunk.release();
+        gray = nullptr; terms = nullptr;
         for (auto& p : partials) p = nullptr;
     }
-    ~evr_dists() {
-        release();
-        if (d_wg) (void)hipFree(d_wg); if (d_wb) (void)hipFree(d_wb); if (d_b1) (void)hipFree(d_b1); if (d_b1in) (void)hipFree(d_b1in);
-        if (d_ab) (void)hipFree(d_ab);
-        if (d_sat) (void)hipFree(d_sat);
-        for (auto& l : L) free_backbone_conv(l);
+    // (vgg_forward) the trunk's buffers with ceil-mode pools, then the head's
+    int buffers(int cap, int H, int W, hipStream_t stream) {
+        int rc;
+        if ((rc = trunk.buffers(cap, H, W, true, stream))) return rc;
+        for (int l = 0; l < 5; ++l) {
+            blocks[l] = stat_blocks(((trunk.h[l] + 1) / 2) * ((trunk.w[l] + 1) / 2), VGG_TAP_C[l]);
+            if ((rc = trunk.allocs.alloc(&partials[l], (size_t)cap * blocks[l] * VGG_TAP_C[l] * 5))) return rc;
+        }
+        gblocks = gray_blocks(H * W);
+        if ((rc = trunk.allocs.alloc(&gray, (size_t)cap * gblocks * 5))) return rc;
+        return trunk.allocs.alloc(&terms, (size_t)cap * NCHUNK * 4);
     }
+    ~evr_dists() { if (d_ab) (void)hipFree(d_ab); }
 };
-
-namespace {
-// pairs per pass at H x W
-int pass_pairs(const evr_dists* m, int H, int W) {
-    const int64_t per_pair = (int64_t)2 * H * W * 64 * 4;      // one buffer, one pair
-    int64_t p = m->max_pairs > 0 ? m->max_pairs : (int64_t)(ACT_BUDGET_BYTES / 2) / per_pair;
-    if (p * per_pair >= ACT_BUFFER_MAX_BYTES) p = (ACT_BUFFER_MAX_BYTES - 1) / per_pair;      // (>= 1: evr_dists_forward refuses larger frames)
-    return p < 1 ? 1 : (int)p;
-}
-}  // namespace
 
 extern "C" int evr_dists_create(const evr_tensor* tensors, int n_tensors, int max_pairs, evr_dists** out) {
     EVR_REQUIRE(tensors && out && max_pairs >= 0, "evr_dists_create: bad argument");
     const StateDict sd("DISTS", tensors, n_tensors);
     evr_dists* m = new evr_dists();
-    m->max_pairs = max_pairs;
-    m->mode = backbone_mode();
     int rc = EVR_OK;
-    const evr_tensor *w, *b, *al, *be;
+    const evr_tensor *al, *be;
     // torchvision vgg16.features indices inside the published stages (conv1_1 first)
-    const char* names[NCONV + 1] = {"stage1.0", "stage1.2", "stage2.5", "stage2.7", "stage3.10", "stage3.12", "stage3.14",
-                                    "stage4.17", "stage4.19", "stage4.21", "stage5.24", "stage5.26", "stage5.28"};
+    const char* const names[VGG_NCONV + 1] = {"stage1.0", "stage1.2", "stage2.5", "stage2.7", "stage3.10", "stage3.12", "stage3.14",
+                                              "stage4.17", "stage4.19", "stage4.21", "stage5.24", "stage5.26", "stage5.28"};
     do {
-        if ((rc = sd.get(std::string(names[0]) + ".weight", 64 * 3 * 9, &w))) break;
-        if ((rc = sd.get(std::string(names[0]) + ".bias", 64, &b))) break;
         // x_c = (g - mean_c)/std_c = g/std_c - mean_c/std_c; the buffers of the state dict where it carries them
         double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225}, fa[3], fb[3];
         if (sd.sd.count("mean") && sd.sd.count("std")) {
@@ -386,13 +364,7 @@ extern "C" int evr_dists_create(const evr_tensor* tensors, int n_tensors, int ma
         }
         if (!(stdv[0] > 0.0 && stdv[1] > 0.0 && stdv[2] > 0.0)) { set_error("DISTS tensor 'std' must be positive"); rc = EVR_ERR_INVALID; break; }
         for (int c = 0; c < 3; ++c) { fa[c] = 1.0 / stdv[c]; fb[c] = -mean[c] / stdv[c]; }
-        fold_scaling_layer(w->data_host, b->data_host, 64, 9, fa, fb, m->wg, m->wb, m->b1, m->b1in);
-        if ((rc = upload(m->wg, &m->d_wg))) break;
-        if ((rc = upload(m->wb, &m->d_wb))) break;
-        if ((rc = upload(m->b1, &m->d_b1))) break;
-        if ((rc = upload(m->b1in, &m->d_b1in))) break;
-        for (int l = 0; l < NCONV && !rc; ++l) rc = prepare_backbone_conv(sd, names[l + 1], VGG_CIN[l], VGG_COUT[l], 3, m->mode, &m->L[l]);
-        if (rc) break;
+        if ((rc = m->trunk.create(sd, names, fa, fb, max_pairs))) break;
         if ((rc = sd.get("alpha", NCH, &al))) break;
         if ((rc = sd.get("beta", NCH, &be))) break;
         double wsum = 0.0;
@@ -403,8 +375,6 @@ extern "C" int evr_dists_create(const evr_tensor* tensors, int n_tensors, int ma
         for (int c = 0; c < NCH; ++c) { ab[c] = (double)al->data_host[c] / wsum; ab[NCH + c] = (double)be->data_host[c] / wsum; }
         if (hipMalloc((void**)&m->d_ab, ab.size() * sizeof(double)) != hipSuccess) { rc = hip_fail(hipGetLastError(), "hipMalloc(alpha, beta)", __FILE__, __LINE__); break; }
         if (hipMemcpy(m->d_ab, ab.data(), ab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { rc = hip_fail(hipGetLastError(), "hipMemcpy(alpha, beta)", __FILE__, __LINE__); break; }
-        if (hipMalloc((void**)&m->d_sat, 64) != hipSuccess) { rc = hip_fail(hipGetLastError(), "hipMalloc(sat)", __FILE__, __LINE__); break; }
-        if (hipMemset(m->d_sat, 0, 64) != hipSuccess) { rc = hip_fail(hipGetLastError(), "hipMemset(sat)", __FILE__, __LINE__); break; }
     } while (0);
     if (rc) { delete m; return rc; }
     *out = m;
@@ -413,75 +383,33 @@ extern "C" int evr_dists_create(const evr_tensor* tensors, int n_tensors, int ma
 
 extern "C" int evr_dists_destroy(evr_dists* m) { delete m; return EVR_OK; }
 
-// (re)allocate the buffers for `cap` pairs per pass of H x W: the only place that synchronises
-static int dists_buffers(evr_dists* m, int cap, int H, int W, hipStream_t stream) {
-    EVR_HIP(hipStreamSynchronize(stream));
-    m->release();
-    m->cap = cap; m->H = H; m->W = W;
-    m->h[0] = H; m->w[0] = W;
-    for (int l = 1; l < 5; ++l) { m->h[l] = (m->h[l - 1] + 1) / 2; m->w[l] = (m->w[l - 1] + 1) / 2; }
-    int rc;
-    // the largest layer: relu1_1 / relu1_2 (a pooled map has at most ((H+1)/2)((W+1)/2) <= HW/2 pixels of twice the channels from 3 x 3 on)
-    const size_t act = (size_t)2 * cap * H * W * 64;
-    for (int i = 0; i < 2; ++i) if ((rc = m->allocs.alloc(&m->act[i], act))) return rc;
-    for (int l = 0; l < 5; ++l) {
-        m->blocks[l] = stat_blocks(((m->h[l] + 1) / 2) * ((m->w[l] + 1) / 2), VGG_TAP_C[l]);
-        if ((rc = m->allocs.alloc(&m->partials[l], (size_t)cap * m->blocks[l] * VGG_TAP_C[l] * 5))) return rc;
-    }
-    m->gblocks = gray_blocks(H * W);
-    if ((rc = m->allocs.alloc(&m->gray, (size_t)cap * m->gblocks * 5))) return rc;
-    if ((rc = m->allocs.alloc(&m->terms, (size_t)cap * NCHUNK * 4))) return rc;
-    if ((rc = m->allocs.alloc(&m->plans.d_args, (size_t)m->plans.NPLANS * NCONV))) return rc;
-    return EVR_OK;
-}
-
-// the plan of n pairs inside the current buffers (PlanCache::get fills a slot with this)
-static void dists_fill_plan(evr_dists* m, PlanCache<NCONV>::Plan& pl, int n) {
-    for (int i = 0; i < NCONV; ++i) {
-        ConvArgs& a = pl.args[i];
-        const int lv = VGG_LEVEL[i], src = vgg_conv_src(i);
-        fill_backbone_conv(a, m->L[i], m->act[src], m->act[src ^ 1], 2 * n, m->h[lv], m->w[lv]);
-        a.sat = m->d_sat;
-        pick_conv_tile(a, 32, &pl.wm[i], &pl.nb[i]);
-    }
-    attach_split_workspace(m->kws, m->allocs, pl.args, NCONV, 0);
-}
-
 // one pass: np pairs starting at img / ref, scores to out[0..np) (and out_stages[0..12 np))
 static int dists_pass(evr_dists* m, const float* img, const float* ref, int np, int clip, double* out, double* out_stages, hipStream_t stream) {
-    int rc;
-    PlanCache<NCONV>::Plan* P = nullptr;
-    if ((rc = m->plans.get(np, stream, [m](PlanCache<NCONV>::Plan& pl, int n) { dists_fill_plan(m, pl, n); }, &P))) return rc;
-    ConvArgs* const d_args = m->plans.device_args(P);
-    const int fmt = packed_fmt(m->mode);
-    hipLaunchKernelGGL(dists_gray_kernel, dim3(m->gblocks, np), dim3(256), 0, stream, img, ref, m->H * m->W, clip, m->gray);
+    VggTrunk& t = m->trunk;
+    int rc, src = 0;
+    VggTrunk::Plan* P = nullptr;
+    if ((rc = t.begin_pass(np, stream, &P))) return rc;
+    hipLaunchKernelGGL(dists_gray_kernel, dim3(m->gblocks, np), dim3(256), 0, stream, img, ref, t.H * t.W, clip, m->gray);
     EVR_LAUNCH_CHECK();
-    Conv11Args c1{};
-    c1.img = img; c1.ref = ref; c1.n = np; c1.H = m->H; c1.W = m->W; c1.clip = clip;
-    c1.wg = m->d_wg; c1.wb = m->d_wb; c1.bias = m->d_b1; c1.bias_in = m->d_b1in; c1.out = m->act[0]; c1.sat = m->d_sat;
-    if ((rc = launch_conv1_1_fmt(fmt, c1, stream))) return rc;
+    if ((rc = t.conv1_1(img, ref, np, clip, stream))) return rc;
     ChannelArgs ca{};
-    int ci = 0;
     for (int l = 0; l < 5; ++l) {
-        for (; ci < NCONV && VGG_LEVEL[ci] == l; ++ci)
-            if ((rc = launch_conv_igemm(P->args[ci], d_args + ci, 32, P->wm[ci], P->nb[ci], stream))) return rc;
-        // the stage's features sit where its last convolution wrote them; the pool goes to the other buffer
-        const int src = vgg_conv_src(ci - 1) ^ 1;
-        StatArgs t{};
-        t.feat = m->act[src]; t.pooled = l < 4 ? m->act[src ^ 1] : nullptr;
-        t.n = np; t.h = m->h[l]; t.w = m->w[l]; t.C = VGG_TAP_C[l]; t.fmt = fmt;
-        t.partials = m->partials[l]; t.sat = m->d_sat;
-        const dim3 grid(m->blocks[l], np, t.C >= 256 ? t.C / 256 : 1);
-        if (l < 4) hipLaunchKernelGGL(dists_stat_pool_kernel<true>, grid, dim3(256), 0, stream, t);
-        else hipLaunchKernelGGL(dists_stat_pool_kernel<false>, grid, dim3(256), 0, stream, t);
+        if ((rc = t.level_convs(P, l, stream, &src))) return rc;
+        StatArgs st{};
+        st.feat = t.act[src]; st.pooled = l < 4 ? t.act[src ^ 1] : nullptr;
+        st.n = np; st.h = t.h[l]; st.w = t.w[l]; st.C = VGG_TAP_C[l]; st.fmt = t.fmt();
+        st.partials = m->partials[l]; st.sat = t.d_sat;
+        const dim3 grid(m->blocks[l], np, st.C >= 256 ? st.C / 256 : 1);
+        if (l < 4) hipLaunchKernelGGL(dists_stat_pool_kernel<true>, grid, dim3(256), 0, stream, st);
+        else hipLaunchKernelGGL(dists_stat_pool_kernel<false>, grid, dim3(256), 0, stream, st);
         EVR_LAUNCH_CHECK();
-        ca.partials[l] = t.partials; ca.blocks[l] = m->blocks[l]; ca.hw[l] = t.h * t.w;
+        ca.partials[l] = st.partials; ca.blocks[l] = m->blocks[l]; ca.hw[l] = st.h * st.w;
     }
     ca.aw = m->d_ab; ca.bw = m->d_ab + NCH; ca.terms = m->terms;
     hipLaunchKernelGGL(dists_channel_kernel, dim3(NCHUNK, np), dim3(256), 0, stream, ca);
     EVR_LAUNCH_CHECK();
     FinishArgs fa{};
-    fa.terms = m->terms; fa.gray = m->gray; fa.gray_blocks = m->gblocks; fa.hw0 = m->H * m->W;
+    fa.terms = m->terms; fa.gray = m->gray; fa.gray_blocks = m->gblocks; fa.hw0 = t.H * t.W;
     fa.aw = ca.aw; fa.bw = ca.bw;
     hipLaunchKernelGGL(dists_finish_kernel, dim3(np), dim3(64), 0, stream, fa, out, out_stages);
     EVR_LAUNCH_CHECK();
@@ -494,36 +422,16 @@ extern "C" int evr_dists_forward(evr_dists* m, const float* img, const float* re
     EVR_REQUIRE(m && img && ref && out && n >= 1 && H >= 1 && W >= 1, "evr_dists_forward: bad argument");
     EVR_REQUIRE(H >= MIN_SIDE && W >= MIN_SIDE, "evr_dists: image %dx%d too small (this backbone runs on frames of at least %d pixels a side)", W, H, MIN_SIDE);
     EVR_REQUIRE((int64_t)2 * H * W * 64 * 4 < ACT_BUFFER_MAX_BYTES, "evr_dists: image %dx%d too large: one pair's 64-channel features must stay below 2 GiB (H*W < 2^22)", W, H);
-    int rc;
-    const int P = pass_pairs(m, H, W), need = n < P ? n : P;
-    if (m->H != H || m->W != W || need > m->cap) if ((rc = dists_buffers(m, need, H, W, stream))) { m->release(); m->H = m->W = 0; return rc; }
-    m->n = n;
-    for (int o = 0; o < n; o += P) {
-        const int np = n - o < P ? n - o : P;
-        if ((rc = dists_pass(m, img + (int64_t)o * H * W, ref + (int64_t)o * H * W, np, clip, out + o,
-                             out_stages ? out_stages + (int64_t)NSETS * 2 * o : nullptr, stream))) return rc;
-    }
-    return EVR_OK;
+    return vgg_forward(m, n, H, W, stream, [&](int o, int np) {
+        return dists_pass(m, img + (int64_t)o * H * W, ref + (int64_t)o * H * W, np, clip, out + o,
+                          out_stages ? out_stages + (int64_t)NSETS * 2 * o : nullptr, stream);
+    });
 }
 
-// algorithmic operations of the last call: 2 per multiply-add of the thirteen convolutions, conv1_1 in the folded one-channel form it
-// runs in (the statistics and the pools are not counted)
-extern "C" double evr_dists_flops(const evr_dists* m) {
-    if (!m || m->n == 0) return 0.0;
-    double f = 2.0 * (2.0 * m->n) * m->H * m->W * 64 * 9;
-    for (int l = 0; l < NCONV; ++l) f += 2.0 * (2.0 * m->n) * m->h[VGG_LEVEL[l]] * m->w[VGG_LEVEL[l]] * VGG_CIN[l] * VGG_COUT[l] * 9;
-    return f;
-}
+// (the statistics and the pools are not counted)
+extern "C" double evr_dists_flops(const evr_dists* m) { return m ? m->trunk.flops() : 0.0; }
 
-// the range-guard counter (output runs beyond the packed format's exact range, packed.h sat_note) since the last read; cleared.
-// Waits for the stream.
 extern "C" int evr_dists_saturation(evr_dists* m, int64_t* count, evr_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     EVR_REQUIRE(m && count, "evr_dists_saturation: null argument");
-    unsigned v = 0;
-    EVR_HIP(hipMemcpyAsync(&v, m->d_sat, sizeof(v), hipMemcpyDeviceToHost, stream));
-    EVR_HIP(hipMemsetAsync(m->d_sat, 0, sizeof(v), stream));
-    EVR_HIP(hipStreamSynchronize(stream));
-    *count = (int64_t)v;
-    return EVR_OK;
+    return m->trunk.saturation(count, (hipStream_t)stream_);
 }

@@ -65,12 +65,15 @@ inline void fold_scaling_layer(const float* w, const float* bias, int cout, int 
         b1in[co] = (float)((double)b1[co] + bsum);
     }
 }
-// The scaling layer of LPIPS: x_c = ((2g-1) - shift_c)/scale_c
+// The scaling layer of LPIPS, x_c = ((2g-1) - shift_c)/scale_c, as (a_c, b_c)
+inline void lpips_scaling(double (&a)[3], double (&b)[3]) {
+    const double shift[3] = {-.030, -.088, -.188}, scale[3] = {.458, .448, .450};
+    for (int c = 0; c < 3; ++c) { a[c] = 2.0 / scale[c]; b[c] = (-1.0 - shift[c]) / scale[c]; }
+}
 inline void fold_scaling_layer(const float* w, const float* bias, int cout, int taps, std::vector<float>& wg, std::vector<float>& wb,
                                std::vector<float>& b1, std::vector<float>& b1in) {
-    const double shift[3] = {-.030, -.088, -.188}, scale[3] = {.458, .448, .450};
     double a[3], b[3];
-    for (int c = 0; c < 3; ++c) { a[c] = 2.0 / scale[c]; b[c] = (-1.0 - shift[c]) / scale[c]; }
+    lpips_scaling(a, b);
     fold_scaling_layer(w, bias, cout, taps, a, b, wg, wb, b1, b1in);
 }
 

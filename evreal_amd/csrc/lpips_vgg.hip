@@ -12,13 +12,15 @@
 // and lin{0..4}.model.1.weight (64, 128, 256, 512, 512 elements), and the pool positions (torchvision indices 4, 9, 16, 23).
 // Scores agree with the restatement tests/lpips_vgg_ref.py on any weights, and with pyiqa only once its weights are supplied.
 //
-// Layers: conv1_1 (3->64) is a direct VALU kernel on the gray input (vgg_backbone.h, shared with dists.hip; the three input channels are affine in the same gray value);
-// the other twelve 3x3 convolutions run on the convolution kernels of conv.hip through the set-up both backbones share (lpips_host.h; split
-// arithmetic: every activation tensor is PACKED / H2; fp32 mode: PLAIN, Winograd where eligible); one streaming kernel per tap
-// layer scores it and writes the 2x2 max pool of both images' features -- the 64-channel full-resolution tensor is read once.
+// Layers: the thirteen convolutions are the VGG-16 trunk this metric shares with dists.hip, kernels (vgg_backbone.h) and host side
+// (vgg_trunk.h: the handle holds a VggTrunk) -- conv1_1 (3->64) is a direct VALU kernel on the gray input (the three input channels are
+// affine in the same gray value); the other twelve 3x3 convolutions run on the convolution kernels of conv.hip (split arithmetic: every
+// activation tensor is PACKED / H2; fp32 mode: PLAIN, Winograd where eligible).  This file's own: the state-dict names, the scaling
+// constants, and the head -- one streaming kernel per tap layer scores it and writes the 2x2 max pool (floor mode) of both images'
+// features -- the 64-channel full-resolution tensor is read once.
 //
-// Memory plan: relu1_2 is 2*H*W*64*4 B per pair (46 MB at 346x260), so features are NOT kept: two ping-pong activation buffers
-// sized for the largest layer, 2*P*H*W*64*4 B each for P pairs per pass, P chosen so that both fit ACT_BUDGET_BYTES (at least 1;
+// Memory plan (vgg_trunk.h): relu1_2 is 2*H*W*64*4 B per pair (46 MB at 346x260), so features are NOT kept: two ping-pong activation
+// buffers sized for the largest layer, 2*P*H*W*64*4 B each for P pairs per pass, P chosen so that both fit ACT_BUDGET_BYTES (at least 1;
 // `max_pairs` at create overrides it); a call with more pairs runs in passes, both frames of a pair always in the same pass.
 #include <cmath>
 #include <cstring>
@@ -27,22 +29,15 @@
 #include <vector>
 
 #include "conv.h"
-#include "lpips_host.h"
 #include "packed.h"
-#include "vgg_backbone.h"
+#include "vgg_trunk.h"
 
 using namespace evr;
 
 namespace {
 
-constexpr size_t ACT_BUDGET_BYTES = (size_t)1 << 30;      // both activation buffers of a handle together (default pass size)
-// one buffer, whatever max_pairs asks: conv.hip sizes the buffer descriptor of a tensor in 32-bit bytes and offsets its pixel rows in
-// 32-bit float elements (this file's own kernels index in 64 bits), and its launcher wants n*hm*wm < 2^31.  2 GiB keeps all three;
-// a frame whose single pair does not fit (H*W >= 2^22) is refused
-constexpr int64_t ACT_BUFFER_MAX_BYTES = (int64_t)1 << 31;
 constexpr int MIN_SIDE = 16;                               // four floor-mode 2x2 pools must leave one pixel
-constexpr int NCONV = VGG_NCONV;      // (the tables of the trunk and conv1_1: vgg_backbone.h)
-constexpr const int* TAP_C = VGG_TAP_C;
+constexpr const int* TAP_C = VGG_TAP_C;      // (the tables of the trunk and conv1_1: vgg_backbone.h)
 
 // ---- one tap layer: LPIPS partial sums + the 2x2 max pool of both images' features -------------------------------------
 // feat: [2n, h, w, C] (first n = img, last n = ref) in format `fmt`; pooled: [2n, h/2, w/2, C] in the same format, or null
@@ -174,75 +169,34 @@ int score_blocks(int n, int nwin, int C) {
 }  // namespace
 
 struct evr_lpips_vgg {
-    std::vector<float> wg, wb, b1, b1in;
-    float* d_wg = nullptr; float* d_wb = nullptr; float* d_b1 = nullptr; float* d_b1in = nullptr;
+    VggTrunk trunk;
     float* d_lin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned* d_sat = nullptr;       // range guard of the packed formats (packed.h sat_note): every producer of this handle counts here
-    BackboneConv L[NCONV];
-    int mode = 0;                    // arithmetic of the twelve convolutions (lpips_host.h backbone_mode)
-    int max_pairs = 0;               // constructor argument: pairs per pass (0: from ACT_BUDGET_BYTES)
-    // shape-dependent.  Buffers are sized for `cap` pairs per pass at H x W and only ever grow; what depends on the pair count of
-    // a pass (the twelve ConvArgs with their tile choice) lives in the plan cache (lpips_host.h).
-    int n = 0, H = 0, W = 0, cap = 0;      // n: pairs of the last call (evr_lpips_vgg_flops)
-    int h[5], w[5];                  // feature map sizes of the five levels
-    DeviceAllocs allocs;
-    float* act[2] = {nullptr, nullptr};
-    PlanCache<NCONV> plans;
-    SplitWorkspace kws;
-    double* partials = nullptr;      // [5][cap][SCORE_BLOCKS_MAX]
-    void release() {
-        allocs.release();
-        cap = 0; plans.clear(); kws = SplitWorkspace(); act[0] = act[1] = nullptr; partials = nullptr;
+    double* partials = nullptr;      // [5][cap][SCORE_BLOCKS_MAX], of trunk.allocs
+    void release() { trunk.release(); partials = nullptr; }
+    // (vgg_forward) the trunk's buffers with floor-mode pools, then the head's
+    int buffers(int cap, int H, int W, hipStream_t stream) {
+        int rc;
+        if ((rc = trunk.buffers(cap, H, W, false, stream))) return rc;
+        return trunk.allocs.alloc(&partials, (size_t)5 * cap * SCORE_BLOCKS_MAX);
     }
-    ~evr_lpips_vgg() {
-        release();
-        if (d_wg) (void)hipFree(d_wg); if (d_wb) (void)hipFree(d_wb); if (d_b1) (void)hipFree(d_b1); if (d_b1in) (void)hipFree(d_b1in);
-        if (d_sat) (void)hipFree(d_sat);
-        for (auto& p : d_lin) if (p) (void)hipFree(p);
-        for (auto& l : L) free_backbone_conv(l);
-    }
+    ~evr_lpips_vgg() { for (auto& p : d_lin) if (p) (void)hipFree(p); }
 };
-
-namespace {
-// pairs per pass at H x W
-int pass_pairs(const evr_lpips_vgg* m, int H, int W) {
-    const int64_t per_pair = (int64_t)2 * H * W * 64 * 4;      // one buffer, one pair
-    int64_t p = m->max_pairs > 0 ? m->max_pairs : (int64_t)(ACT_BUDGET_BYTES / 2) / per_pair;
-    if (p * per_pair >= ACT_BUFFER_MAX_BYTES) p = (ACT_BUFFER_MAX_BYTES - 1) / per_pair;      // (>= 1: evr_lpips_vgg_forward refuses larger frames)
-    return p < 1 ? 1 : (int)p;
-}
-}  // namespace
 
 extern "C" int evr_lpips_vgg_create(const evr_tensor* tensors, int n_tensors, int max_pairs, evr_lpips_vgg** out) {
     EVR_REQUIRE(tensors && out && max_pairs >= 0, "evr_lpips_vgg_create: bad argument");
     const StateDict sd("LPIPS-VGG", tensors, n_tensors);
-    evr_lpips_vgg* m = new evr_lpips_vgg();
-    m->max_pairs = max_pairs;
-    m->mode = backbone_mode();
-    int rc = EVR_OK;
-    const evr_tensor *w, *b;
     // torchvision vgg16.features indices inside pyiqa's slices (conv1_1 first)
-    const char* names[NCONV + 1] = {"net.slice1.0", "net.slice1.2", "net.slice2.5", "net.slice2.7", "net.slice3.10", "net.slice3.12", "net.slice3.14",
-                                    "net.slice4.17", "net.slice4.19", "net.slice4.21", "net.slice5.24", "net.slice5.26", "net.slice5.28"};
-    do {
-        if ((rc = sd.get(std::string(names[0]) + ".weight", 64 * 3 * 9, &w))) break;
-        if ((rc = sd.get(std::string(names[0]) + ".bias", 64, &b))) break;
-        fold_scaling_layer(w->data_host, b->data_host, 64, 9, m->wg, m->wb, m->b1, m->b1in);
-        if ((rc = upload(m->wg, &m->d_wg))) break;
-        if ((rc = upload(m->wb, &m->d_wb))) break;
-        if ((rc = upload(m->b1, &m->d_b1))) break;
-        if ((rc = upload(m->b1in, &m->d_b1in))) break;
-        for (int l = 0; l < NCONV && !rc; ++l) rc = prepare_backbone_conv(sd, names[l + 1], VGG_CIN[l], VGG_COUT[l], 3, m->mode, &m->L[l]);
-        if (rc) break;
-        for (int l = 0; l < 5 && !rc; ++l) {
-            if ((rc = sd.get("lin" + std::to_string(l) + ".model.1.weight", TAP_C[l], &w))) break;
-            std::vector<float> lw(w->data_host, w->data_host + TAP_C[l]);
-            rc = upload(lw, &m->d_lin[l]);
-        }
-        if (rc) break;
-        if (hipMalloc((void**)&m->d_sat, 64) != hipSuccess) { rc = hip_fail(hipGetLastError(), "hipMalloc(sat)", __FILE__, __LINE__); break; }
-        if (hipMemset(m->d_sat, 0, 64) != hipSuccess) { rc = hip_fail(hipGetLastError(), "hipMemset(sat)", __FILE__, __LINE__); break; }
-    } while (0);
+    const char* const names[VGG_NCONV + 1] = {"net.slice1.0", "net.slice1.2", "net.slice2.5", "net.slice2.7", "net.slice3.10", "net.slice3.12", "net.slice3.14",
+                                              "net.slice4.17", "net.slice4.19", "net.slice4.21", "net.slice5.24", "net.slice5.26", "net.slice5.28"};
+    double a[3], b[3];
+    lpips_scaling(a, b);
+    evr_lpips_vgg* m = new evr_lpips_vgg();
+    int rc = m->trunk.create(sd, names, a, b, max_pairs);
+    for (int l = 0; l < 5 && !rc; ++l) {
+        const evr_tensor* w;
+        if ((rc = sd.get("lin" + std::to_string(l) + ".model.1.weight", TAP_C[l], &w))) break;
+        rc = upload(std::vector<float>(w->data_host, w->data_host + TAP_C[l]), &m->d_lin[l]);
+    }
     if (rc) { delete m; return rc; }
     *out = m;
     return EVR_OK;
@@ -250,59 +204,24 @@ extern "C" int evr_lpips_vgg_create(const evr_tensor* tensors, int n_tensors, in
 
 extern "C" int evr_lpips_vgg_destroy(evr_lpips_vgg* m) { delete m; return EVR_OK; }
 
-// (re)allocate the activation buffers for `cap` pairs per pass of H x W: the only place that synchronises
-static int vgg_buffers(evr_lpips_vgg* m, int cap, int H, int W, hipStream_t stream) {
-    EVR_HIP(hipStreamSynchronize(stream));
-    m->release();
-    m->cap = cap; m->H = H; m->W = W;
-    m->h[0] = H; m->w[0] = W;
-    for (int l = 1; l < 5; ++l) { m->h[l] = m->h[l - 1] / 2; m->w[l] = m->w[l - 1] / 2; }
-    int rc;
-    const size_t act = (size_t)2 * cap * H * W * 64;      // the largest layer: relu1_1 / relu1_2 (every later one is at most half of it)
-    for (int i = 0; i < 2; ++i) if ((rc = m->allocs.alloc(&m->act[i], act))) return rc;
-    if ((rc = m->allocs.alloc(&m->partials, (size_t)5 * cap * SCORE_BLOCKS_MAX))) return rc;
-    if ((rc = m->allocs.alloc(&m->plans.d_args, (size_t)m->plans.NPLANS * NCONV))) return rc;
-    return EVR_OK;
-}
-
-// the plan of n pairs inside the current buffers (PlanCache::get fills a slot with this)
-static void vgg_fill_plan(evr_lpips_vgg* m, PlanCache<NCONV>::Plan& pl, int n) {
-    for (int i = 0; i < NCONV; ++i) {
-        ConvArgs& a = pl.args[i];
-        const int lv = VGG_LEVEL[i], src = vgg_conv_src(i);
-        fill_backbone_conv(a, m->L[i], m->act[src], m->act[src ^ 1], 2 * n, m->h[lv], m->w[lv]);
-        a.sat = m->d_sat;
-        pick_conv_tile(a, 32, &pl.wm[i], &pl.nb[i]);
-    }
-    attach_split_workspace(m->kws, m->allocs, pl.args, NCONV, 0);
-}
-
 // one pass: np pairs starting at img / ref, scores to out[0..np) (and out_layers[0..5 np))
 static int vgg_pass(evr_lpips_vgg* m, const float* img, const float* ref, int np, int clip, double* out, double* out_layers, hipStream_t stream) {
-    int rc;
-    PlanCache<NCONV>::Plan* P = nullptr;
-    if ((rc = m->plans.get(np, stream, [m](PlanCache<NCONV>::Plan& pl, int n) { vgg_fill_plan(m, pl, n); }, &P))) return rc;
-    ConvArgs* const d_args = m->plans.device_args(P);
-    const int fmt = packed_fmt(m->mode);
-    Conv11Args c1{};
-    c1.img = img; c1.ref = ref; c1.n = np; c1.H = m->H; c1.W = m->W; c1.clip = clip;
-    c1.wg = m->d_wg; c1.wb = m->d_wb; c1.bias = m->d_b1; c1.bias_in = m->d_b1in; c1.out = m->act[0]; c1.sat = m->d_sat;
-    if ((rc = launch_conv1_1_fmt(fmt, c1, stream))) return rc;
+    VggTrunk& t = m->trunk;
+    int rc, src = 0;
+    VggTrunk::Plan* P = nullptr;
+    if ((rc = t.begin_pass(np, stream, &P))) return rc;
+    if ((rc = t.conv1_1(img, ref, np, clip, stream))) return rc;
     FinalArgs fa{};
-    int ci = 0;
     for (int l = 0; l < 5; ++l) {
-        for (; ci < NCONV && VGG_LEVEL[ci] == l; ++ci)
-            if ((rc = launch_conv_igemm(P->args[ci], d_args + ci, 32, P->wm[ci], P->nb[ci], stream))) return rc;
-        // the tap layer sits where the level's last convolution wrote it; its pool goes to the other buffer
-        const int src = vgg_conv_src(ci - 1) ^ 1;
-        TapArgs t{};
-        t.feat = m->act[src]; t.pooled = l < 4 ? m->act[src ^ 1] : nullptr; t.lin = m->d_lin[l];
-        t.n = np; t.h = m->h[l]; t.w = m->w[l]; t.C = TAP_C[l]; t.fmt = fmt;
-        t.partials = m->partials + (size_t)l * m->cap * SCORE_BLOCKS_MAX;
-        const int nwin = ((t.h + 1) / 2) * ((t.w + 1) / 2), blocks = score_blocks(np, nwin, t.C);
-        hipLaunchKernelGGL(vgg_pool_score_kernel, dim3(blocks, np), dim3(256), 0, stream, t);
+        if ((rc = t.level_convs(P, l, stream, &src))) return rc;
+        TapArgs tp{};
+        tp.feat = t.act[src]; tp.pooled = l < 4 ? t.act[src ^ 1] : nullptr; tp.lin = m->d_lin[l];
+        tp.n = np; tp.h = t.h[l]; tp.w = t.w[l]; tp.C = TAP_C[l]; tp.fmt = t.fmt();
+        tp.partials = m->partials + (size_t)l * t.cap * SCORE_BLOCKS_MAX;
+        const int nwin = ((tp.h + 1) / 2) * ((tp.w + 1) / 2), blocks = score_blocks(np, nwin, tp.C);
+        hipLaunchKernelGGL(vgg_pool_score_kernel, dim3(blocks, np), dim3(256), 0, stream, tp);
         EVR_LAUNCH_CHECK();
-        fa.partials[l] = t.partials; fa.hw[l] = t.h * t.w; fa.blocks[l] = blocks;
+        fa.partials[l] = tp.partials; fa.hw[l] = tp.h * tp.w; fa.blocks[l] = blocks;
     }
     hipLaunchKernelGGL(vgg_final_kernel, dim3(np), dim3(64), 0, stream, fa, np, out, out_layers);
     EVR_LAUNCH_CHECK();
@@ -315,35 +234,14 @@ extern "C" int evr_lpips_vgg_forward(evr_lpips_vgg* m, const float* img, const f
     EVR_REQUIRE(m && img && ref && out && n >= 1 && H >= 1 && W >= 1, "evr_lpips_vgg_forward: bad argument");
     EVR_REQUIRE(H >= MIN_SIDE && W >= MIN_SIDE, "evr_lpips_vgg: image %dx%d too small for VGG-16 (four 2x2 pools need %d pixels a side)", W, H, MIN_SIDE);
     EVR_REQUIRE((int64_t)2 * H * W * 64 * 4 < ACT_BUFFER_MAX_BYTES, "evr_lpips_vgg: image %dx%d too large: one pair's 64-channel features must stay below 2 GiB (H*W < 2^22)", W, H);
-    int rc;
-    const int P = pass_pairs(m, H, W), need = n < P ? n : P;
-    if (m->H != H || m->W != W || need > m->cap) if ((rc = vgg_buffers(m, need, H, W, stream))) { m->release(); m->H = m->W = 0; return rc; }
-    m->n = n;
-    for (int o = 0; o < n; o += P) {
-        const int np = n - o < P ? n - o : P;
-        if ((rc = vgg_pass(m, img + (int64_t)o * H * W, ref + (int64_t)o * H * W, np, clip, out + o, out_layers ? out_layers + (int64_t)5 * o : nullptr, stream))) return rc;
-    }
-    return EVR_OK;
+    return vgg_forward(m, n, H, W, stream, [&](int o, int np) {
+        return vgg_pass(m, img + (int64_t)o * H * W, ref + (int64_t)o * H * W, np, clip, out + o, out_layers ? out_layers + (int64_t)5 * o : nullptr, stream);
+    });
 }
 
-// algorithmic operations of the last call: 2 per multiply-add of the thirteen convolutions, conv1_1 in the folded one-channel form it
-// runs in (304,704 multiply-adds per input pixel at sides that are multiples of 16)
-extern "C" double evr_lpips_vgg_flops(const evr_lpips_vgg* m) {
-    if (!m || m->n == 0) return 0.0;
-    double f = 2.0 * (2.0 * m->n) * m->H * m->W * 64 * 9;
-    for (int l = 0; l < NCONV; ++l) f += 2.0 * (2.0 * m->n) * m->h[VGG_LEVEL[l]] * m->w[VGG_LEVEL[l]] * VGG_CIN[l] * VGG_COUT[l] * 9;
-    return f;
-}
+extern "C" double evr_lpips_vgg_flops(const evr_lpips_vgg* m) { return m ? m->trunk.flops() : 0.0; }
 
-// the range-guard counter (output runs beyond the packed format's exact range, packed.h sat_note) since the last read; cleared.
-// Waits for the stream.
 extern "C" int evr_lpips_vgg_saturation(evr_lpips_vgg* m, int64_t* count, evr_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     EVR_REQUIRE(m && count, "evr_lpips_vgg_saturation: null argument");
-    unsigned v = 0;
-    EVR_HIP(hipMemcpyAsync(&v, m->d_sat, sizeof(v), hipMemcpyDeviceToHost, stream));
-    EVR_HIP(hipMemsetAsync(m->d_sat, 0, sizeof(v), stream));
-    EVR_HIP(hipStreamSynchronize(stream));
-    *count = (int64_t)v;
-    return EVR_OK;
+    return m->trunk.saturation(count, (hipStream_t)stream_);
 }

@@ -1,6 +1,7 @@
-// What the metrics on the VGG-16 trunk share (lpips_vgg.hip: LPIPS-VGG, dists.hip: DISTS): the table of the twelve convolutions that
-// run on the kernels of conv.hip, and conv1_1 -- the direct kernel on the gray frame with its launcher.  The fold of a metric's input
-// scaling into conv1_1's weights is lpips_host.h fold_scaling_layer.
+// The kernel side of what the metrics on the VGG-16 trunk share (lpips_vgg.hip: LPIPS-VGG, dists.hip: DISTS): the table of the twelve
+// convolutions that run on the kernels of conv.hip, and conv1_1 -- the direct kernel on the gray frame with its launcher.  The host side
+// (weights, buffers, plans, the passes of a call) is vgg_trunk.h; the fold of a metric's input scaling into conv1_1's weights is
+// lpips_host.h fold_scaling_layer.
 #pragma once
 #include "conv.h"
 #include "packed.h"

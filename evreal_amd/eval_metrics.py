@@ -31,7 +31,7 @@ from os.path import join
 import numpy as np
 import torch
 
-from .lpips import DISTS, LPIPSVGG
+from .lpips import DISTS, LPIPS, LPIPSVGG
 from .prepost import GMSD, FullRefMetrics, Metrics, histogram_equalization
 
 DEFAULT_METRICS = ('mse', 'ssim', 'lpips')      # the reference's default (eval.py:413-445, utils/eval_metrics.py:171)
@@ -49,35 +49,27 @@ BRISQUE_MODEL_ENV = 'EVREAL_BRISQUE_MODEL'      # path to a BRISQUE model (.npz,
 BRISQUE_RANGE_ENV = 'EVREAL_BRISQUE_RANGE'      # the svm-scale range file of a libsvm model (default: allrange beside it)
 
 
-def _load_lpips():
-    """The reference lets pyiqa download the LPIPS weights; offline they must be supplied as a file."""
-    path = os.environ.get(LPIPS_WEIGHTS_ENV, os.path.join('pretrained', 'lpips_alex.pth'))
+def _load_backbone(name, cls, env, file):
+    """`cls` on the state dict at $env or pretrained/`file`.  The reference lets pyiqa download the weights; offline they must be
+    supplied as a file, made where pyiqa exists by torch.save(pyiqa.create_metric(name).net.state_dict(), path)."""
+    path = os.environ.get(env, os.path.join('pretrained', file))
     if not os.path.exists(path):
-        print(f"lpips: no weights at ${LPIPS_WEIGHTS_ENV} or pretrained/lpips_alex.pth (pyiqa downloads them; "
+        print(f"{name}: no weights at ${env} or pretrained/{file} (pyiqa downloads them; "
               "offline they must be provided) -> falling back to pyiqa if it is installed")
         return None
-    from .lpips import LPIPS
-    return LPIPS(torch.load(path, map_location='cpu', weights_only=False))
+    return cls(torch.load(path, map_location='cpu', weights_only=False))
+
+
+def _load_lpips():
+    return _load_backbone('lpips', LPIPS, LPIPS_WEIGHTS_ENV, 'lpips_alex.pth')
 
 
 def _load_lpips_vgg():
-    """As _load_lpips: made where pyiqa exists by torch.save(pyiqa.create_metric('lpips-vgg').net.state_dict(), path)."""
-    path = os.environ.get(LPIPS_VGG_WEIGHTS_ENV, os.path.join('pretrained', 'lpips_vgg.pth'))
-    if not os.path.exists(path):
-        print(f"lpips-vgg: no weights at ${LPIPS_VGG_WEIGHTS_ENV} or pretrained/lpips_vgg.pth (pyiqa downloads them; "
-              "offline they must be provided) -> falling back to pyiqa if it is installed")
-        return None
-    return LPIPSVGG(torch.load(path, map_location='cpu', weights_only=False))
+    return _load_backbone('lpips-vgg', LPIPSVGG, LPIPS_VGG_WEIGHTS_ENV, 'lpips_vgg.pth')
 
 
 def _load_dists():
-    """As _load_lpips: made where pyiqa exists by torch.save(pyiqa.create_metric('dists').net.state_dict(), path)."""
-    path = os.environ.get(DISTS_WEIGHTS_ENV, os.path.join('pretrained', 'dists.pth'))
-    if not os.path.exists(path):
-        print(f"dists: no weights at ${DISTS_WEIGHTS_ENV} or pretrained/dists.pth (pyiqa downloads them; "
-              "offline they must be provided) -> falling back to pyiqa if it is installed")
-        return None
-    return DISTS(torch.load(path, map_location='cpu', weights_only=False))
+    return _load_backbone('dists', DISTS, DISTS_WEIGHTS_ENV, 'dists.pth')
 
 
 def gpu_fr_metrics_enabled():

@@ -70,35 +70,51 @@ class LPIPS(_Backbone):
         return out
 
 
-class LPIPSVGG(_Backbone):
-    """pyiqa.create_metric('lpips-vgg') stand-in on the GPU (evr_lpips_vgg_*): same call shape as LPIPS.
+class _VggTrunkMetric(_Backbone):
+    """The metrics on the VGG-16 trunk (csrc/vgg_trunk.h): their entry points have one shape.
 
     max_pairs: frame pairs per pass (0: as many as keep the handle's two activation buffers within 1 GiB); a call with more pairs
     runs in passes."""
-    _entry = 'evr_lpips_vgg'
-    MIN_SIDE = 16           # four floor-mode 2x2 pools must leave one pixel
+    # the trunk's kernels run down to the 1x1 maps of a 16x16 frame: LPIPS-VGG's four floor-mode 2x2 pools must leave one pixel
+    # (pyiqa's dists would accept smaller frames)
+    MIN_SIDE = 16
+    _too_small = None       # the metric's sentence, with {m} for MIN_SIDE and {H}, {W}
 
     def __init__(self, state_dict, max_pairs=0):
         self._create(state_dict, int(max_pairs))
 
     @classmethod
     def too_small(cls, H, W):
-        """The message of the exception `lpips-vgg` raises on frames of this size, or None where it is defined."""
+        """The message of the exception the metric raises on frames of this size, or None where it is defined."""
         if min(H, W) >= cls.MIN_SIDE:
             return None
-        return (f"lpips-vgg needs frames of at least {cls.MIN_SIDE}x{cls.MIN_SIDE} pixels (VGG-16 pools 2x2 four times), "
-                f"got {H}x{W}")
+        return cls._too_small.format(m=cls.MIN_SIDE, H=H, W=W)
 
-    def _forward(self, img, ref, clip, out, layers):
+    def _forward(self, img, ref, clip, out, parts):
+        """parts: None, or the device array of the per-layer / per-stage distances to fill."""
         img, ref, out = self._inputs(img, ref, out)
         assert img.dtype == ref.dtype == torch.float32
         n, H, W = img.shape
         if self.too_small(H, W):
             raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
         assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n
-        _lib.check(self.lib.evr_lpips_vgg_forward(self.handle, _lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0,
-                                                  _lib.ptr(out), _lib.ptr(layers), _lib.stream_ptr()), 'evr_lpips_vgg_forward')
+        _lib.check(getattr(self.lib, self._entry + '_forward')(self.handle, _lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0,
+                                                               _lib.ptr(out), _lib.ptr(parts), _lib.stream_ptr()), self._entry + '_forward')
         return out
+
+    def saturation(self):
+        """Output runs that left the exact range of the arithmetic mode's activation format since the last call (the counter is
+        cleared); waits for the current stream."""
+        c = ctypes.c_int64(0)
+        _lib.check(getattr(self.lib, self._entry + '_saturation')(self.handle, ctypes.byref(c), _lib.stream_ptr()),
+                   self._entry + '_saturation')
+        return int(c.value)
+
+
+class LPIPSVGG(_VggTrunkMetric):
+    """pyiqa.create_metric('lpips-vgg') stand-in on the GPU (evr_lpips_vgg_*): same call shape as LPIPS."""
+    _entry = 'evr_lpips_vgg'
+    _too_small = "lpips-vgg needs frames of at least {m}x{m} pixels (VGG-16 pools 2x2 four times), got {H}x{W}"
 
     def __call__(self, img, ref, clip=True, out=None):
         """img, ref: cuda fp32 [n,H,W] in [0,1] -> double [n] on device."""
@@ -110,42 +126,11 @@ class LPIPSVGG(_Backbone):
         self._forward(img, ref, clip, None, layers)
         return layers
 
-    def saturation(self):
-        """Output runs that left the exact range of the arithmetic mode's activation format since the last call (the counter is
-        cleared); waits for the current stream."""
-        c = ctypes.c_int64(0)
-        _lib.check(self.lib.evr_lpips_vgg_saturation(self.handle, ctypes.byref(c), _lib.stream_ptr()), 'evr_lpips_vgg_saturation')
-        return int(c.value)
 
-
-class DISTS(_Backbone):
-    """pyiqa.create_metric('dists') stand-in on the GPU (evr_dists_*): same call shape as LPIPSVGG, on the same VGG-16 trunk.
-
-    max_pairs: frame pairs per pass (0: as many as keep the handle's two activation buffers within 1 GiB); a call with more pairs
-    runs in passes."""
+class DISTS(_VggTrunkMetric):
+    """pyiqa.create_metric('dists') stand-in on the GPU (evr_dists_*): same call shape as LPIPSVGG, on the same VGG-16 trunk."""
     _entry = 'evr_dists'
-    MIN_SIDE = 16           # the backbone's kernels run down to the 1x1 maps of a 16x16 frame (pyiqa would accept smaller frames)
-
-    def __init__(self, state_dict, max_pairs=0):
-        self._create(state_dict, int(max_pairs))
-
-    @classmethod
-    def too_small(cls, H, W):
-        """The message of the exception `dists` raises on frames of this size, or None where it is defined."""
-        if min(H, W) >= cls.MIN_SIDE:
-            return None
-        return f"dists needs frames of at least {cls.MIN_SIDE}x{cls.MIN_SIDE} pixels on this VGG-16 trunk, got {H}x{W}"
-
-    def _forward(self, img, ref, clip, out, stages):
-        img, ref, out = self._inputs(img, ref, out)
-        assert img.dtype == ref.dtype == torch.float32
-        n, H, W = img.shape
-        if self.too_small(H, W):
-            raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
-        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n
-        _lib.check(self.lib.evr_dists_forward(self.handle, _lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0,
-                                              _lib.ptr(out), _lib.ptr(stages), _lib.stream_ptr()), 'evr_dists_forward')
-        return out
+    _too_small = "dists needs frames of at least {m}x{m} pixels on this VGG-16 trunk, got {H}x{W}"
 
     def __call__(self, img, ref, clip=True, out=None):
         """img, ref: cuda fp32 [n,H,W] in [0,1] -> double [n] on device: 1 - (D1 + D2)."""
@@ -158,8 +143,4 @@ class DISTS(_Backbone):
         self._forward(img, ref, clip, None, stages)
         return stages
 
-    def saturation(self):
-        """As LPIPSVGG.saturation()."""
-        c = ctypes.c_int64(0)
-        _lib.check(self.lib.evr_dists_saturation(self.handle, ctypes.byref(c), _lib.stream_ptr()), 'evr_dists_saturation')
-        return int(c.value)
+

@@ -2,17 +2,14 @@
 synthetic weights, and the `-qm dists` path of the tracker and of evaluate().  Parity with pyiqa itself is unpinned
 (tests/test_dists_pins.py)."""
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import dists_ref as R
-from conftest import ROOT
 from test_gpu_nriqa import _compare_lines, _queue_lines, _write_tree
+from vgg_metric_common import _bound, _cuda, _feed, _frames, BATCHES, run_child, write_weights_file
 
 pytestmark = pytest.mark.gpu
 
@@ -20,10 +17,6 @@ pytestmark = pytest.mark.gpu
 # 3x4); 64x80: several tiles, and cout = 64 and cout >= 128 both reach their kernels
 SHAPES = [(16, 16), (37, 53), (64, 80)]
 _REF = {}
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.fixture(scope='module')
@@ -38,12 +31,6 @@ def _reference(sd, H, W):
         img, ref = R.frame_pairs(H, W)
         _REF[(H, W)] = (img, ref, R.dists(sd, img, ref, torch.float64), R.dists(sd, img, ref, torch.float32))
     return _REF[(H, W)]
-
-
-def _bound(want64, want32, scale=1.0):
-    """The issue's gate, `_bound` of tests/test_gpu_lpips_vgg.py: this project's own LPIPS gate (2e-4 relative + 1e-7), or eight times
-    the reference arithmetic's own fp32-against-fp64 error on the same inputs where that is larger."""
-    return scale * np.maximum(2e-4 * np.abs(want64) + 1e-7, 8.0 * np.abs(want32 - want64))
 
 
 def _assert_within(got_total, got_stages, ref, tag, scale=1.0):
@@ -125,6 +112,34 @@ def test_passes_determinism_and_a_handle_that_changes_shape(sd):
     assert one.saturation() == 0 and chunked.saturation() == 0
 
 
+def test_handles_of_both_trunk_metrics_in_one_process_keep_their_state_apart(sd):
+    """An LPIPSVGG and a DISTS handle hold the same trunk code (csrc/vgg_trunk.h): a static, or a plan cached without its handle, would
+    show where they alternate call by call on one stream and change shape.  37x53 is the smallest frame whose floor- and ceil-mode
+    level sizes differ on several levels, 16x24 the smallest where they still agree; five pairs at max_pairs = 2 run in three passes.
+    Every result equals, bit for bit, that of a fresh handle of the same kind given the same call."""
+    from evreal_amd import weights
+    from evreal_amd.lpips import DISTS, LPIPSVGG
+    kinds = ((LPIPSVGG, weights.synth_lpips_vgg_state_dict(seed=3)), (DISTS, sd))
+    big = [_cuda(a) for a in R.frame_pairs(37, 53)]
+    small = [_cuda(a[1:3]) for a in R.frame_pairs(16, 24)]
+    five = [_cuda(a[[0, 1, 2, 3, 1]]) for a in R.frame_pairs(37, 53)]
+    handles = []
+    for max_pairs, calls in ((0, (big, small, big)), (2, (five,))):
+        pair = [cls(w, max_pairs=max_pairs) for cls, w in kinds]
+        got = [m(img, ref) for img, ref in calls for m in pair]      # alternating; nothing waits for a result in between
+        want = []
+        for img, ref in calls:
+            fresh = [cls(w, max_pairs=max_pairs) for cls, w in kinds]
+            want += [m(img, ref) for m in fresh]
+            handles += fresh
+        for k, (g, w) in enumerate(zip(got, want)):
+            g, w = g.cpu().numpy(), w.cpu().numpy()
+            assert g.max() > 1e-3, (max_pairs, k, g)
+            np.testing.assert_array_equal(g, w, err_msg=f'max_pairs={max_pairs} call {k // 2} {kinds[k % 2][0].__name__}')
+        handles += pair
+    assert [m.saturation() for m in handles] == [0] * len(handles)
+
+
 def test_a_side_below_16_and_a_frame_too_large_are_refused(sd):
     from evreal_amd import lib as L
     from evreal_amd.lpips import DISTS
@@ -185,12 +200,7 @@ def test_arithmetic_modes(sd, mode, scale):
     project's image gates for those modes and for h3 (1e-4 against 1e-5).
     Worst measured error / bound on an MI355X: fp32 totals 0.002, stage distances 0.010; mx and mx6 (of their ten-fold bound)
     totals 0.006, stage distances 0.025."""
-    env = dict(os.environ, EVR_ARITH=mode)
-    env.pop('EVR_FP32', None)
-    r = subprocess.run([sys.executable, '-c', _CHILD, ROOT, os.path.join(ROOT, 'tests')], env=env, cwd=ROOT, capture_output=True,
-                       text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    got = json.loads([l for l in r.stdout.splitlines() if l.startswith('RESULT ')][-1][7:])
+    got = run_child(_CHILD, mode)
     total, stages = np.array(got['total']), np.array(got['stages'])
     _assert_construction_zeros(total, stages, 37, 53)
     _assert_within(total, stages, _reference(sd, 37, 53), mode, scale)
@@ -200,32 +210,7 @@ def test_arithmetic_modes(sd, mode, scale):
 @pytest.fixture()
 def weights_file(tmp_path, monkeypatch, sd):
     from evreal_amd import eval_metrics as em
-    path = str(tmp_path / 'dists.pth')
-    torch.save({k: torch.from_numpy(v) for k, v in sd.items()}, path)
-    monkeypatch.setenv(em.DISTS_WEIGHTS_ENV, path)
-    monkeypatch.setattr(em.EvalMetricsTracker, '_dists_cache', [False, None])
-    return path
-
-
-def _frames(H, W, n):
-    rng = np.random.default_rng([H, W, n])
-    yy, xx = np.mgrid[0:H, 0:W]
-    refs = [(0.5 + 0.4 * np.sin(xx / (5.0 + i)) * np.cos(yy / (6.0 + i))).astype(np.float32) for i in range(n)]
-    frames = [(r + 0.2 * rng.standard_normal(r.shape)).astype(np.float32) for r in refs]      # leaves [0,1]: the clip is exercised
-    return frames, refs
-
-
-BATCHES = (3, 5, 2)
-
-
-def _feed(t, frames, refs):
-    idx, k = list(range(len(frames))), 0
-    for n in BATCHES:
-        t.update_batch(idx[k:k + n], _cuda(np.stack(frames[k:k + n])), _cuda(np.stack(refs[k:k + n])),
-                       [0.01 * i for i in idx[k:k + n]], None)
-        k += n
-    t.finalize(idx[-1])
-    return idx
+    return write_weights_file(tmp_path, monkeypatch, sd, 'dists.pth', em.DISTS_WEIGHTS_ENV, '_dists_cache')
 
 
 def test_tracker_books_like_the_reference_queue(tmp_path, weights_file, sd):

@@ -3,16 +3,14 @@ deterministic synthetic weights, and the `-qm lpips-vgg` path of the tracker and
 unpinned (tests/test_lpips_vgg_pins.py)."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import lpips_vgg_ref as R
-from conftest import ROOT
 from test_gpu_nriqa import _compare_lines, _queue_lines, _write_tree
+from vgg_metric_common import _bound, _cuda, _feed, _frames, BATCHES, run_child, write_weights_file
 
 pytestmark = pytest.mark.gpu
 
@@ -20,10 +18,6 @@ pytestmark = pytest.mark.gpu
 # and cout = 64 and cout >= 128 both reach their kernels
 SHAPES = [(16, 16), (37, 53), (64, 80)]
 _REF = {}
-
-
-def _cuda(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.fixture(scope='module')
@@ -38,12 +32,6 @@ def _reference(sd, H, W):
         img, ref = R.frame_pairs(H, W)
         _REF[(H, W)] = (img, ref, R.lpips_vgg(sd, img, ref, torch.float64), R.lpips_vgg(sd, img, ref, torch.float32))
     return _REF[(H, W)]
-
-
-def _bound(want64, want32, scale=1.0):
-    """The issue's gate: this project's own LPIPS gate (2e-4 relative + 1e-7), or eight times the reference arithmetic's own
-    fp32-against-fp64 error on the same inputs where that is larger (the margin rule of tests/test_gpu_wino.py)."""
-    return scale * np.maximum(2e-4 * np.abs(want64) + 1e-7, 8.0 * np.abs(want32 - want64))
 
 
 def _assert_within(got_total, got_layers, ref, tag, scale=1.0):
@@ -173,12 +161,7 @@ def test_arithmetic_modes(sd, mode, scale):
     image gates for those modes and for h3 (1e-4 against 1e-5).
     Worst measured error / bound on an MI355X: fp32 totals below 0.0005, layers 0.002; mx and mx6 (of their ten-fold bound)
     totals 0.001, layers 0.007."""
-    env = dict(os.environ, EVR_ARITH=mode)
-    env.pop('EVR_FP32', None)
-    r = subprocess.run([sys.executable, '-c', _CHILD, ROOT, os.path.join(ROOT, 'tests')], env=env, cwd=ROOT, capture_output=True,
-                       text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    got = json.loads([l for l in r.stdout.splitlines() if l.startswith('RESULT ')][-1][7:])
+    got = run_child(_CHILD, mode)
     img, ref = R.frame_pairs(37, 53, n=2)
     ref4 = (img, ref, R.lpips_vgg(sd, img, ref, torch.float64), R.lpips_vgg(sd, img, ref, torch.float32))
     total, layers = np.array(got['total']), np.array(got['layers'])
@@ -190,32 +173,7 @@ def test_arithmetic_modes(sd, mode, scale):
 @pytest.fixture()
 def weights_file(tmp_path, monkeypatch, sd):
     from evreal_amd import eval_metrics as em
-    path = str(tmp_path / 'lpips_vgg.pth')
-    torch.save({k: torch.from_numpy(v) for k, v in sd.items()}, path)
-    monkeypatch.setenv(em.LPIPS_VGG_WEIGHTS_ENV, path)
-    monkeypatch.setattr(em.EvalMetricsTracker, '_lpips_vgg_cache', [False, None])
-    return path
-
-
-def _frames(H, W, n):
-    rng = np.random.default_rng([H, W, n])
-    yy, xx = np.mgrid[0:H, 0:W]
-    refs = [(0.5 + 0.4 * np.sin(xx / (5.0 + i)) * np.cos(yy / (6.0 + i))).astype(np.float32) for i in range(n)]
-    frames = [(r + 0.2 * rng.standard_normal(r.shape)).astype(np.float32) for r in refs]      # leaves [0,1]: the clip is exercised
-    return frames, refs
-
-
-BATCHES = (3, 5, 2)
-
-
-def _feed(t, frames, refs):
-    idx, k = list(range(len(frames))), 0
-    for n in BATCHES:
-        t.update_batch(idx[k:k + n], _cuda(np.stack(frames[k:k + n])), _cuda(np.stack(refs[k:k + n])),
-                       [0.01 * i for i in idx[k:k + n]], None)
-        k += n
-    t.finalize(idx[-1])
-    return idx
+    return write_weights_file(tmp_path, monkeypatch, sd, 'lpips_vgg.pth', em.LPIPS_VGG_WEIGHTS_ENV, '_lpips_vgg_cache')
 
 
 def test_tracker_books_like_the_reference_queue(tmp_path, weights_file, sd):
