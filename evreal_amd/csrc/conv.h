@@ -61,6 +61,14 @@ struct ConvTaps {
 // Entry 0 describes the first band (bits 16-27 only); entries 1..prog_steps are the steps.
 constexpr int BAND_PROG_MAX = 128;
 
+// Tile map of conv3x3_wide16_kernel<2, true, true, SHORT = true> (conv_route.cpp wide16_tile_map): block b belongs to range b % 8 (blocks
+// b and b + 8 share an XCD), and range x holds count[x] M tiles that lie end to end from pixel pix0[x] on -- full[x] tiles of 256 pixels,
+// then 192-pixel ones.  Every range has `slots` places in the grid (8 * slots * N tiles blocks); a block past its range's count leaves at once.
+struct Wide16Map {
+    int slots;                // 0: no map -- every tile 256 pixels, in grid order (every other kernel, and this one as it was)
+    int pix0[8], full[8], count[8];
+};
+
 struct ConvArgs {
     const float* in0; const float* in1;
     int c0, c1;               // channels of in0/in1 (IN_SINGLE: c1 == 0)
@@ -116,6 +124,7 @@ struct ConvArgs {
     unsigned wdiv_t_mul, wdiv_t_sh, wdiv_tw_mul, wdiv_tw_sh;
     int wino_s2d;             // 0, or 1 + log2(cin / 8): a k5 stride-2 convolution on the Winograd kernel in space-to-depth form (wgt_wino from its s2d weights)
     int wino_order;           // 1: items of a launch ordered 8 tile blocks x 4 column blocks per XCD round (wino.hip); 0: column block fastest
+    Wide16Map w16map;         // ConvLSTM gate launches on the skewed 256 x 256 form: the plan's tile map (conv_plan_wide16_map); slots == 0: none
 };
 // A split launch has at most 512 blocks (one per resident slot) of 64 KB of partial accumulators each
 constexpr size_t KSPLIT_WS_BYTES = (size_t)512 * 4 * 16 * 64 * 16;
@@ -438,6 +447,8 @@ int launch_conv_igemm_m6(const ConvArgs& a, const ConvArgs* d_args, int kc, int 
 int64_t conv_wide16_alt_launches();
 // ... and of conv3x3_wide16_kernel, either form, with the trimmed prologue / epilogue (TAIL; EVR_WIDE16_TAIL=0: none)
 int64_t conv_wide16_tail_launches();
+// ... and of the skewed 256 x 256 form with at least one 192-pixel tile in its map (ConvArgs::w16map; EVR_WIDE16_SHORT=0: none)
+int64_t conv_wide16_short_launches();
 // Winograd F(2x2, 3x3) path of the exact-fp32 mode (wino.hip; EVR_WINO=0: never): host-side weight transform (w = [n_gemm][9][cin]
 // in prep_conv2d's order; lstm_hidden > 0: ConvLSTM row permutation), the eligibility test of a launch plan, the launch
 void wino_pack_weights(const std::vector<float>& w, int n_gemm, int cin, int lstm_hidden, std::vector<float>& out);

@@ -48,6 +48,7 @@
 #include "packed.h"
 #include <atomic>
 #include <initializer_list>
+#include <type_traits>
 
 // This file is compiled once per split arithmetic (build.py): EVR_ARITH = 2 -- f16 + MX-fp8 on PACKED tensors, plus the
 // exact-fp32 kernels -- EVR_ARITH = 3 -- three f16 products on H2 tensors -- and EVR_ARITH = 4 -- f16 + MX-fp6 on P6 tensors, the
@@ -2102,10 +2103,18 @@ static_assert(check(1, 4) && check(1, 5) && check(2, 4) && check(2, 5) && check(
 //   h stores   lanes (p, o) and (p, o ^ 1) trade halves (v_permlane16_swap: partners share their pixel, so they are active together):
 //              the even lane stores 16 B of hi, the odd lane 16 B of lo -- 8 stores per lane where there were 16, same bytes
 // (tried with these and dropped, DESIGN.md section 8: a c_prev warm-up piece in the last step, static priority for the late half)
-template <int WN, bool ALT = false, bool TAIL = false>
+// SHORT (<2, true, true> only; EVR_WIDE16_SHORT=0: without): the block's tile comes from the plan's map (ConvArgs::w16map, conv_route.cpp
+// wide16_tile_map) and is 256 or 192 contiguous pixels.  In a 192-pixel tile a wave owns three 16-pixel blocks at a stride of 48: its main
+// loop is the same schedule without set D (its fragment reads and MFMAs; 72 MFMAs per step), and D's neighbour decode, c_prev loads and
+// finish() are skipped -- all under block-uniform tests; the loop itself is compiled twice (skewed_loop(FULL)) and picked once per block.
+// Band and weight requests are the full tile's (64 band rows fetched and not read), so the request counts alt16::check models stay what
+// they are.  A pixel's accumulators see the same MFMAs in the same order in either tile, whichever wave holds them; the one rounding that
+// depended on the block a pixel sat in is pinned (finish(), cd): the same bits.
+template <int WN, bool ALT = false, bool TAIL = false, bool SHORT = false>
 __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvArgs* __restrict__ ap) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const ConvArgs& a = *ap;
+    static_assert(!SHORT || (WN == 2 && ALT && TAIL), "192-pixel tiles: the skewed 256 x 256 form with the trimmed tail only");
     constexpr bool T_PRO = TAIL, T_ST16 = TAIL && FMT == 2;
     constexpr int WM = 4, NW = WM * WN, SP = 8, NF = 8;
     constexpr bool SINGLE = (WN == 1);
@@ -2128,14 +2137,27 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
     const int hw = H * W;
     const int M = a.n * hw;
     const int ntiles = a.cout / TN;
-    int lin;
-    {   // XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8)
+    int ntile, m0;
+    [[maybe_unused]] bool rows4 = true;                        // block-uniform: a 256-pixel tile (four 16-pixel blocks per wave); false: 192 (three)
+    if constexpr (SHORT) {
+        // the plan's map: range x = the blocks of one XCD, `slots` M tiles wide in the grid; its tiles lie end to end from pix0[x]
+        const Wide16Map& tm = a.w16map;
+        const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
+        const int mt = idx / ntiles, nf = tm.full[xcd];
+        ntile = idx - mt * ntiles;
+        if (mt >= tm.count[xcd]) return;                       // (a place past the range's last tile: the whole block leaves)
+        rows4 = mt < nf;
+        m0 = tm.pix0[xcd] + (rows4 ? mt * TM : nf * TM + (mt - nf) * (TM - 64));
+    } else {   // XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8)
         const int total = gridDim.x, bid = blockIdx.x;
         const int q = total >> 3, rr = total & 7, xcd = bid & 7, idx = bid >> 3;
-        lin = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
+        const int lin = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
+        ntile = lin % ntiles;
+        m0 = (lin / ntiles) * TM;
     }
-    const int ntile = lin % ntiles, mtile = lin / ntiles;
-    const int m0 = mtile * TM, n0 = ntile * TN;
+    const int n0 = ntile * TN;
+    const bool haveD = !SHORT || rows4;                        // the wave's fourth pixel block exists
+    const int wstride = haveD ? 64 : 48;                       // pixels (and band rows) from one wave of a half to the next
     const int n0w = n0 + wni * 128;
     const int c0 = a.c0, c1 = a.c1;
     const int nchunks = (c0 + (a.in_mode == IN_CAT ? c1 : 0)) / 32;
@@ -2198,7 +2220,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
         if constexpr (!(EPI_ABLATE & 1024)) b4 = *(const f4*)(a.bias + n0w + 16 * f + 4 * o);
         accA[f] = b4; accB[f] = b4; accC[f] = b4; accD[f] = b4;
     }
-    const int mP = m0 + wmi * 64 + p;                          // the lane's pixel of block 0; block b: + 16b
+    const int mP = m0 + wmi * wstride + p;                     // the lane's pixel of block 0; block b: + 16b
     auto neighbours = [&](int m) -> unsigned {   // validity of the pixel's 9 neighbours (bit t = tap (t/3 - 1, t%3 - 1))
         unsigned vm = 0;
         if constexpr (EPI_ABLATE & 1024) return 0x1ffu;
@@ -2213,7 +2235,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
         }
         return vm;
     };
-    const unsigned vmA = neighbours(mP), vmB = neighbours(mP + 16), vmC = neighbours(mP + 32), vmD = neighbours(mP + 48);
+    const unsigned vmA = neighbours(mP), vmB = neighbours(mP + 16), vmC = neighbours(mP + 32), vmD = haveD ? neighbours(mP + 48) : 0u;
 
     if (tid < SP) lds[NBUF * A_F4 + 2 * B_F4 + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (!T_PRO) {
@@ -2227,6 +2249,9 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
         const bool late = wni != 0;                                        // wave-uniform
         if (late) asm volatile("s_barrier" ::: "memory");                 // alt16::idle_barriers(1): the late half sits out segment 0
         static_assert(alt16::idle_barriers(0) == 0 && alt16::idle_barriers(1) == 1);
+        // FULL: the wave's four pixel blocks; !FULL (a 192-pixel tile): blocks A..C at a wave stride of 48 band rows, nothing of set D
+        auto skewed_loop = [&](auto full_c) __attribute__((always_inline)) {
+        constexpr bool FULL = decltype(full_c)::value;
         for (int c = 0; c < nchunks; ++c) {
             const int pa = c & 1;
 #pragma unroll
@@ -2243,19 +2268,21 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
                 __builtin_amdgcn_sched_barrier(0);
                 const int ab = pa ^ ((t / 3) & 1);
                 const float4* lb = &lds[NBUF * A_F4 + (pa ^ (t & 1)) * B_F4 + (wni * 128 + p) * SP];
-                int l0 = wmi * 64 + p + (t % 3);
+                int l0 = wmi * (FULL ? 64 : 48) + p + (t % 3);
                 asm volatile("" : "+v"(l0));
                 const int xs = swz<32>(l0);
                 int iA = ab * A_ROWS + l0, iB = iA + 16, iC = iA + 32, iD = iA + 48;
                 if (t != 4) {
                     iA = ((vmA >> t) & 1u) ? iA : ZROW; iB = ((vmB >> t) & 1u) ? iB : ZROW;
-                    iC = ((vmC >> t) & 1u) ? iC : ZROW; iD = ((vmD >> t) & 1u) ? iD : ZROW;
+                    iC = ((vmC >> t) & 1u) ? iC : ZROW;
+                    if constexpr (FULL) iD = ((vmD >> t) & 1u) ? iD : ZROW;
                 }
                 auto ld = [&](const float4* q) { return __builtin_bit_cast(f16x8, *q); };
                 const f16x8 xhA = ld(&lds[iA * SP + (hs ^ xs)]), xlA = ld(&lds[iA * SP + ((hs | 2) ^ xs)]);
                 const f16x8 xhB = ld(&lds[iB * SP + (hs ^ xs)]), xlB = ld(&lds[iB * SP + ((hs | 2) ^ xs)]);
                 const f16x8 xhC = ld(&lds[iC * SP + (hs ^ xs)]), xlC = ld(&lds[iC * SP + ((hs | 2) ^ xs)]);
-                const f16x8 xhD = ld(&lds[iD * SP + (hs ^ xs)]), xlD = ld(&lds[iD * SP + ((hs | 2) ^ xs)]);
+                [[maybe_unused]] f16x8 xhD, xlD;
+                if constexpr (FULL) { xhD = ld(&lds[iD * SP + (hs ^ xs)]); xlD = ld(&lds[iD * SP + ((hs | 2) ^ xs)]); }
                 f16x8 wh = ld(lb + wq_h), wl = ld(lb + wq_l);
                 // the fragments are in registers before the barrier: the band may be replaced from the next segment on
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -2268,7 +2295,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
                     accA[f] = mma16_h3(accA[f], wh, wl, xhA, xlA);
                     accB[f] = mma16_h3(accB[f], wh, wl, xhB, xlB);
                     accC[f] = mma16_h3(accC[f], wh, wl, xhC, xlC);
-                    accD[f] = mma16_h3(accD[f], wh, wl, xhD, xlD);
+                    if constexpr (FULL) accD[f] = mma16_h3(accD[f], wh, wl, xhD, xlD);
                     __builtin_amdgcn_sched_barrier(0);
                     wh = whn; wl = wln;
                 }
@@ -2277,6 +2304,10 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
                 if (alt16::barrier_after_mma(late ? 1 : 0, 9 * c + t, 9 * nchunks)) asm volatile("s_barrier" ::: "memory");
             }
         }
+        };
+        if constexpr (SHORT) {
+            if (rows4) skewed_loop(std::true_type{}); else skewed_loop(std::false_type{});
+        } else skewed_loop(std::true_type{});
     } else
     for (int c = 0; c < nchunks; ++c) {
         const int pa = c & 1;
@@ -2336,7 +2367,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
     const float sc = a.acc_scale;
     const unsigned hid = (unsigned)a.hidden;
     const int ch0 = (n0w >> 2) + 4 * o;
-    const bool okA = mP < M, okB = mP + 16 < M, okC = mP + 32 < M, okD = mP + 48 < M;
+    const bool okA = mP < M, okB = mP + 16 < M, okC = mP + 32 < M, okD = haveD && mP + 48 < M;
     const unsigned rA = (unsigned)(okA ? mP : 0) * hid, rB = (unsigned)(okB ? mP + 16 : 0) * hid;
     const unsigned rC = (unsigned)(okC ? mP + 32 : 0) * hid, rD = (unsigned)(okD ? mP + 48 : 0) * hid;
     f4 cpA[2], cpB[2], cpC[2], cpD[2];
@@ -2347,9 +2378,14 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
         cpA[s] = lds_c ? *(const f4*)(a.state + rA + ch0 + 16 * s) : z;
         cpB[s] = lds_c ? *(const f4*)(a.state + rB + ch0 + 16 * s) : z;
         cpC[s] = lds_c ? *(const f4*)(a.state + rC + ch0 + 16 * s) : z;
-        cpD[s] = lds_c ? *(const f4*)(a.state + rD + ch0 + 16 * s) : z;
+        cpD[s] = (lds_c && haveD) ? *(const f4*)(a.state + rD + ch0 + 16 * s) : z;
     }
-    auto finish = [&](const f4 (&acc)[NF], const f4 (&cp)[2], unsigned row, bool ok) {
+    // (cd: f * c + i * g is contracted to ONE fma, and hipcc picks per call site which product stays rounded: in every instantiation of this
+    // kernel as it was it is fma(i, g, f * c) for a wave's blocks A and B and fma(c, f, i * g) for C and D -- the two differ in the last bit of
+    // c for about a fifth of the values.  With 64-pixel wave tiles on a 64-pixel grid "C or D" is bit 5 of the pixel index.  The skewed loop's
+    // instantiations say so explicitly -- the SHORT one by that bit, since its 48-pixel wave tiles put a pixel into another block: the same
+    // bits as every other form; the lock-step and twin forms keep the expression, and the code, they had)
+    auto finish = [&](const f4 (&acc)[NF], const f4 (&cp)[2], unsigned row, bool ok, [[maybe_unused]] bool cd) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             f4 cn, hn;
@@ -2360,7 +2396,8 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
                 const float gf = sigmoid_t<true>(acc[2 + s][j] * sc);
                 const float go = sigmoid_t<true>(acc[4 + s][j] * sc);
                 const float gc = tanh_t<true>(acc[6 + s][j] * sc);
-                cn[j] = __fadd_rn(__fmul_rn(gf, cp[s][j]), __fmul_rn(gi, gc));
+                if constexpr (ALT) cn[j] = cd ? __builtin_fmaf(cp[s][j], gf, gi * gc) : __builtin_fmaf(gi, gc, gf * cp[s][j]);
+                else cn[j] = __fadd_rn(__fmul_rn(gf, cp[s][j]), __fmul_rn(gi, gc));
                 hn[j] = go * tanh_t<true>(cn[j]);
             }
             [[maybe_unused]] unsigned h16[4];
@@ -2384,14 +2421,14 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
             }
         }
     };
-    finish(accA, cpA, rA, okA);
-    finish(accB, cpB, rB, okB);
-    finish(accC, cpC, rC, okC);
-    finish(accD, cpD, rD, okD);
+    finish(accA, cpA, rA, okA, SHORT ? (mP & 32) != 0 : false);
+    finish(accB, cpB, rB, okB, SHORT ? ((mP + 16) & 32) != 0 : false);
+    finish(accC, cpC, rC, okC, SHORT ? ((mP + 32) & 32) != 0 : true);
+    if (haveD) finish(accD, cpD, rD, okD, SHORT ? ((mP + 48) & 32) != 0 : true);
 #endif
 }
 
-static std::atomic<int64_t> g_wide16_alt_launches{0}, g_wide16_tail_launches{0};
+static std::atomic<int64_t> g_wide16_alt_launches{0}, g_wide16_tail_launches{0}, g_wide16_short_launches{0};
 
 #endif   // EVR_ARITH == 3
 
@@ -2777,6 +2814,7 @@ using namespace EVR_ANS;
 #if EVR_ARITH == 3
 int64_t conv_wide16_alt_launches() { return g_wide16_alt_launches.load(std::memory_order_relaxed); }
 int64_t conv_wide16_tail_launches() { return g_wide16_tail_launches.load(std::memory_order_relaxed); }
+int64_t conv_wide16_short_launches() { return g_wide16_short_launches.load(std::memory_order_relaxed); }
 #endif
 
 // one launch with the route's grid, block and dynamic LDS
@@ -2823,9 +2861,9 @@ static int launch_c16_rows(const ConvRoute& r, const ConvArgs* d_args, hipStream
     if (const int e = c16_lds_attribute({(const void*)conv3x3_c16_rows_kernel<1, RPB, NSRC, HALFW>}, attr_done)) return e;
     return launch_routed(conv3x3_c16_rows_kernel<1, RPB, NSRC, HALFW>, r, stream, d_args, img, r.rseg, r.nseg, r.nstrips);
 }
-template <int WN, bool ALT, bool TAIL>
+template <int WN, bool ALT, bool TAIL, bool SHORT = false>
 static int launch_wide16(const ConvRoute& r, const ConvArgs* d_args, hipStream_t stream) {
-    if (const int e = launch_routed(conv3x3_wide16_kernel<WN, ALT, TAIL>, r, stream, d_args)) return e;
+    if (const int e = launch_routed(conv3x3_wide16_kernel<WN, ALT, TAIL, SHORT>, r, stream, d_args)) return e;
     if (ALT) g_wide16_alt_launches.fetch_add(1, std::memory_order_relaxed);
     if (TAIL) g_wide16_tail_launches.fetch_add(1, std::memory_order_relaxed);
     return EVR_OK;
@@ -2914,8 +2952,15 @@ int EVR_LAUNCH_NAME(const ConvArgs& a, const ConvArgs* d_args, int kc, int wm, i
 #if EVR_ARITH == 3
     case CONV_WIDE16:
         if (r.wn == 1) return r.tail ? launch_wide16<1, false, true>(r, d_args, stream) : launch_wide16<1, false, false>(r, d_args, stream);
-        if (r.alt) return r.tail ? launch_wide16<2, true, true>(r, d_args, stream) : launch_wide16<2, true, false>(r, d_args, stream);
-        return r.tail ? launch_wide16<2, false, true>(r, d_args, stream) : launch_wide16<2, false, false>(r, d_args, stream);
+        if (r.alt && !r.short16) return r.tail ? launch_wide16<2, true, true>(r, d_args, stream) : launch_wide16<2, true, false>(r, d_args, stream);
+        if (!r.short16) return r.tail ? launch_wide16<2, false, true>(r, d_args, stream) : launch_wide16<2, false, false>(r, d_args, stream);
+        {   // the plan's tile map: 192-pixel tiles among the 256-pixel ones (counted when the map holds one)
+            int nshort = 0;
+            for (int x = 0; x < 8; ++x) nshort += a.w16map.count[x] - a.w16map.full[x];
+            if (const int e = launch_wide16<2, true, true, true>(r, d_args, stream)) return e;
+            if (nshort > 0) g_wide16_short_launches.fetch_add(1, std::memory_order_relaxed);
+            return EVR_OK;
+        }
 #endif
     case CONV_WIDE: case CONV_BAND: {      // the 3x3 band layers: ConvLSTM gates, plain layers, transposed decoders -- 256-pixel tiles or 128
         const bool wide = r.family == CONV_WIDE;

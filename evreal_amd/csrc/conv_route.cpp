@@ -3,6 +3,8 @@
 // Which object carries a kernel follows from a.x3, which each object of conv.hip requires to be its own: 3 = h3 (c16, wide16),
 // 4 = m6, 0 / 2 = mx (the exact-fp32 implicit GEMM with its REGSTAGE ConvLSTM and KC = 16 cases).
 #include "conv_route.h"
+#include <algorithm>
+#include <vector>
 
 namespace evr {
 
@@ -31,6 +33,11 @@ ConvKnobs conv_knobs_from(const char* (*get)(const char*)) {
     k.mfma16 = num("EVR_MFMA16", 1);
     k.wide16_alt = num("EVR_WIDE16_ALT", 1);
     k.wide16_tail = num("EVR_WIDE16_TAIL", 1);
+    if (const char* e = get("EVR_WIDE16_SHORT")) {
+        if (!strcmp(e, "all")) k.wide16_short = WIDE16_SHORT_ALL;
+        else if (!strncmp(e, "last=", 5)) { k.wide16_short = WIDE16_SHORT_LAST; k.wide16_short_last = atoi(e + 5) > 0 ? atoi(e + 5) : 0; }
+        else k.wide16_short = atoi(e) != 0 ? WIDE16_SHORT_RULE : WIDE16_SHORT_OFF;
+    }
     k.c16_blocks = num("EVR_C16_BLOCKS", 3);
     k.c16_out_nbuf = num("EVR_C16_OUT", 2); k.c16_out_blocks = second("EVR_C16_OUT", 3);
     k.c16_zr_nbuf = num("EVR_C16_ZR", 2); k.c16_zr_blocks = second("EVR_C16_ZR", 3);
@@ -103,7 +110,7 @@ ConvRoute route_band(ConvRoute r, const ConvArgs& a, bool lstm, bool grouped, in
     return r;
 }
 
-// conv3x3_wide_kernel<LSTM, WN, GROUPED, PHASES> / conv3x3_wide16_kernel<WN, ALT, TAIL>
+// conv3x3_wide_kernel<LSTM, WN, GROUPED, PHASES> / conv3x3_wide16_kernel<WN, ALT, TAIL, SHORT> (SHORT and its grid: conv_route below)
 ConvRoute route_wide(ConvRoute r, int family, const ConvArgs& a, bool lstm, int wn, bool grouped, int phases) {
     const int M = a.n * a.hm * a.wm;
     const int total = ((M + 255) / 256) * (a.cout / (128 * wn));
@@ -341,6 +348,9 @@ ConvRoute conv_route(const ConvArgs& a, int kc, int wm, int nb, const ConvKnobs&
                     r.alt = !twin && k.wide16_alt;
                     // the trimmed prologue / epilogue (TAIL, above the kernel); EVR_WIDE16_TAIL=0: the tile's fixed part as it was
                     r.tail = k.wide16_tail != 0;
+                    // 192-pixel tiles in the ragged last round: the plan's map (conv_plan_wide16_map below; EVR_WIDE16_SHORT=0: never one)
+                    r.short16 = r.alt && r.tail && a.w16map.slots > 0;
+                    if (r.short16) r.grid = 8u * (unsigned)a.w16map.slots * (unsigned)(a.cout / 256);
                     return r;
                 }
             }
@@ -409,6 +419,98 @@ ConvRoute conv_route(const ConvArgs& a, int kc, int wm, int nb, const ConvKnobs&
     if (mode != 0 && wmnb) return route_igemm(r, a, 32, wm, nb, false, false, false, 2);
     if (mx_object && wmnb && (kc == 32 || (kc == 16 && nb == 1))) return route_igemm(r, a, kc, wm, nb, false, false, false, 0);
     return route_none(r, ROUTE_NO_KERNEL);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The tile map of conv3x3_wide16_kernel<2, true, true>.  The form holds ONE block per CU and its tiles are all alike, so a launch of T
+// tiles on C units takes ceil(T / C) rounds however empty the last one is (profiles/r10_tail_pricing.txt: 5.50, 5.67 and 5.95 rounds cost
+// the same).  The mixed map spends the same whole number of rounds R on R * C blocks instead: as many 256-pixel tiles as before minus the
+// ones that four 192-pixel tiles replace three of, so that the last round is full and part of the blocks finish early everywhere.
+namespace {
+
+// `slots` places per XCD range, the last shorts[x] of them 192 pixels: walk the M pixels through the ranges in order
+Wide16Map fill_ranges(int64_t M, int slots, const int (&shorts)[8]) {
+    Wide16Map m = {};
+    m.slots = slots;
+    int64_t pix = 0;
+    for (int x = 0; x < 8; ++x) {
+        m.pix0[x] = (int)pix;
+        int64_t nf = (M - pix + 255) / 256;
+        if (nf > slots - shorts[x]) nf = slots - shorts[x];
+        pix = pix + 256 * nf < M ? pix + 256 * nf : M;
+        int64_t ns = (M - pix + 191) / 192;
+        if (ns > shorts[x]) ns = shorts[x];
+        pix = pix + 192 * ns < M ? pix + 192 * ns : M;
+        m.full[x] = (int)nf; m.count[x] = (int)(nf + ns);
+    }
+    return m;      // (pix == M when the capacity of the ranges covers M: the callers see to that)
+}
+
+}  // namespace
+
+double wide16_makespan(const Wide16Map& m, int nt, int cus_per_xcd, double rho) {
+    double worst = 0.0;
+    std::vector<double> free_at((size_t)(cus_per_xcd > 0 ? cus_per_xcd : 1));
+    for (int x = 0; x < 8; ++x) {
+        std::fill(free_at.begin(), free_at.end(), 0.0);
+        for (int t = 0; t < m.count[x]; ++t)
+            for (int j = 0; j < nt; ++j) {
+                auto cu = std::min_element(free_at.begin(), free_at.end());
+                *cu += t < m.full[x] ? 1.0 : rho;
+            }
+        const double end = *std::max_element(free_at.begin(), free_at.end());
+        if (end > worst) worst = end;
+    }
+    return worst;
+}
+
+Wide16Plan wide16_tile_map(int64_t M, int nt, int cus, int mode, int last_k) {
+    Wide16Plan p = {};
+    p.mtiles = (int)((M + 255) / 256);
+    if (M <= 0 || nt <= 0 || mode == WIDE16_SHORT_OFF) return p;
+    int shorts[8];
+    if (mode == WIDE16_SHORT_ALL) {
+        const int slots = (int)(((M + 191) / 192 + 7) / 8);
+        for (int& s : shorts) s = slots;
+        p.map = fill_ranges(M, slots, shorts);
+    } else if (mode == WIDE16_SHORT_LAST) {
+        int slots = 1;
+        const auto cap = [&](int sl) { const int s = last_k < sl ? last_k : sl; return 8 * (256LL * (sl - s) + 192LL * s); };
+        while (cap(slots) < M) ++slots;
+        for (int& s : shorts) s = last_k < slots ? last_k : slots;
+        p.map = fill_ranges(M, slots, shorts);
+    } else {
+        // the rule: the smallest whole number of rounds R whose R * cus blocks -- Mt = R * cus / nt M tiles of at most 256 pixels, the same
+        // number in every XCD range -- cover M; then b tiles can give up 64 pixels each
+        if (cus <= 0 || cus % (8 * nt) != 0) return p;
+        const int64_t per_round = cus / nt;
+        const int64_t R = (M + 256 * per_round - 1) / (256 * per_round), Mt = R * per_round;
+        int64_t b = (256 * Mt - M) / 64;
+        if (b > Mt) b = Mt;
+        // (nothing to give up; or M so small that even 192-pixel tiles leave some of the Mt without a pixel: the uniform map)
+        if (b == 0 || 256 * (Mt - b) + 192 * b - M >= 192 || Mt * nt > (1LL << 30)) return p;
+        for (int x = 0; x < 8; ++x) shorts[x] = (int)(b / 8 + (x < b % 8 ? 1 : 0));
+        const Wide16Map m = fill_ranges(M, (int)(Mt / 8), shorts);
+        // whole rounds of the uniform map (its XCD ranges hold total / 8 blocks, the first total % 8 of them one more)
+        const int64_t total = (int64_t)p.mtiles * nt;
+        p.makespan_uniform = (double)(((total + 7) / 8 + cus / 8 - 1) / (cus / 8));
+        p.makespan = wide16_makespan(m, nt, cus / 8, WIDE16_SHORT_RHO);
+        if (!(p.makespan <= p.makespan_uniform - WIDE16_SHORT_MARGIN)) return p;
+        p.map = m;
+    }
+    p.mtiles = 0; p.nshort = 0;
+    for (int x = 0; x < 8; ++x) { p.mtiles += p.map.count[x]; p.nshort += p.map.count[x] - p.map.full[x]; }
+    return p;
+}
+
+void conv_plan_wide16_map(ConvArgs& a, int kc, int wm, int nb, int cus, const ConvKnobs& k) {
+    a.w16map = {};
+    if (k.wide16_short == WIDE16_SHORT_OFF) return;
+    const ConvRoute r = conv_route(a, kc, wm, nb, k);
+    if (r.family != CONV_WIDE16 || r.wn != 2 || !r.alt || !r.tail) return;
+    // (the rule keeps clear of everything an explicit EVR_WIDE_MIN moves: the shapes the tests pin run the map they always had)
+    if (k.wide16_short == WIDE16_SHORT_RULE && k.wide_min_set) return;
+    a.w16map = wide16_tile_map((int64_t)a.n * a.hm * a.wm, a.cout / 256, cus, k.wide16_short, k.wide16_short_last).map;
 }
 
 }  // namespace evr

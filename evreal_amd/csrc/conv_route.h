@@ -7,6 +7,7 @@
 namespace evr {
 
 constexpr int KSPLIT_RUNS_MAX = 8;      // what conv_ksplit_epi4_kernel<..., 8> sums; ksplit_cap clamps EVR_KSPLIT / EVR_KSPLIT_SMALL to it
+enum Wide16ShortMode { WIDE16_SHORT_OFF = 0, WIDE16_SHORT_RULE = 1, WIDE16_SHORT_ALL = 2, WIDE16_SHORT_LAST = 3 };
 
 // Every switch of the conv dispatch (README "Run-time switches" lists them in this order).  Fields hold the values in force:
 // defaults that depend on another switch being set are resolved where the table is filled (conv_knobs_from).
@@ -34,6 +35,8 @@ struct ConvKnobs {
     int mfma16 = 1;               // EVR_MFMA16=0: the ConvLSTM gate launches on the 32x32x16 form (h3 object)
     int wide16_alt = 1;           // EVR_WIDE16_ALT=0: the 256 x 256 16x16x32 form on its lock-step loop
     int wide16_tail = 1;          // EVR_WIDE16_TAIL=0: the tile's fixed part as it was (no trimmed prologue / epilogue)
+    int wide16_short = WIDE16_SHORT_RULE;   // EVR_WIDE16_SHORT: 0 never a 192-pixel tile (A/B), unset / 1 the rule of wide16_tile_map, "all" every tile
+    int wide16_short_last = 0;    //   short, "last=<k>" the last k M tiles of every XCD range short (the last two: tests, and measuring a short tile)
     // ---- FireNet's 16-channel layers (h3 object)
     int c16_blocks = 3;           // EVR_C16_BLOCKS (A/B: blocks per CU of the one-source form)
     int c16_out_nbuf = 2, c16_out_blocks = 3;     // EVR_C16_OUT=<nbuf>,<blocks>: the candidate convolution (nbuf 4 = the ring of four)
@@ -71,7 +74,7 @@ enum ConvFamily {
     CONV_BANDK,             // conv_bandk_kernel<KW, NB>
     CONV_BAND,              // conv3x3_band_kernel<4, 2, LSTM, GROUPED, false, PHASES, ks > 1> (+ the split-K epilogue)
     CONV_WIDE,              // conv3x3_wide_kernel<LSTM, WN, GROUPED, PHASES>
-    CONV_WIDE16,            // conv3x3_wide16_kernel<WN, ALT, TAIL>
+    CONV_WIDE16,            // conv3x3_wide16_kernel<WN, ALT, TAIL, SHORT>
     CONV_IGEMM              // conv_igemm_kernel<KC, WM, NB, LSTM, GROUPED, REGSTAGE, X3>
 };
 enum ConvRouteErr { ROUTE_OK = 0, ROUTE_LSTM_KC, ROUTE_NO_GROUPED, ROUTE_NO_KERNEL };
@@ -80,6 +83,7 @@ struct ConvRoute {
     // template selectors (those of `family` are meaningful)
     int kc, wm, nb, x3, phases, wn, kw, rpb, nsrc, nbuf;
     bool lstm, grouped, regstage, alt, tail, halfw;
+    bool short16;                   // CONV_WIDE16: the plan carries a tile map (ConvArgs::w16map) -- the grid is the map's, the kernel the SHORT one
     unsigned grid, block;
     size_t lds;                     // dynamic LDS bytes
     int ks;                         // split-K runs per tile (1: no split, no epilogue launch)
@@ -90,5 +94,24 @@ struct ConvRoute {
 
 bool conv_c16_eligible(const ConvArgs& a, int kc);
 ConvRoute conv_route(const ConvArgs& a, int kc, int wm, int nb, const ConvKnobs& k);
+
+// ---- the tile map of the skewed 256 x 256 ConvLSTM form (conv3x3_wide16_kernel<2, true, true>): 192-pixel tiles fill the ragged last round
+// A 192-pixel tile's time in units of a 256-pixel tile's (profiles/r10_layer_times.txt, section B: every tile forced short at 55
+// sequences, where both maps fill their rounds -- 0.787 / 0.791 / 0.767 on enc0 / enc1 / enc2.rec), and how many full-tile times the
+// mixed map's predicted makespan must lie below the uniform map's whole rounds before a launch takes it
+constexpr double WIDE16_SHORT_RHO = 0.79;
+constexpr double WIDE16_SHORT_MARGIN = 0.15;
+struct Wide16Plan {
+    Wide16Map map;                  // slots == 0: the uniform map
+    int mtiles, nshort;             // M tiles in all, and how many of them are 192 pixels
+    double makespan, makespan_uniform;      // predicted, in full-tile times (rule mode only)
+};
+// M pixels, nt N tiles per M tile, `cus` compute units (one block each); mode / last_k: ConvKnobs::wide16_short / wide16_short_last
+Wide16Plan wide16_tile_map(int64_t M, int nt, int cus, int mode, int last_k);
+// blocks of one XCD range handed in grid order to cus_per_xcd units, a full tile 1 and a short one rho: when the last one ends
+double wide16_makespan(const Wide16Map& m, int nt, int cus_per_xcd, double rho);
+// plan time: a.w16map for the launch conv_route() gives this plan (none unless it is the skewed form with the trimmed tail; the rule
+// also leaves launches under an explicit EVR_WIDE_MIN alone).  conv_route() then reads the map back from the plan
+void conv_plan_wide16_map(ConvArgs& a, int kc, int wm, int nb, int cus, const ConvKnobs& k);
 
 }  // namespace evr

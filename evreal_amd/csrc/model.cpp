@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "conv.h"
+#include "conv_route.h"
 
 using namespace evr;
 
@@ -148,6 +149,7 @@ struct evr_model {
     std::vector<int64_t> prof_n;
     int64_t prof_alt0 = 0;          // conv_wide16_alt_launches() when the profile was enabled
     int64_t prof_tail0 = 0;         // conv_wide16_tail_launches() likewise
+    int64_t prof_short0 = 0;        // conv_wide16_short_launches() likewise
 
     ~evr_model() { release_shape(); for (auto& c : convs) { if (c.d_w) (void)hipFree(c.d_w); if (c.d_b) (void)hipFree(c.d_b); if (c.d_wino) (void)hipFree(c.d_wino);
                                             if (c.d_w2) (void)hipFree(c.d_w2); if (c.d_prog) (void)hipFree(c.d_prog); }
@@ -1634,6 +1636,13 @@ extern "C" int evr_model_reset_states(evr_model* m, int n_seq, int H, int W, evr
         }
         for (auto& c : m->convs) { c.args[0].ksplit_ws = kws; c.args[1].ksplit_ws = kws; }
     }
+    {   // the ConvLSTM gate launches on the skewed 256 x 256 form: 192-pixel tiles where they fill the ragged last round of one block per CU
+        int dev = 0, cus = 0;
+        EVR_HIP(hipGetDevice(&dev));
+        EVR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        for (auto& c : m->convs)
+            for (auto& a : c.args) if (a.epi == EPI_LSTM) conv_plan_wide16_map(a, c.kc, c.wm, c.nb, cus, conv_knobs());
+    }
     // upload the launch plans (a failure here leaves no half-built shape behind: the next reset re-plans)
     std::vector<ConvArgs> all;
     for (auto& c : m->convs) { c.arg_slot = (int)all.size(); all.push_back(c.args[0]); all.push_back(c.args[1]); }
@@ -1847,6 +1856,7 @@ extern "C" int evr_model_profile_enable(evr_model* m, const char* filter) {
     m->prof_filter = filter ? filter : "";
     m->prof_alt0 = conv_wide16_alt_launches();
     m->prof_tail0 = conv_wide16_tail_launches();
+    m->prof_short0 = conv_wide16_short_launches();
     return EVR_OK;
 }
 
@@ -1885,7 +1895,9 @@ extern "C" int evr_model_profile_read(evr_model* m, int max_layers, char* names,
     // since the profile was enabled (no time, no FLOPs -- the layers' own rows carry those)
     // (likewise "kernel.wide16_tail": launches of conv3x3_wide16_kernel, either tile form, with its trimmed prologue / epilogue)
     const struct { const char* name; int64_t n; } kernel_rows[] = {{"kernel.wide16_alt", conv_wide16_alt_launches() - m->prof_alt0},
-                                                                   {"kernel.wide16_tail", conv_wide16_tail_launches() - m->prof_tail0}};
+                                                                   {"kernel.wide16_tail", conv_wide16_tail_launches() - m->prof_tail0},
+                                                                   // ("kernel.wide16_short": launches of the skewed form whose tile map held at least one 192-pixel tile)
+                                                                   {"kernel.wide16_short", conv_wide16_short_launches() - m->prof_short0}};
     for (const auto& kr : kernel_rows) {
         if (m->prof_on && !m->prof_filter.empty() && std::string(kr.name).find(m->prof_filter) != std::string::npos && k < max_layers) {
             snprintf(names + (size_t)k * 64, 64, "%s", kr.name);

@@ -217,7 +217,8 @@ int evr_model_saturation_async(evr_model* model, unsigned* counters_host, int ma
  * A non-empty filter contained in "kernel.wide16_alt" (no layer's name) adds one row of that name: how often this process
  * launched the skewed loop of the 256 x 256 ConvLSTM gate kernel since the profile was enabled (0 ms, 0 FLOPs).  Likewise
  * "kernel.wide16_tail": launches of the 16x16x32 ConvLSTM gate kernel, either tile form, with its trimmed prologue and epilogue
- * (EVR_WIDE16_TAIL=0: none). */
+ * (EVR_WIDE16_TAIL=0: none); "kernel.wide16_short": launches of the skewed 256 x 256 form whose tile map held at least one
+ * 192-pixel tile (EVR_WIDE16_SHORT=0: none). */
 int evr_model_profile_enable(evr_model* m, const char* filter);
 int evr_model_profile_read(evr_model* m, int max_layers, char* names, double* ms, double* flops_per_launch,
                            int64_t* launches, int* n_layers, evr_stream_t stream);
