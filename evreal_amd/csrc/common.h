@@ -33,6 +33,11 @@ inline int upload(const std::vector<float>& h, float** d) {
     EVR_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     return EVR_OK;
 }
+inline int upload(const std::vector<unsigned>& h, unsigned** d) {
+    EVR_HIP(hipMalloc((void**)d, h.size() * sizeof(unsigned) + 64));
+    EVR_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+    return EVR_OK;
+}
 }  // namespace evr
 
 // wave64 helpers

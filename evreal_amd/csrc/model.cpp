@@ -38,9 +38,20 @@ struct HostTensor {
 struct DevTensor {   // NHWC activation / state
     float* p = nullptr;
     int n = 0, h = 0, w = 0, c = 0;
-    bool packed = false;   // PACKED activation format (conv.h): f16 hi | fp8 lo8 | fp8 x8 per 16 channels
+    int fmt = 0;           // activation format as the kernels get it: 0 plain fp32, else conv.h packed_fmt (1 PACKED, 2 H2, 3 P6)
     int c_valid = 0;       // channels evr_model_read_tensor returns (0: all; FireNet's tensors are padded 16 -> 32)
-    int64_t numel() const { return (int64_t)n * h * w * c; }
+    int64_t pixels() const { return (int64_t)n * h * w; }
+    int64_t numel() const { return pixels() * c; }
+};
+
+struct Pair {   // an operand per frame parity: t[p] is what a frame of parity p reads or writes
+    DevTensor t[2];
+    Pair() {}
+    Pair(const DevTensor& both) : t{both, both} {}
+    Pair(const DevTensor& t0, const DevTensor& t1) : t{t0, t1} {}
+    const DevTensor& operator[](int p) const { return t[p]; }
+    Pair swapped() const { return Pair(t[1], t[0]); }      // ping-pong state: hb in, hb.swapped() out
+    explicit operator bool() const { return t[0].p != nullptr; }
 };
 
 struct Conv {   // one prepared implicit-GEMM convolution
@@ -309,18 +320,23 @@ int prep_tconv(Conv& c, const HostTensor* w, const Affine& af, int cin, int cout
 // conv(k5, stride 2, pad 2) in space-to-depth form (conv.hip, conv_band_prog_kernel): a 3x3 stride-1 convolution
 // over 2x2 pixel blocks with 4*cin phase-major channels.  in(2y + ky - 2, .) = block row y + dy, phase py with
 // 2*dy + py = ky - 2; the (dy = +1, py = 1) and (dx = +1, px = 1) combinations do not exist and get no step.
-void prep_s2d(Conv& c) {
-    const int cin = c.cin0, nch = cin / 32, nch2 = 4 * nch, k2 = 9 * 4 * cin;
-    c.w2.assign((size_t)c.n_gemm * k2, 0.f);
-    for (int row = 0; row < c.n_gemm; ++row)
+// the weights: [n_gemm][25][cin] -> [n_gemm][9][4 * cin], zeros where a (block tap, phase) pair has no k5 tap
+std::vector<float> s2d_weights(const std::vector<float>& w, int n_gemm, int cin) {
+    std::vector<float> w2((size_t)n_gemm * 9 * 4 * cin, 0.f);
+    for (int row = 0; row < n_gemm; ++row)
         for (int dy = -1; dy <= 1; ++dy) for (int dx = -1; dx <= 1; ++dx)
             for (int py = 0; py < 2; ++py) for (int px = 0; px < 2; ++px) {
                 const int ky = 2 * dy + py + 2, kx = 2 * dx + px + 2;
                 if (ky < 0 || ky > 4 || kx < 0 || kx > 4) continue;
-                const float* src = &c.w[((size_t)row * 25 + ky * 5 + kx) * cin];
-                float* dst = &c.w2[((size_t)row * 9 + (dy + 1) * 3 + dx + 1) * 4 * cin + (py * 2 + px) * cin];
-                memcpy(dst, src, (size_t)cin * sizeof(float));
+                memcpy(&w2[((size_t)row * 9 + (dy + 1) * 3 + dx + 1) * 4 * cin + (py * 2 + px) * cin], &w[((size_t)row * 25 + ky * 5 + kx) * cin],
+                       (size_t)cin * sizeof(float));
             }
+    return w2;
+}
+
+void prep_s2d(Conv& c) {
+    const int cin = c.cin0, nch = cin / 32, nch2 = 4 * nch;
+    c.w2 = s2d_weights(c.w, c.n_gemm, cin);
     // the program: bands = (phase, channel chunk, dy) in K order, steps = their dx taps
     struct Band { int src, dy; std::vector<int> taps; };
     std::vector<Band> bands;
@@ -373,8 +389,7 @@ int finish_conv(evr_model* m, Conv& c) {
         std::vector<float> probe(c.w);
         EVR_REQUIRE(pack_weights_for(c.x3, probe) == e2, "conv %s: the two weight layouts disagree on the packing exponent", c.name.c_str());
         if ((rc = upload(c.w2, &c.d_w2))) return rc;
-        EVR_HIP(hipMalloc((void**)&c.d_prog, c.prog.size() * sizeof(unsigned)));
-        EVR_HIP(hipMemcpy(c.d_prog, c.prog.data(), c.prog.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        if ((rc = upload(c.prog, &c.d_prog))) return rc;
     }
     // exact-fp32 mode: the 3x3 stride-1 layers whose shape wino.hip covers (ConvLSTM gates, residual convolutions) get their
     // Winograd-domain weights too -- G g G^T in fp64 -- and run F(2x2, 3x3): 2.25x fewer fp32 MFMAs (EVR_WINO=0: direct form only)
@@ -392,16 +407,8 @@ int finish_conv(evr_model* m, Conv& c) {
         c.cin1 == 0 && c.cin0 % 8 == 0 && ((c.cin0 / 8) & (c.cin0 / 8 - 1)) == 0 && c.n_gemm % 64 == 0 && c.n_valid == c.n_gemm &&
         (c.epi == EPI_BIAS || c.epi == EPI_BIAS_RELU)) {
         const int cin = c.cin0;
-        std::vector<float> w2((size_t)c.n_gemm * 9 * 4 * cin, 0.f), u;
-        for (int row = 0; row < c.n_gemm; ++row)
-            for (int dy = -1; dy <= 1; ++dy) for (int dx = -1; dx <= 1; ++dx)
-                for (int py = 0; py < 2; ++py) for (int px = 0; px < 2; ++px) {
-                    const int ky = 2 * dy + py + 2, kx = 2 * dx + px + 2;
-                    if (ky < 0 || ky > 4 || kx < 0 || kx > 4) continue;
-                    memcpy(&w2[((size_t)row * 9 + (dy + 1) * 3 + dx + 1) * 4 * cin + (py * 2 + px) * cin], &c.w[((size_t)row * 25 + ky * 5 + kx) * cin],
-                           (size_t)cin * sizeof(float));
-                }
-        wino_pack_weights(w2, c.n_gemm, 4 * cin, 0, u);
+        std::vector<float> u;
+        wino_pack_weights(s2d_weights(c.w, c.n_gemm, cin), c.n_gemm, 4 * cin, 0, u);
         if ((rc = upload(u, &c.d_wino))) return rc;
         c.wino_s2d = 1 + __builtin_ctz((unsigned)(cin / 8));
     }
@@ -462,6 +469,17 @@ int add_lstm(evr_model* m, const std::string& name, const std::string& prefix, i
     return finish_conv(m, c);
 }
 
+// two Conv2d(cin -> C, k3) stacked into one GEMM: rows [0, C) = the first, [C, 2C) = the second
+int prep_stacked(Conv& c, const HostTensor* w0, const Affine& a0, const HostTensor* w1, const Affine& a1, int C, int cin, int n_gemm) {
+    int rc;
+    Conv tmp; tmp.name = c.name;
+    if ((rc = prep_conv2d(c, w0, a0, C, cin, 3, 1, [](int co) { return co; }, n_gemm))) return rc;
+    if ((rc = prep_conv2d(tmp, w1, a1, C, cin, 3, 1, [C](int co) { return C + co; }, n_gemm))) return rc;
+    std::copy(tmp.w.begin() + (size_t)C * 9 * cin, tmp.w.begin() + (size_t)2 * C * 9 * cin, c.w.begin() + (size_t)C * 9 * cin);
+    std::copy(tmp.b.begin() + C, tmp.b.begin() + 2 * C, c.b.begin() + C);
+    return EVR_OK;
+}
+
 // ConvGRU (submodules.py:255-285): GEMM 1 = [update | reset] over (x|h); GEMM 2 = candidate over (x|h*r)
 int add_gru(evr_model* m, const std::string& name, const std::string& prefix, int C) {
     EVR_REQUIRE(C % 16 == 0, "ConvGRU with %d hidden channels (need a multiple of 16)", C);
@@ -477,12 +495,7 @@ int add_gru(evr_model* m, const std::string& name, const std::string& prefix, in
     {
         Conv c; c.name = name + ".zr";
         c.kc = pick_kc(C, C); c.cin0 = C; c.cin1 = C; c.stride = 1; c.epi = EPI_GRU_ZR; c.hidden = C; c.n_valid = 2 * C;
-        const int ng = round_up(2 * C, 32);
-        Conv tmp; tmp.name = c.name;
-        if ((rc = prep_conv2d(c, wz, az, C, 2 * C, 3, 1, [](int co) { return co; }, ng))) return rc;
-        if ((rc = prep_conv2d(tmp, wr, ar, C, 2 * C, 3, 1, [C](int co) { return C + co; }, ng))) return rc;
-        for (size_t i = (size_t)C * 9 * 2 * C; i < (size_t)2 * C * 9 * 2 * C; ++i) c.w[i] = tmp.w[i];
-        for (int i = C; i < 2 * C; ++i) c.b[i] = tmp.b[i];
+        if ((rc = prep_stacked(c, wz, az, wr, ar, C, 2 * C, round_up(2 * C, 32)))) return rc;
         if ((rc = finish_conv(m, c))) return rc;
     }
     {
@@ -499,6 +512,26 @@ int conv_index(const evr_model* m, const std::string& name) {
     return -1;
 }
 
+// head weights [co][b][t] -> [b][t][co] with `af` folded, uploaded; in the split modes the 5-bin k5 32-channel head also gets its
+// MFMA-fragment order for the matrix-core head kernel
+int upload_head(evr_model* m, const HostTensor* w, const Affine& af, int B, int k, int C) {
+    int rc;
+    m->head_w.assign((size_t)B * k * k * C, 0.f); m->head_b.assign(C, 0.f);
+    for (int co = 0; co < C; ++co) {
+        m->head_b[co] = (float)af.shift[co];
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < k * k; ++t) m->head_w[((size_t)b * k * k + t) * C + co] = (float)((double)w->data[((size_t)co * B + b) * k * k + t] * af.scale[co]);
+    }
+    if ((rc = upload(m->head_w, &m->d_head_w))) return rc;
+    if ((rc = upload(m->head_b, &m->d_head_b))) return rc;
+    if (m->arith != 0 && B == 5 && k == 5 && C == 32) {
+        std::vector<unsigned> wf;
+        m->head_wfrag_e = head_pack_wfrag(m->head_w.data(), B, wf);
+        if ((rc = upload(wf, &m->d_head_wfrag))) return rc;
+    }
+    return EVR_OK;
+}
+
 // head: Conv2d(num_bins -> C, k) [B*k*k][C]; pred: 1x1 C -> 1 (+BN)
 // (head_norm: prefix of a norm layer behind the head convolution -- ET-Net's ConvLayer head takes `norm`, u_trans.py:19; empty: none)
 int prep_head_pred(evr_model* m, const std::string& head_prefix, const std::string& pred_prefix, bool pred_bn, int C, bool pred_in = false,
@@ -512,12 +545,7 @@ int prep_head_pred(evr_model* m, const std::string& head_prefix, const std::stri
     if (head_norm.empty()) rc = make_affine(m, head_prefix + ".bias", "", false, C, &af);
     else rc = make_affine(m, pred_bn ? std::string() : head_prefix + ".bias", head_norm, true, C, &af, !pred_in);    // ConvLayer: no conv bias with BN (submodules.py:13)
     if (rc) return rc;
-    m->head_w.assign((size_t)B * k * k * C, 0.f); m->head_b.assign(C, 0.f);
-    for (int co = 0; co < C; ++co) {
-        m->head_b[co] = (float)af.shift[co];
-        for (int b = 0; b < B; ++b)
-            for (int t = 0; t < k * k; ++t) m->head_w[((size_t)b * k * k + t) * C + co] = (float)((double)w->data[((size_t)co * B + b) * k * k + t] * af.scale[co]);
-    }
+    if ((rc = upload_head(m, w, af, B, k, C))) return rc;
     if ((rc = find(m, pred_prefix + ".conv2d.weight", &w))) return rc;
     EVR_REQUIRE(w->numel() == C, "pred weight has %lld elements, expected %d", (long long)w->numel(), C);
     Affine ap;
@@ -525,16 +553,7 @@ int prep_head_pred(evr_model* m, const std::string& head_prefix, const std::stri
     m->pred_w.assign(C, 0.f);
     for (int c = 0; c < C; ++c) m->pred_w[c] = (float)((double)w->data[c] * ap.scale[0]);
     m->pred_b = (float)ap.shift[0];
-    if ((rc = upload(m->head_w, &m->d_head_w))) return rc;
-    if (m->arith != 0 && B == 5 && k == 5 && C == 32) {
-        std::vector<unsigned> wf;
-        m->head_wfrag_e = head_pack_wfrag(m->head_w.data(), B, wf);
-        EVR_HIP(hipMalloc((void**)&m->d_head_wfrag, wf.size() * sizeof(unsigned)));
-        EVR_HIP(hipMemcpy(m->d_head_wfrag, wf.data(), wf.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-    }
-    if ((rc = upload(m->head_b, &m->d_head_b))) return rc;
-    if ((rc = upload(m->pred_w, &m->d_pred_w))) return rc;
-    return EVR_OK;
+    return upload(m->pred_w, &m->d_pred_w);
 }
 
 int build_unet(evr_model* m) {
@@ -608,7 +627,7 @@ int build_unet(evr_model* m) {
 // kernels.  Measured at 240x180, 64 sequences: 12.0k frames/s against 14.2k on the fp32 path (4x the multiply-adds on tiles
 // sized for wider layers), so it is NOT the default; it exists because the shipped FireNet checkpoints are the only TRAINED
 // weights available offline, and this is how the split arithmetic is exercised on them (tests/test_gpu_modes.py).
-static void firenet_pad_state_dict(evr_model* m, const std::string& head, const std::string& pred) {
+static void firenet_pad_state_dict(evr_model* m, const std::string& head) {
     for (auto& kv : m->sd) {
         HostTensor& t = kv.second;
         const std::string& name = kv.first;
@@ -618,11 +637,10 @@ static void firenet_pad_state_dict(evr_model* m, const std::string& head, const 
             t.data = m->pad_store.back().data(); t.shape[0] = 32;
         } else if (t.ndim == 4) {
             const int co = (int)t.shape[0], ci = (int)t.shape[1], kk = (int)(t.shape[2] * t.shape[3]);
-            const bool is_head = name == head + ".weight", is_pred = name.compare(0, pred.size(), pred) == 0;
+            const bool is_head = name == head + ".weight";
             const int co2 = (co == 16) ? 32 : co;
             const int ci2 = is_head ? ci : (ci == 16 ? 32 : (ci == 32 ? 64 : ci));
             if (co2 == co && ci2 == ci) continue;
-            (void)is_pred;
             m->pad_store.emplace_back((size_t)co2 * ci2 * kk, 0.f);
             float* dst = m->pad_store.back().data();
             for (int o = 0; o < co; ++o)
@@ -649,7 +667,7 @@ int build_firenet(evr_model* m) {
     static const bool pad32 = getenv("EVR_FIRENET_PAD32") ? atoi(getenv("EVR_FIRENET_PAD32")) != 0 : false;
     m->fire_C = C;
     if (C == 16 && m->arith != 0 && pad32) {
-        firenet_pad_state_dict(m, head, pred);
+        firenet_pad_state_dict(m, head);
         C = m->fire_C = 32;
     }
     int rc;
@@ -696,12 +714,9 @@ int add_pair_conv(evr_model* m, const std::string& name, const std::string& p0, 
     Affine a0, a1;
     if ((rc = make_affine(m, p0 + ".bias", "", false, C, &a0))) return rc;
     if ((rc = make_affine(m, p1 + ".bias", "", false, C, &a1))) return rc;
-    Conv c; c.name = name; Conv tmp; tmp.name = name;
+    Conv c; c.name = name;
     c.kc = pick_kc(cin, 0); c.cin0 = cin; c.stride = 1; c.epi = EPI_BIAS; c.n_valid = 2 * C;
-    if ((rc = prep_conv2d(c, w0, a0, C, cin, 3, 1, [](int co) { return co; }, 2 * C))) return rc;
-    if ((rc = prep_conv2d(tmp, w1, a1, C, cin, 3, 1, [C](int co) { return C + co; }, 2 * C))) return rc;
-    for (size_t i = (size_t)C * 9 * cin; i < (size_t)2 * C * 9 * cin; ++i) c.w[i] = tmp.w[i];
-    for (int i = C; i < 2 * C; ++i) c.b[i] = tmp.b[i];
+    if ((rc = prep_stacked(c, w0, a0, w1, a1, C, cin, 2 * C))) return rc;
     return finish_conv(m, c);
 }
 
@@ -716,19 +731,7 @@ int build_spade(evr_model* m) {
         EVR_REQUIRE(w->ndim == 4 && w->shape[0] == 32 && w->shape[1] == 5 && w->shape[2] == 5 && w->shape[3] == 5, "fc weight shape mismatch");
         Affine af;
         if ((rc = make_affine(m, "fc.bias", "", false, 32, &af))) return rc;
-        m->head_w.assign((size_t)5 * 25 * 32, 0.f); m->head_b.assign(32, 0.f);
-        for (int co = 0; co < 32; ++co) {
-            m->head_b[co] = (float)af.shift[co];
-            for (int b = 0; b < 5; ++b) for (int t = 0; t < 25; ++t) m->head_w[((size_t)b * 25 + t) * 32 + co] = w->data[((size_t)co * 5 + b) * 25 + t];
-        }
-        if ((rc = upload(m->head_w, &m->d_head_w))) return rc;
-        if ((rc = upload(m->head_b, &m->d_head_b))) return rc;
-        if (m->arith != 0) {
-            std::vector<unsigned> wf;
-            m->head_wfrag_e = head_pack_wfrag(m->head_w.data(), 5, wf);
-            EVR_HIP(hipMalloc((void**)&m->d_head_wfrag, wf.size() * sizeof(unsigned)));
-            EVR_HIP(hipMemcpy(m->d_head_wfrag, wf.data(), wf.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-        }
+        if ((rc = upload_head(m, w, af, 5, 5, 32))) return rc;
     }
     const int cin[3] = {32, 64, 128}, cout[3] = {64, 128, 256}, stride[3] = {1, 2, 2};
     for (int i = 0; i < 3; ++i) {
@@ -803,7 +806,7 @@ int add_patch_conv(evr_model* m, const std::string& name, const std::string& pre
     return finish_conv(m, c);
 }
 
-int add_layernorm(evr_model* m, const std::string& prefix, int* index) {
+int add_layernorm(evr_model* m, const std::string& prefix) {
     const HostTensor *w, *b; int rc;
     if ((rc = find(m, prefix + ".weight", &w))) return rc;
     if ((rc = find(m, prefix + ".bias", &b))) return rc;
@@ -812,12 +815,9 @@ int add_layernorm(evr_model* m, const std::string& prefix, int* index) {
     float *dw, *db;
     if ((rc = upload(hw, &dw))) return rc;
     if ((rc = upload(hb, &db))) return rc;
-    *index = (int)m->et_ln.size();
     m->et_ln.push_back({dw, db});
     return EVR_OK;
 }
-
-struct EtLayer { int ln1, ln2, ln21, ln22, ln3; };       // LayerNorm indices (encoder: ln1, ln2; decoder: ln1, ln21, ln22, ln3)
 
 int build_etnet(evr_model* m) {
     const evr_model_desc& d = m->desc;
@@ -835,12 +835,11 @@ int build_etnet(evr_model* m) {
     }
     if ((rc = add_patch_conv(m, "split1", "split1", 128, 256, 2))) return rc;
     if ((rc = add_patch_conv(m, "split2", "split2", 64, 256, 4))) return rc;
-    int dummy;
     for (int s = 0; s < 3; ++s) {
         for (int l = 0; l < 3; ++l) {
             const std::string p = "trans_encoder" + std::to_string(s) + ".encoder.layers." + std::to_string(l), n = "te" + std::to_string(s) + "." + std::to_string(l);
-            if ((rc = add_layernorm(m, p + ".norm1", &dummy))) return rc;
-            if ((rc = add_layernorm(m, p + ".norm2", &dummy))) return rc;
+            if ((rc = add_layernorm(m, p + ".norm1"))) return rc;
+            if ((rc = add_layernorm(m, p + ".norm2"))) return rc;
             if ((rc = add_linear(m, n + ".qkv", p + ".self_attn.in_proj_weight", p + ".self_attn.in_proj_bias", 0, 768, 256, EPI_BIAS))) return rc;
             if ((rc = add_linear(m, n + ".out", p + ".self_attn.out_proj.weight", p + ".self_attn.out_proj.bias", 0, 256, 256, EPI_BIAS))) return rc;
             if ((rc = add_linear(m, n + ".ff1", p + ".linear1.weight", p + ".linear1.bias", 0, 1024, 256, EPI_BIAS_RELU))) return rc;
@@ -848,10 +847,10 @@ int build_etnet(evr_model* m) {
         }
         for (int l = 0; l < 2; ++l) {
             const std::string p = "trans_decoder" + std::to_string(s) + ".decoder.layers." + std::to_string(l), n = "td" + std::to_string(s) + "." + std::to_string(l);
-            if ((rc = add_layernorm(m, p + ".norm1", &dummy))) return rc;
-            if ((rc = add_layernorm(m, p + ".norm21", &dummy))) return rc;
-            if ((rc = add_layernorm(m, p + ".norm22", &dummy))) return rc;
-            if ((rc = add_layernorm(m, p + ".norm3", &dummy))) return rc;
+            if ((rc = add_layernorm(m, p + ".norm1"))) return rc;
+            if ((rc = add_layernorm(m, p + ".norm21"))) return rc;
+            if ((rc = add_layernorm(m, p + ".norm22"))) return rc;
+            if ((rc = add_layernorm(m, p + ".norm3"))) return rc;
             if ((rc = add_linear(m, n + ".qkv", p + ".self_attn.in_proj_weight", p + ".self_attn.in_proj_bias", 0, 768, 256, EPI_BIAS))) return rc;
             if ((rc = add_linear(m, n + ".out", p + ".self_attn.out_proj.weight", p + ".self_attn.out_proj.bias", 0, 256, 256, EPI_BIAS))) return rc;
             if ((rc = add_linear(m, n + ".cq", p + ".cross_attn.in_proj_weight", p + ".cross_attn.in_proj_bias", 0, 256, 256, EPI_BIAS))) return rc;
@@ -871,9 +870,9 @@ int build_etnet(evr_model* m) {
 
 // ------------------------------------------------------------------------------------------------
 // shape-dependent planning
-int alloc(evr_model* m, DevTensor* t, int n, int h, int w, int c, hipStream_t stream, bool packed = false) {
-    t->n = n; t->h = h; t->w = w; t->c = c; t->packed = packed;
-    EVR_REQUIRE(!packed || c % 16 == 0, "PACKED activation tensor with %d channels", c);
+int alloc(evr_model* m, DevTensor* t, int n, int h, int w, int c, hipStream_t stream, int fmt) {
+    t->n = n; t->h = h; t->w = w; t->c = c; t->fmt = fmt;
+    EVR_REQUIRE(!fmt || c % 16 == 0, "PACKED activation tensor with %d channels", c);
     EVR_HIP(hipMalloc((void**)&t->p, (size_t)t->numel() * sizeof(float) + 256));
     m->allocs.push_back({t->p, (size_t)t->numel() * sizeof(float)});
     EVR_HIP(hipMemsetAsync(t->p, 0, (size_t)t->numel() * sizeof(float), stream));
@@ -881,507 +880,416 @@ int alloc(evr_model* m, DevTensor* t, int n, int h, int w, int c, hipStream_t st
     return EVR_OK;
 }
 
-// fills both parities of a conv's launch plan; in0/in1/out/... given per parity
-struct ConvIO {
-    const float* in0[2]; const float* in1[2]; float* out[2];
-    const float* residual[2] = {nullptr, nullptr}; const float* post_add[2] = {nullptr, nullptr};
-    float* state[2] = {nullptr, nullptr}; float* aux0[2] = {nullptr, nullptr};
-    bool in_packed = false, out_packed = false, res_packed = false, padd_packed = false, state_packed = false;
-};
+// optional operands of a conv, per parity
+struct ConvOpts { Pair in1, residual, post_add, state, aux0; };
 
-void plan_conv(evr_model* m, int ci, int n, int hin, int win, const ConvIO& io, int cout_total) {
-    Conv& c = m->convs[ci];
+// post_add operand of a planned conv: as much data as the conv writes (the ConvArgs flag is 0/1: the epilogues read nothing else from it)
+int set_post_add(Conv& c, const Pair& t) {
     for (int p = 0; p < 2; ++p) {
         ConvArgs& a = c.args[p];
+        EVR_REQUIRE(t[p].numel() == (int64_t)a.n * a.hout * a.wout * a.cout_total, "conv %s: post_add tensor [%d,%d,%d,%d], the output has %d x %d x %d x %d elements",
+                    c.name.c_str(), t[p].n, t[p].h, t[p].w, t[p].c, a.n, a.hout, a.wout, a.cout_total);
+        a.post_add = t[p].p; a.padd_packed = t[p].fmt != 0;
+    }
+    return EVR_OK;
+}
+
+// fills both parities of a conv's launch plan.  Shapes and formats come from the tensors: n, hin, win from in0, cout_total from out, every
+// *_packed flag from the operand's own format -- and the tensors are checked against what the conv was prepared for
+int plan_conv(evr_model* m, int ci, const Pair& in0, const Pair& out, const ConvOpts& o) {
+    Conv& c = m->convs[ci];
+    const char* nm = c.name.c_str();
+    EVR_REQUIRE((bool)o.in1 == (c.cin1 != 0), "conv %s: %s", nm, c.cin1 ? "concatenating conv without in1" : "single-input conv with in1");
+    for (int p = 0; p < 2; ++p) {
+        const DevTensor& x = in0[p];
+        const DevTensor& y = out[p];
+        EVR_REQUIRE(x.p && x.c == c.cin0, "conv %s: in0 has %d channels, the conv takes %d", nm, x.c, c.cin0);
+        EVR_REQUIRE(!c.cin1 || (o.in1[p].c == c.cin1 && o.in1[p].pixels() == x.pixels() && o.in1[p].fmt == x.fmt),
+                    "conv %s: in1 [%d,%d,%d,%d] format %d beside in0 [%d,%d,%d,%d] format %d, the conv concatenates %d + %d channels", nm,
+                    o.in1[p].n, o.in1[p].h, o.in1[p].w, o.in1[p].c, o.in1[p].fmt, x.n, x.h, x.w, x.c, x.fmt, c.cin0, c.cin1);
+        ConvArgs& a = c.args[p];
         memset(&a, 0, sizeof(a));
-        a.in0 = io.in0[p]; a.in1 = io.in1[p];
+        a.in0 = x.p; a.in1 = o.in1[p].p;
         a.c0 = c.cin0; a.c1 = c.cin1; a.in_mode = c.cin1 ? IN_CAT : IN_SINGLE;
-        a.n = n; a.hin = hin; a.win = win;
-        if (c.transposed) { a.hm = hin; a.wm = win; a.stride = 1; a.os = 2; a.hout = 2 * hin; a.wout = 2 * win; }
-        else { a.hm = hin / c.stride; a.wm = win / c.stride; a.stride = c.stride; a.os = 1; a.hout = a.hm; a.wout = a.wm; }
+        a.n = x.n; a.hin = x.h; a.win = x.w;
+        if (c.transposed) { a.hm = x.h; a.wm = x.w; a.stride = 1; a.os = 2; a.hout = 2 * x.h; a.wout = 2 * x.w; }
+        else { a.hm = x.h / c.stride; a.wm = x.w / c.stride; a.stride = c.stride; a.os = 1; a.hout = a.hm; a.wout = a.wm; }
+        EVR_REQUIRE(y.p && y.pixels() == (int64_t)a.n * a.hout * a.wout, "conv %s: out tensor [%d,%d,%d,%d] for %d x %d x %d pixels", nm, y.n, y.h, y.w, y.c, a.n, a.hout, a.wout);
         a.tp = c.tp;
         a.wgt = c.d_w; a.bias = c.d_b; a.cout = c.n_gemm; a.n_valid = c.n_valid;
-        a.out = io.out[p]; a.cout_total = cout_total;
-        a.epi = c.epi; a.residual = io.residual[p]; a.post_add = io.post_add[p];
-        a.state = io.state[p]; a.aux0 = io.aux0[p]; a.hidden = c.hidden;
+        a.out = y.p; a.cout_total = y.c;
+        a.epi = c.epi; a.hidden = c.hidden;
+        if (const DevTensor& r = o.residual[p]; r.p) {
+            EVR_REQUIRE(r.numel() == y.numel(), "conv %s: residual tensor [%d,%d,%d,%d], out [%d,%d,%d,%d]", nm, r.n, r.h, r.w, r.c, y.n, y.h, y.w, y.c);
+            a.residual = r.p; a.res_packed = r.fmt != 0;
+        }
+        if (const DevTensor& s = o.state[p]; s.p) {
+            EVR_REQUIRE(s.pixels() == y.pixels(), "conv %s: state tensor [%d,%d,%d,%d], out [%d,%d,%d,%d]", nm, s.n, s.h, s.w, s.c, y.n, y.h, y.w, y.c);
+            a.state = s.p; a.state_packed = s.fmt != 0;
+        }
+        a.aux0 = o.aux0[p].p;
         set_mode_fields(a, c.x3, c.mx_e);
         a.wgt2 = c.d_w2; a.prog = c.d_prog; a.prog_steps = c.prog_steps;
         a.wgt_wino = c.d_wino; a.wino_s2d = c.wino_s2d; set_wino_grid(a);
         a.sat = m->d_sat ? m->d_sat + ci : nullptr;
-        a.in_packed = io.in_packed; a.out_packed = io.out_packed; a.res_packed = io.res_packed;
-        a.padd_packed = io.padd_packed; a.state_packed = io.state_packed;
+        a.in_packed = x.fmt != 0; a.out_packed = y.fmt != 0;
         if (const char* e = getenv("EVR_ABLATE")) a.debug_ablate = (c.epi == EPI_LSTM || getenv("EVR_ABLATE_ALL")) ? atoi(e) : 0;
     }
+    if (o.post_add) { if (int rc = set_post_add(c, o.post_add)) return rc; }
     pick_conv_tile(c.args[0], c.kc, &c.wm, &c.nb);
     // direct-conv FLOPs: a transposed conv counts its k*k taps once per INPUT pixel (= k*k/4 per output pixel x 4 phases)
     const double taps = c.transposed ? c.useful_taps * 4.0 : c.useful_taps;
-    c.flops = 2.0 * (double)n * c.args[0].hm * c.args[0].wm * taps * (c.cin0 + c.cin1) * c.n_valid;
+    c.flops = 2.0 * (double)c.args[0].n * c.args[0].hm * c.args[0].wm * taps * (c.cin0 + c.cin1) * c.n_valid;
     m->flops += c.flops;
+    return EVR_OK;
 }
 
-void push_conv(evr_model* m, int ci) { Step s; s.kind = ST_CONV; s.conv = ci; m->steps.push_back(s); }
+// What the four plan_* functions are written against: tensors, steps and debug names of the model being planned, the sub-graphs that
+// more than one family has.  Sticky on error: the first failure is kept in `rc`, every later call does nothing, and a plan_* function
+// ends with `return pl.rc;` (evr_model_reset_states releases the half-built shape).
+struct Planner {
+    evr_model* m; hipStream_t stream;
+    int n;              // sequences
+    int P;              // format of every tensor that feeds a matrix-core convolution: PACKED (1) / H2 (2) / P6 (3) in the split modes, else 0
+    int c_valid = 0;    // DevTensor::c_valid of the tensors made from here on (FireNet)
+    int rc = EVR_OK;
+    int last_conv = -1; // index of the conv planned last
+    Step none{};        // what step() hands back after a failure
 
-void name2(evr_model* m, const std::string& name, const DevTensor& t0, const DevTensor& t1) { m->named[0][name] = t0; m->named[1][name] = t1; }
+    Planner(evr_model* m_, hipStream_t s) : m(m_), stream(s), n(m_->n_seq), P(m_->packed ? m_->fmt : 0) {}
 
-// Fold the 1x1 prediction conv (+ skip-sum with `skip`, final activation, centre crop) into conv `ci`'s epilogue
-// when its GEMM has a single N tile; otherwise the standalone pred kernel runs.  reserved[0] bit 0 (debug) keeps
-// the conv's own NHWC output for evr_model_read_tensor.
-void try_fuse_pred(evr_model* m, int ci, const float* skip, bool skip_packed, float* skip_dot = nullptr) {
-    Conv& c = m->convs[ci];
-    m->pred_fused_conv = -1;
-    m->head.pred_w = nullptr; m->head.pred_dot = nullptr;
-    if (c.n_gemm != 32 * c.nb || c.n_gemm > 128) return;
-    if (c.epi != EPI_BIAS_RELU && c.epi != EPI_RESIDUAL_RELU && c.epi != EPI_BIAS) return;
-    // the skip is the head tensor and the matrix-core head kernel runs: it also writes sum_c pred_w[c] * head[c] per pixel,
-    // and the decoder's epilogue adds that one float instead of loading and unpacking the 32 skip channels
-    const bool by_dot = skip_dot && m->head.wfrag && m->head.cout == 32 && getenv("EVR_NO_PRED_DOT") == nullptr;
-    if (by_dot) { m->head.pred_w = m->d_pred_w; m->head.pred_dot = skip_dot; }
-    for (int p = 0; p < 2; ++p) {
-        ConvArgs& a = c.args[p];
-        a.post_add = by_dot ? nullptr : skip; a.padd_packed = skip_packed ? 1 : 0;
-        a.pred_skip_dot = by_dot ? skip_dot : nullptr;
-        a.pred_w = m->d_pred_w; a.pred_b = m->pred_b; a.pred_sigmoid = m->desc.final_activation == EVR_ACT_SIGMOID;
-        a.crop_h = m->H; a.crop_w = m->W; a.crop_y0 = m->iy0; a.crop_x0 = m->ix0;
-        a.prev_rec = m->prev_rec;
-        if (!(m->desc.reserved[0] & 1)) a.out = nullptr;
+    // allocated, registered in m->allocs (zeroed by every reset), zeroed
+    DevTensor tensor(int h, int w, int c, int fmt = 0) {
+        DevTensor t;
+        if (rc || (rc = alloc(m, &t, n, h, w, c, stream, fmt))) return DevTensor();
+        t.c_valid = c_valid;
+        return t;
     }
-    m->pred_fused_conv = ci;
+    void name(const std::string& nm, const Pair& t) { if (!rc) { m->named[0][nm] = t[0]; m->named[1][nm] = t[1]; } }
+    void require(bool ok, const char* what) { if (!rc && !ok) { set_error("%s", what); rc = EVR_ERR_INVALID; } }
+
+    // the head convolution's output: [n, hp, wp, c], named "head"
+    DevTensor head(int c, bool matrix_core = true) {
+        const DevTensor t = tensor(m->hp, m->wp, c, P);
+        name("head", t);
+        m->head.out = t.p; m->head.out_packed = P; m->head.cout = c;
+        m->head.wfrag = (P && matrix_core) ? m->d_head_wfrag : nullptr;      // matrix-core head conv in the split modes
+        return t;
+    }
+    void conv(const std::string& nm, const Pair& in0, const Pair& out, const ConvOpts& o = ConvOpts()) {
+        if (rc) return;
+        const int ci = conv_index(m, nm);
+        if (ci < 0) { set_error("the model has no conv '%s'", nm.c_str()); rc = EVR_ERR_INVALID; return; }
+        if ((rc = plan_conv(m, ci, in0, out, o))) return;
+        Step s; s.kind = ST_CONV; s.conv = ci; m->steps.push_back(s);
+        last_conv = ci;
+    }
+    // a non-conv launch: operands, formats and h, w, c (of `a`, else of `out`) from the tensors; `index` is the kind's own (Step::conv)
+    Step& step(StepKind kind, const Pair& a = Pair(), const Pair& b = Pair(), const DevTensor& out = DevTensor(), int index = -1) {
+        if (rc) return none;
+        Step s; s.kind = kind; s.conv = index;
+        for (int p = 0; p < 2; ++p) { s.a[p] = a[p].p; s.b[p] = b[p].p; }
+        s.out = out.p;
+        const DevTensor& dims = a ? a[0] : out;
+        s.h = dims.h; s.w = dims.w; s.c = dims.c;
+        s.a_packed = a[0].fmt; s.b_packed = b[0].fmt; s.out_packed = out.fmt;
+        m->steps.push_back(s);
+        return m->steps.back();
+    }
+    // skip_sum (model_util.py:4-5) folded after the fact into the epilogue of the conv planned last
+    void fold_skip(const Pair& skip) { if (!rc) rc = set_post_add(m->convs[last_conv], skip); }
+
+    // strided conv -> ConvLSTM (RecurrentConvLayer): convs prefix.conv / prefix.rec, ping-pong hidden buffers named h{idx}, an fp32 cell
+    // buffer (never a GEMM operand) named c{idx}.  Returns the new hidden state.
+    Pair conv_lstm(const std::string& prefix, int idx, const Pair& x, int cout, int stride, bool name_conv = false) {
+        const int h = x[0].h / stride, w = x[0].w / stride;
+        const DevTensor cv = tensor(h, w, cout, P);
+        conv(prefix + ".conv", x, cv);
+        if (name_conv) name(prefix + ".conv", cv);
+        const Pair hb(tensor(h, w, cout, P), tensor(h, w, cout, P));
+        const DevTensor cb = tensor(h, w, cout);
+        ConvOpts o; o.in1 = hb; o.state = cb;
+        conv(prefix + ".rec", cv, hb.swapped(), o);
+        name("h" + std::to_string(idx), hb.swapped());
+        name("c" + std::to_string(idx), cb);
+        return hb.swapped();
+    }
+    // ConvGRU: prefix.zr writes z (fp32, never a GEMM operand) and hr = h * r; prefix.out writes the new h in place.  Returns hs.
+    DevTensor conv_gru(const std::string& prefix, const Pair& x, const DevTensor& hs, const DevTensor& z, const DevTensor& hr) {
+        ConvOpts a, b;
+        a.in1 = hs; a.state = hs; a.aux0 = z;
+        b.in1 = hr; b.state = hs; b.aux0 = z;
+        conv(prefix + ".zr", x, hr, a);
+        conv(prefix + ".out", x, hs, b);
+        return hs;
+    }
+    // two-conv residual block: prefix.conv1 -> t, prefix.conv2 (+ x, relu) -> the block's output, named `nm`
+    DevTensor res_block(const std::string& prefix, const std::string& nm, const Pair& x, DevTensor t = DevTensor()) {
+        if (!t.p) t = tensor(x[0].h, x[0].w, x[0].c, P);
+        const DevTensor o = tensor(x[0].h, x[0].w, x[0].c, P);
+        ConvOpts r; r.residual = x;
+        conv(prefix + ".conv1", x, t);
+        conv(prefix + ".conv2", t, o, r);
+        name(nm, o);
+        return o;
+    }
+    // bilinear x2 of x + skip (one kernel, written in the conv's operand format), then conv `nm`, whose output takes that name
+    DevTensor upsample_conv(const std::string& nm, const Pair& x, const Pair& skip, int cout, bool name_up = false) {
+        const DevTensor up = tensor(2 * x[0].h, 2 * x[0].w, x[0].c, P);
+        step(ST_UPSAMPLE, x, skip, up);
+        if (name_up) name(nm + ".up", up);
+        const DevTensor o = tensor(up.h, up.w, cout, P);
+        conv(nm, up, o);
+        name(nm, o);
+        return o;
+    }
+    // input of the prediction layer (and its skip): the standalone kernel's operands
+    void pred(const Pair& x, const DevTensor& skip) {
+        for (int p = 0; p < 2; ++p) { m->pred_x[p] = x[p].p; m->pred_skip[p] = skip.p; }
+        m->pred_c = x[0].c; m->pred_x_packed = x[0].fmt; m->pred_skip_packed = skip.fmt;
+    }
+    // Fold the 1x1 prediction conv (+ skip-sum with `skip`, final activation, centre crop) into conv `nm`'s epilogue
+    // when its GEMM has a single N tile; otherwise the standalone pred kernel runs.  reserved[0] bit 0 (debug) keeps
+    // the conv's own NHWC output for evr_model_read_tensor.
+    void fuse_pred(const std::string& nm, const DevTensor& skip, bool by_head_dot = false) {
+        m->pred_fused_conv = -1;
+        m->head.pred_w = nullptr; m->head.pred_dot = nullptr;
+        const DevTensor hdot = by_head_dot ? tensor(m->hp, m->wp, 1) : DevTensor();
+        if (rc) return;
+        const int ci = conv_index(m, nm);
+        Conv& c = m->convs[ci];
+        if (c.n_gemm != 32 * c.nb || c.n_gemm > 128) return;
+        if (c.epi != EPI_BIAS_RELU && c.epi != EPI_RESIDUAL_RELU && c.epi != EPI_BIAS) return;
+        // the skip is the head tensor and the matrix-core head kernel runs: it also writes sum_c pred_w[c] * head[c] per pixel (hdot),
+        // and the decoder's epilogue adds that one float instead of loading and unpacking the 32 skip channels
+        const bool by_dot = hdot.p && m->head.wfrag && m->head.cout == 32 && getenv("EVR_NO_PRED_DOT") == nullptr;
+        if (by_dot) { m->head.pred_w = m->d_pred_w; m->head.pred_dot = hdot.p; }
+        if (skip.p && (rc = set_post_add(c, skip))) return;
+        for (int p = 0; p < 2; ++p) {
+            ConvArgs& a = c.args[p];
+            if (by_dot) a.post_add = nullptr;
+            a.pred_skip_dot = by_dot ? hdot.p : nullptr;
+            a.pred_w = m->d_pred_w; a.pred_b = m->pred_b; a.pred_sigmoid = m->desc.final_activation == EVR_ACT_SIGMOID;
+            a.crop_h = m->H; a.crop_w = m->W; a.crop_y0 = m->iy0; a.crop_x0 = m->ix0;
+            a.prev_rec = m->prev_rec;
+            if (!(m->desc.reserved[0] & 1)) a.out = nullptr;
+        }
+        m->pred_fused_conv = ci;
+    }
+};
+
+// HyperE2VID's first decoder (DynamicUpsampleLayer, submodules.py:100-127): upsample + skip, per-pixel filters from the context
+// (previous reconstruction | events at 1/4 resolution), the compositional 1x1 conv `dn`
+DevTensor plan_dynamic_decoder(Planner& pl, const std::string& dn, const Pair& x, const Pair& skip, int cout) {
+    evr_model* m = pl.m;
+    const evr_model_desc& d = m->desc;
+    const int n = pl.n, P = pl.P, cin = x[0].c, h = 2 * x[0].h, w = 2 * x[0].w;
+    const DevTensor up = pl.tensor(h, w, cin);
+    const DevTensor ctxp = pl.tensor(1, (d.num_bins + 1) * (m->hp / 4), m->wp / 4);   // planar [n,B+1,hp/4,wp/4]
+    const DevTensor ctxf = pl.tensor(m->hp / 4, m->wp / 4, 32, P);
+    const DevTensor t1 = pl.tensor(h, w, 64, P);
+    const DevTensor coef = pl.tensor(h, w, 72);             // stays PLAIN (VALU kernel)
+    const DevTensor inter = pl.tensor(h, w, cin * 6, P);    // the filtered tensor, in the 1x1 convolution's operand format
+    const DevTensor prev = pl.tensor(m->hp, m->wp, 1);
+    m->prev_rec = prev.p;
+    pl.step(ST_UPSAMPLE, x, skip, up);
+    pl.require(h == m->hp / 4 && w == m->wp / 4, "dynamic decoder: context resolution mismatch");
+    memset(&m->ctx, 0, sizeof(m->ctx));
+    m->ctx.prev_rec = prev.p; m->ctx.n = n; m->ctx.B = d.num_bins; m->ctx.H = m->H; m->ctx.W = m->W; m->ctx.hp = m->hp; m->ctx.wp = m->wp;
+    m->ctx.pad_top = m->pad_top; m->ctx.pad_left = m->pad_left; m->ctx.out = ctxp.p;
+    pl.step(ST_CTX);
+    memset(&m->ctxconv, 0, sizeof(m->ctxconv));
+    m->ctxconv.vox = ctxp.p; m->ctxconv.n = n; m->ctxconv.B = d.num_bins + 1; m->ctxconv.H = h; m->ctxconv.W = w; m->ctxconv.hp = h; m->ctxconv.wp = w;
+    m->ctxconv.k = 3; m->ctxconv.cout = 32; m->ctxconv.wgt = m->d_ctx_w; m->ctxconv.bias = m->d_ctx_b; m->ctxconv.out = ctxf.p; m->ctxconv.relu = 0; m->ctxconv.out_packed = ctxf.fmt;
+    pl.step(ST_CTXCONV);
+    pl.conv(dn + ".bn1", ctxf, t1);
+    pl.conv(dn + ".bn2", t1, coef);
+    // the filter kernel writes its output in the 1x1 convolution's operand format itself when it can (c <= 256); else PLAIN, converted in place
+    DevTensor filtered = inter;
+    if (cin > 256) filtered.fmt = 0;
+    pl.step(ST_DYN, up, coef, filtered);
+    if (P && cin > 256) pl.step(ST_TOPACKED, Pair(), Pair(), inter);
+    const DevTensor o = pl.tensor(h, w, cout, P);
+    pl.conv(dn, inter, o);
+    m->dyn_flops = 2.0 * n * h * w * (double)cin * 25 * 6;
+    m->flops += 2.0 * n * h * w * (double)cin * 25 * 6 + 2.0 * n * h * w * 72.0 * 25 + 2.0 * n * h * w * 9.0 * (d.num_bins + 1) * 32;
+    pl.name("ctx", ctxf); pl.name("coeff", coef);
+    return o;
 }
 
 int plan_unet(evr_model* m, hipStream_t stream) {
     const evr_model_desc& d = m->desc;
-    const int E = d.num_encoders, base = d.base_num_channels, n = m->n_seq;
-    const bool lstm = d.recurrent_block == EVR_REC_CONVLSTM;
-    int rc;
-    const int P = m->packed ? m->fmt : 0;   // every tensor that feeds a matrix-core convolution is PACKED (1) / H2 (2) / P6 (3) in the split modes
-    DevTensor head;
-    if ((rc = alloc(m, &head, n, m->hp, m->wp, base, stream, P))) return rc;
-    name2(m, "head", head, head);
-    m->head.out = head.p; m->head.out_packed = P;
-    m->head.wfrag = P ? m->d_head_wfrag : nullptr;      // matrix-core head conv in the split modes
-
-    // x[p]: current activation pointer per parity
-    const float* x[2] = {head.p, head.p};
-    int h = m->hp, w = m->wp;
-    std::vector<DevTensor> blk0(E), blk1(E);   // encoder outputs (skip connections) per parity
+    const int E = d.num_encoders, base = d.base_num_channels;
+    const bool lstm = d.recurrent_block == EVR_REC_CONVLSTM, inn = d.norm == EVR_NORM_IN;
+    Planner pl(m, stream);
+    const int P = pl.P;
+    const DevTensor head = pl.head(base);
+    Pair x = head;              // the current activation
+    std::vector<Pair> blk(E);   // encoder outputs (skip connections)
     for (int i = 0; i < E; ++i) {
         const int cout = base << (i + 1);
         const std::string en = "enc" + std::to_string(i);
-        DevTensor cv;
-        if ((rc = alloc(m, &cv, n, h / 2, w / 2, cout, stream, P))) return rc;
-        ConvIO io{};
-        io.in_packed = P; io.out_packed = P;
-        io.in0[0] = x[0]; io.in0[1] = x[1]; io.in1[0] = io.in1[1] = nullptr; io.out[0] = io.out[1] = cv.p;
-        const int ci = conv_index(m, en + ".conv");
-        plan_conv(m, ci, n, h, w, io, cout);
-        push_conv(m, ci);
-        name2(m, en + ".conv", cv, cv);
-        h /= 2; w /= 2;
         if (lstm) {
-            DevTensor hb[2], cb;
-            if ((rc = alloc(m, &hb[0], n, h, w, cout, stream, P))) return rc;
-            if ((rc = alloc(m, &hb[1], n, h, w, cout, stream, P))) return rc;
-            if ((rc = alloc(m, &cb, n, h, w, cout, stream))) return rc;      // cell state: fp32, never a GEMM operand
-            ConvIO r{};
-            r.in_packed = P; r.out_packed = P;
-            for (int p = 0; p < 2; ++p) { r.in0[p] = cv.p; r.in1[p] = hb[p].p; r.out[p] = hb[1 - p].p; r.state[p] = cb.p; }
-            const int ri = conv_index(m, en + ".rec");
-            plan_conv(m, ri, n, h, w, r, cout);
-            push_conv(m, ri);
-            x[0] = hb[1].p; x[1] = hb[0].p;
-            blk0[i] = hb[1]; blk1[i] = hb[0];
-            name2(m, "h" + std::to_string(i), hb[1], hb[0]);
-            name2(m, "c" + std::to_string(i), cb, cb);
+            x = pl.conv_lstm(en, i, x, cout, 2, true);
         } else {
-            DevTensor hs, z, hr;
-            if ((rc = alloc(m, &hs, n, h, w, cout, stream, P))) return rc;
-            if ((rc = alloc(m, &z, n, h, w, cout, stream))) return rc;
-            if ((rc = alloc(m, &hr, n, h, w, cout, stream, P))) return rc;
-            ConvIO a{}, b{};
-            a.in_packed = b.in_packed = P; a.out_packed = b.out_packed = P; a.state_packed = b.state_packed = P;
-            for (int p = 0; p < 2; ++p) {
-                a.in0[p] = cv.p; a.in1[p] = hs.p; a.out[p] = hr.p; a.state[p] = hs.p; a.aux0[p] = z.p;
-                b.in0[p] = cv.p; b.in1[p] = hr.p; b.out[p] = hs.p; b.state[p] = hs.p; b.aux0[p] = z.p;
-            }
-            const int zi = conv_index(m, en + ".rec.zr"), oi = conv_index(m, en + ".rec.out");
-            plan_conv(m, zi, n, h, w, a, cout); push_conv(m, zi);
-            plan_conv(m, oi, n, h, w, b, cout); push_conv(m, oi);
-            x[0] = x[1] = hs.p;
-            blk0[i] = blk1[i] = hs;
-            name2(m, "h" + std::to_string(i), hs, hs);
+            const int h = x[0].h / 2, w = x[0].w / 2;
+            const DevTensor cv = pl.tensor(h, w, cout, P), hs = pl.tensor(h, w, cout, P), z = pl.tensor(h, w, cout), hr = pl.tensor(h, w, cout, P);
+            pl.conv(en + ".conv", x, cv);
+            pl.name(en + ".conv", cv);
+            x = pl.conv_gru(en + ".rec", cv, hs, z, hr);
+            pl.name("h" + std::to_string(i), hs);
         }
+        blk[i] = x;
     }
-    const int cm = base << E;
-    // where the first decoder's skip-sum can be fused: into the last plain conv before it
-    const bool fuse = !d.use_upsample_conv;
-    int last_plain = -1;   // conv index whose epilogue may take post_add
-    const bool inn = d.norm == EVR_NORM_IN;
-    int last_inorm = -1;   // step index of the last ST_INORM (takes the first decoder's fused skip instead of a conv epilogue)
+    // the next decoder's skip-sum rides on the epilogue of the conv planned last where that is a plain conv (transposed decoders only:
+    // the upsample kernel adds the skip itself)
+    bool can_fold = false;
     for (int i = 0; i < d.num_residual_blocks; ++i) {
         const std::string rn = "res" + std::to_string(i);
-        DevTensor t, o;
-        if ((rc = alloc(m, &t, n, h, w, cm, stream, P))) return rc;
-        if ((rc = alloc(m, &o, n, h, w, cm, stream, P))) return rc;
-        const int c1 = conv_index(m, rn + ".conv1"), c2 = conv_index(m, rn + ".conv2");
-        if (inn) {
-            // conv (bias) -> InstanceNorm2d -> relu -> conv (bias) -> InstanceNorm2d -> + x -> relu  (submodules.py:169-184)
-            DevTensor raw;
-            if ((rc = alloc(m, &raw, n, h, w, cm, stream))) return rc;                 // PLAIN: the norm kernel's input
-            ConvIO a{}, b{};
-            a.in_packed = b.in_packed = P;
-            for (int p = 0; p < 2; ++p) { a.in0[p] = x[p]; a.out[p] = raw.p; b.in0[p] = t.p; b.out[p] = raw.p; }
-            plan_conv(m, c1, n, h, w, a, cm); push_conv(m, c1);
-            { Step s; s.kind = ST_INORM; s.a[0] = s.a[1] = raw.p; s.out = t.p; s.h = h; s.w = w; s.c = cm; s.out_packed = P; m->steps.push_back(s); }
-            plan_conv(m, c2, n, h, w, b, cm); push_conv(m, c2);
-            { Step s; s.kind = ST_INORM; s.a[0] = s.a[1] = raw.p; s.b[0] = x[0]; s.b[1] = x[1]; s.b_packed = P; s.out = o.p; s.h = h; s.w = w; s.c = cm;
-              s.out_packed = P; m->steps.push_back(s); last_inorm = (int)m->steps.size() - 1; }
-            x[0] = x[1] = o.p;
-            name2(m, rn, o, o);
-            last_plain = -1;
-            continue;
-        }
-        ConvIO a{}, b{};
-        a.in_packed = b.in_packed = P; a.out_packed = b.out_packed = P; b.res_packed = P;
-        for (int p = 0; p < 2; ++p) {
-            a.in0[p] = x[p]; a.out[p] = t.p;
-            b.in0[p] = t.p; b.out[p] = o.p; b.residual[p] = x[p];
-        }
-        plan_conv(m, c1, n, h, w, a, cm); push_conv(m, c1);
-        plan_conv(m, c2, n, h, w, b, cm); push_conv(m, c2);
-        x[0] = x[1] = o.p;
-        name2(m, rn, o, o);
-        last_plain = c2;
+        can_fold = !inn;
+        if (!inn) { x = pl.res_block(rn, rn, x); continue; }
+        // conv (bias) -> InstanceNorm2d -> relu -> conv (bias) -> InstanceNorm2d -> + x -> relu  (submodules.py:169-184)
+        const int h = x[0].h, w = x[0].w, cm = x[0].c;
+        const DevTensor t = pl.tensor(h, w, cm, P), o = pl.tensor(h, w, cm, P);
+        const DevTensor raw = pl.tensor(h, w, cm);                 // PLAIN: the norm kernel's input
+        pl.conv(rn + ".conv1", x, raw);
+        pl.step(ST_INORM, raw, Pair(), t);
+        pl.conv(rn + ".conv2", t, raw);
+        pl.step(ST_INORM, raw, x, o);
+        pl.name(rn, o);
+        x = o;
     }
-    (void)last_inorm;
     for (int i = 0; i < E; ++i) {
-        const int cin = base << (E - i), cout = base << (E - i - 1);
-        const DevTensor sk[2] = {blk0[E - 1 - i], blk1[E - 1 - i]};
+        const int cout = base << (E - i - 1);
+        const Pair& sk = blk[E - 1 - i];
         const std::string dn = "dec" + std::to_string(i);
-        const int di = conv_index(m, dn);
-        DevTensor o;
         if (i == 0 && m->dynamic) {
-            DevTensor up, ctxp, ctxf, t1, coef, inter, prev;
-            if ((rc = alloc(m, &up, n, 2 * h, 2 * w, cin, stream))) return rc;
-            if ((rc = alloc(m, &ctxp, n, 1, (d.num_bins + 1) * (m->hp / 4), m->wp / 4, stream))) return rc;   // planar [n,B+1,hp/4,wp/4]
-            if ((rc = alloc(m, &ctxf, n, m->hp / 4, m->wp / 4, 32, stream, P))) return rc;
-            if ((rc = alloc(m, &t1, n, 2 * h, 2 * w, 64, stream, P))) return rc;
-            if ((rc = alloc(m, &coef, n, 2 * h, 2 * w, 72, stream))) return rc;
-            if ((rc = alloc(m, &inter, n, 2 * h, 2 * w, cin * 6, stream))) return rc;
-            if ((rc = alloc(m, &prev, n, m->hp, m->wp, 1, stream))) return rc;
-            m->prev_rec = prev.p;
-            { Step s; s.kind = ST_UPSAMPLE; s.out = up.p; s.h = h; s.w = w; s.c = cin; s.a_packed = P; s.b_packed = P;
-              for (int p = 0; p < 2; ++p) { s.a[p] = x[p]; s.b[p] = sk[p].p; }
-              m->steps.push_back(s); }
-            h *= 2; w *= 2;
-            EVR_REQUIRE(h == m->hp / 4 && w == m->wp / 4, "dynamic decoder: context resolution mismatch");
-            memset(&m->ctx, 0, sizeof(m->ctx));
-            m->ctx.prev_rec = prev.p; m->ctx.n = n; m->ctx.B = d.num_bins; m->ctx.H = m->H; m->ctx.W = m->W; m->ctx.hp = m->hp; m->ctx.wp = m->wp;
-            m->ctx.pad_top = m->pad_top; m->ctx.pad_left = m->pad_left; m->ctx.out = ctxp.p;
-            { Step s; s.kind = ST_CTX; m->steps.push_back(s); }
-            memset(&m->ctxconv, 0, sizeof(m->ctxconv));
-            m->ctxconv.vox = ctxp.p; m->ctxconv.n = n; m->ctxconv.B = d.num_bins + 1; m->ctxconv.H = h; m->ctxconv.W = w; m->ctxconv.hp = h; m->ctxconv.wp = w;
-            m->ctxconv.k = 3; m->ctxconv.cout = 32; m->ctxconv.wgt = m->d_ctx_w; m->ctxconv.bias = m->d_ctx_b; m->ctxconv.out = ctxf.p; m->ctxconv.relu = 0; m->ctxconv.out_packed = P;
-            { Step s; s.kind = ST_CTXCONV; m->steps.push_back(s); }
-            const int b1 = conv_index(m, dn + ".bn1"), b2 = conv_index(m, dn + ".bn2");
-            ConvIO a1{}, a2{}, a3{};
-            a1.in_packed = P; a1.out_packed = P; a2.in_packed = P;     // coeff stays PLAIN (VALU kernel); the filtered tensor is
-            a3.in_packed = P; a3.out_packed = P;                       // converted in place for the matrix-core conv
-            for (int p = 0; p < 2; ++p) { a1.in0[p] = ctxf.p; a1.out[p] = t1.p; a2.in0[p] = t1.p; a2.out[p] = coef.p; a3.in0[p] = inter.p; }
-            plan_conv(m, b1, n, h, w, a1, 64); push_conv(m, b1);
-            plan_conv(m, b2, n, h, w, a2, 72); push_conv(m, b2);
-            { Step s; s.kind = ST_DYN; s.a[0] = s.a[1] = up.p; s.b[0] = s.b[1] = coef.p; s.out = inter.p; s.h = h; s.w = w; s.c = cin; s.out_packed = (cin <= 256) ? P : 0; m->steps.push_back(s); }
-            // (the filter kernel writes its output in the 1x1 convolution's operand format itself when it can: c <= 256)
-            if (P && cin > 256) { Step s; s.kind = ST_TOPACKED; s.out = inter.p; s.h = h; s.w = w; s.c = cin * 6; m->steps.push_back(s); }
-            if ((rc = alloc(m, &o, n, h, w, cout, stream, P))) return rc;
-            for (int p = 0; p < 2; ++p) a3.out[p] = o.p;
-            plan_conv(m, di, n, h, w, a3, cout); push_conv(m, di);
-            m->dyn_flops = 2.0 * n * h * w * (double)cin * 25 * 6;
-            m->flops += 2.0 * n * h * w * (double)cin * 25 * 6 + 2.0 * n * h * w * 72.0 * 25 + 2.0 * n * h * w * 9.0 * (d.num_bins + 1) * 32;
-            name2(m, "ctx", ctxf, ctxf); name2(m, "coeff", coef, coef);
-            last_plain = -1;   // the next decoder adds its skip itself
+            x = plan_dynamic_decoder(pl, dn, x, sk, cout);
+            pl.name(dn, x);
+            can_fold = false;   // the next decoder adds its skip itself
         } else if (d.use_upsample_conv) {
-            DevTensor up;
-            if ((rc = alloc(m, &up, n, 2 * h, 2 * w, cin, stream, P))) return rc;
-            Step s; s.kind = ST_UPSAMPLE; s.out = up.p; s.h = h; s.w = w; s.c = cin; s.a_packed = P; s.b_packed = P; s.out_packed = P;
-            for (int p = 0; p < 2; ++p) { s.a[p] = x[p]; s.b[p] = sk[p].p; }
-            m->steps.push_back(s);
-            name2(m, dn + ".up", up, up);
-            h *= 2; w *= 2;
-            if ((rc = alloc(m, &o, n, h, w, cout, stream, P))) return rc;
-            ConvIO a{};
-            a.in_packed = P; a.out_packed = P;      // the upsample kernel writes the conv's operand format
-            for (int p = 0; p < 2; ++p) { a.in0[p] = up.p; a.out[p] = o.p; }
-            plan_conv(m, di, n, h, w, a, cout); push_conv(m, di);
+            x = pl.upsample_conv(dn, x, sk, cout, true);
+            can_fold = false;
         } else {
-            const float* xin[2] = {x[0], x[1]};
-            if (fuse && last_plain >= 0) {
-                // skip_sum (model_util.py:4-5) folded into the producer's epilogue
-                for (int p = 0; p < 2; ++p) { m->convs[last_plain].args[p].post_add = sk[p].p; m->convs[last_plain].args[p].padd_packed = P; }
+            Pair xin = x;
+            if (can_fold) {
+                pl.fold_skip(sk);
             } else {
-                DevTensor sum;
-                if ((rc = alloc(m, &sum, n, h, w, cin, stream, P))) return rc;
-                Step s; s.kind = ST_ADD; s.out = sum.p; s.h = h; s.w = w; s.c = cin; s.a_packed = s.b_packed = s.out_packed = P;
-                for (int p = 0; p < 2; ++p) { s.a[p] = x[p]; s.b[p] = sk[p].p; }
-                m->steps.push_back(s);
-                xin[0] = xin[1] = sum.p;
+                const DevTensor sum = pl.tensor(x[0].h, x[0].w, x[0].c, P);
+                pl.step(ST_ADD, x, sk, sum);
+                xin = sum;
             }
-            if ((rc = alloc(m, &o, n, 2 * h, 2 * w, cout, stream, P))) return rc;
-            ConvIO a{};
-            a.in_packed = P; a.out_packed = P;
-            for (int p = 0; p < 2; ++p) { a.in0[p] = xin[p]; a.out[p] = o.p; }
-            plan_conv(m, di, n, h, w, a, cout); push_conv(m, di);
-            h *= 2; w *= 2;
-            last_plain = di;
+            const DevTensor o = pl.tensor(2 * x[0].h, 2 * x[0].w, cout, P);
+            pl.conv(dn, xin, o);
+            pl.name(dn, o);
+            x = o;
+            can_fold = true;
         }
-        x[0] = x[1] = o.p;
-        name2(m, dn, o, o);
     }
-    m->pred_x[0] = x[0]; m->pred_x[1] = x[1];
-    m->pred_skip[0] = m->pred_skip[1] = head.p;
-    m->pred_c = base; m->pred_x_packed = P; m->pred_skip_packed = P;
-    DevTensor hdot;      // sum_c pred_w[c] * head[c] per pixel, written by the matrix-core head kernel (try_fuse_pred)
-    if ((rc = alloc(m, &hdot, n, m->hp, m->wp, 1, stream))) return rc;
-    try_fuse_pred(m, conv_index(m, "dec" + std::to_string(E - 1)), head.p, P, hdot.p);
+    pl.pred(x, head);
+    const std::string last = "dec" + std::to_string(E - 1);
+    pl.fuse_pred(last, head, true);
     if (P == 3 && m->pred_fused_conv >= 0 && (d.reserved[0] & 1)) {
         // the debug copy of the last decoder's own output is written run by run (4 channels): PLAIN in the P6 mode
-        const std::string dn = "dec" + std::to_string(E - 1);
-        for (int p = 0; p < 2; ++p) { m->convs[m->pred_fused_conv].args[p].out_packed = 0; m->named[p][dn].packed = 0; }
+        for (int p = 0; p < 2; ++p) { m->convs[m->pred_fused_conv].args[p].out_packed = 0; m->named[p][last].fmt = 0; }
     }
-    EVR_REQUIRE(!m->dynamic || m->pred_fused_conv >= 0, "dynamic decoder: the prediction layer could not be fused (prev_recs needs it)");
-    return EVR_OK;
+    pl.require(!m->dynamic || m->pred_fused_conv >= 0, "dynamic decoder: the prediction layer could not be fused (prev_recs needs it)");
+    return pl.rc;
 }
 
 int plan_firenet(evr_model* m, hipStream_t stream) {
-    const int C = m->fire_C, Creal = m->desc.base_num_channels, n = m->n_seq, h = m->hp, w = m->wp;
-    const int P = m->packed ? m->fmt : 0;      // (padded to 32 channels: every tensor between the convolutions is PACKED / H2)
-    int rc;
-    DevTensor x0, hs[2], z, hr, t, r[2];
-    if ((rc = alloc(m, &x0, n, h, w, C, stream, P))) return rc;
-    if ((rc = alloc(m, &hs[0], n, h, w, C, stream, P))) return rc;
-    if ((rc = alloc(m, &hs[1], n, h, w, C, stream, P))) return rc;
-    if ((rc = alloc(m, &z, n, h, w, C, stream))) return rc;             // the update gate stays fp32 (never a GEMM operand)
-    if ((rc = alloc(m, &hr, n, h, w, C, stream, P))) return rc;
-    if ((rc = alloc(m, &t, n, h, w, C, stream, P))) return rc;
-    if ((rc = alloc(m, &r[0], n, h, w, C, stream, P))) return rc;
-    if ((rc = alloc(m, &r[1], n, h, w, C, stream, P))) return rc;
-    for (DevTensor* q : {&x0, &hs[0], &hs[1], &z, &hr, &t, &r[0], &r[1]}) q->c_valid = Creal;
-    m->head.out = x0.p; m->head.out_packed = P; m->head.cout = C;
-    name2(m, "head", x0, x0);
-    const float* x = x0.p;
+    const int C = m->fire_C, Creal = m->desc.base_num_channels, h = m->hp, w = m->wp;
+    Planner pl(m, stream);      // (padded to 32 channels: every tensor between the convolutions is PACKED / H2)
+    const int P = pl.P;
+    pl.c_valid = Creal;
+    Pair x = pl.head(C, /*matrix_core=*/false);
+    const DevTensor z = pl.tensor(h, w, C);             // the update gate stays fp32 (never a GEMM operand)
+    const DevTensor hr = pl.tensor(h, w, C, P), t = pl.tensor(h, w, C, P);
     const char* gn[2] = {"g1", "g2"};
     const char* rn[2] = {"r1", "r2"};
-    const double real = (double)Creal * Creal / ((double)C * C);       // direct-conv FLOPs of the REAL channels
-    auto plan = [&](int ci, const ConvIO& io) {
-        const double before = m->flops;
-        plan_conv(m, ci, n, h, w, io, C);
-        m->convs[ci].flops *= real;
-        m->flops = before + m->convs[ci].flops;
-        push_conv(m, ci);
-    };
     for (int s = 0; s < 2; ++s) {
-        ConvIO a{}, b{};
-        a.in_packed = b.in_packed = P; a.out_packed = b.out_packed = P; a.state_packed = b.state_packed = P;
-        for (int p = 0; p < 2; ++p) {
-            a.in0[p] = x; a.in1[p] = hs[s].p; a.out[p] = hr.p; a.state[p] = hs[s].p; a.aux0[p] = z.p;
-            b.in0[p] = x; b.in1[p] = hr.p; b.out[p] = hs[s].p; b.state[p] = hs[s].p; b.aux0[p] = z.p;
-        }
-        plan(conv_index(m, std::string(gn[s]) + ".zr"), a);
-        plan(conv_index(m, std::string(gn[s]) + ".out"), b);
-        name2(m, "h" + std::to_string(s), hs[s], hs[s]);
-        ConvIO c1{}, c2{};
-        c1.in_packed = c2.in_packed = P; c1.out_packed = c2.out_packed = P; c2.res_packed = P;
-        for (int p = 0; p < 2; ++p) {
-            c1.in0[p] = hs[s].p; c1.out[p] = t.p;
-            c2.in0[p] = t.p; c2.out[p] = r[s].p; c2.residual[p] = hs[s].p;
-        }
-        plan(conv_index(m, std::string(rn[s]) + ".conv1"), c1);
-        plan(conv_index(m, std::string(rn[s]) + ".conv2"), c2);
-        name2(m, "res" + std::to_string(s), r[s], r[s]);
-        x = r[s].p;
+        const DevTensor hs = pl.conv_gru(gn[s], x, pl.tensor(h, w, C, P), z, hr);
+        pl.name("h" + std::to_string(s), hs);
+        x = pl.res_block(rn[s], "res" + std::to_string(s), hs, t);
     }
-    m->pred_x[0] = m->pred_x[1] = x;
-    m->pred_skip[0] = m->pred_skip[1] = nullptr;
-    m->pred_c = C;
-    m->pred_x_packed = P; m->pred_skip_packed = 0;
-    try_fuse_pred(m, conv_index(m, "r2.conv2"), nullptr, false);
-    return EVR_OK;
+    // direct-conv FLOPs of the REAL channels
+    const double real = (double)Creal * Creal / ((double)C * C);
+    m->flops = 0.0;
+    for (Conv& c : m->convs) { c.flops *= real; m->flops += c.flops; }
+    pl.pred(x, DevTensor());
+    pl.fuse_pred("r2.conv2", DevTensor());
+    return pl.rc;
 }
 
 int plan_spade(evr_model* m, hipStream_t stream) {
-    const int n = m->n_seq, hp = m->hp, wp = m->wp;
-    const int P = m->packed ? m->fmt : 0;
-    int rc;
+    const int hp = m->hp, wp = m->wp;
     EVR_REQUIRE(hp % 4 == 0 && wp % 4 == 0, "SPADE-E2VID: padded size %dx%d not a multiple of 4", wp, hp);
-    DevTensor xpad, xorg, xorgh, head;
-    if ((rc = alloc(m, &xpad, n, m->desc.num_bins, hp, wp, stream))) return rc;          // planar [n,B,hp,wp]
-    if ((rc = alloc(m, &xorg, n, 3, hp, wp, stream))) return rc;                          // planar [n,3,hp,wp]
-    if ((rc = alloc(m, &xorgh, n, 3, hp / 2, wp / 2, stream))) return rc;
-    if ((rc = alloc(m, &head, n, hp, wp, 32, stream, P))) return rc;
-    m->sp_xpad = xpad.p; m->sp_xorg = xorg.p; m->sp_xorg_half = xorgh.p;
-    name2(m, "head", head, head);
-    m->head.out = head.p; m->head.out_packed = P;
-    m->head.wfrag = P ? m->d_head_wfrag : nullptr;
-
-    const float* x[2] = {head.p, head.p};
-    int h = hp, w = wp;
-    DevTensor hs[4][2];      // hidden states (new-after-parity-p at index [i][p])
-    auto add_rec = [&](const std::string& nm, int idx, int cin_unused, int cout, int stride) -> int {
-        (void)cin_unused;
-        DevTensor cv;
-        int r;
-        if ((r = alloc(m, &cv, n, h / stride, w / stride, cout, stream, P))) return r;
-        ConvIO io{};
-        io.in_packed = P; io.out_packed = P;
-        io.in0[0] = x[0]; io.in0[1] = x[1]; io.in1[0] = io.in1[1] = nullptr; io.out[0] = io.out[1] = cv.p;
-        const int ci = conv_index(m, nm + ".conv");
-        plan_conv(m, ci, n, h, w, io, cout); push_conv(m, ci);
-        h /= stride; w /= stride;
-        DevTensor hb[2], cb;
-        if ((r = alloc(m, &hb[0], n, h, w, cout, stream, P))) return r;
-        if ((r = alloc(m, &hb[1], n, h, w, cout, stream, P))) return r;
-        if ((r = alloc(m, &cb, n, h, w, cout, stream))) return r;
-        ConvIO q{};
-        q.in_packed = P; q.out_packed = P;
-        for (int p = 0; p < 2; ++p) { q.in0[p] = cv.p; q.in1[p] = hb[p].p; q.out[p] = hb[1 - p].p; q.state[p] = cb.p; }
-        const int ri = conv_index(m, nm + ".rec");
-        plan_conv(m, ri, n, h, w, q, cout); push_conv(m, ri);
-        x[0] = hb[1].p; x[1] = hb[0].p;
-        hs[idx][0] = hb[1]; hs[idx][1] = hb[0];
-        name2(m, "h" + std::to_string(idx), hb[1], hb[0]);
-        name2(m, "c" + std::to_string(idx), cb, cb);
-        return EVR_OK;
-    };
-    if ((rc = add_rec("rec0", 0, 32, 64, 1))) return rc;
-    if ((rc = add_rec("rec1", 1, 64, 128, 2))) return rc;
-    if ((rc = add_rec("rec2", 2, 128, 256, 2))) return rc;
-    int last = -1;
-    for (int i = 0; i < 2; ++i) {
-        const std::string rn = "res" + std::to_string(i);
-        DevTensor t, o;
-        if ((rc = alloc(m, &t, n, h, w, 256, stream, P))) return rc;
-        if ((rc = alloc(m, &o, n, h, w, 256, stream, P))) return rc;
-        ConvIO a{}, b{};
-        a.in_packed = b.in_packed = P; a.out_packed = b.out_packed = P; b.res_packed = P;
-        for (int p = 0; p < 2; ++p) { a.in0[p] = x[p]; a.out[p] = t.p; b.in0[p] = t.p; b.out[p] = o.p; b.residual[p] = x[p]; }
-        const int c1 = conv_index(m, rn + ".conv1"), c2 = conv_index(m, rn + ".conv2");
-        plan_conv(m, c1, n, h, w, a, 256); push_conv(m, c1);
-        plan_conv(m, c2, n, h, w, b, 256); push_conv(m, c2);
-        x[0] = x[1] = o.p;
-        name2(m, rn, o, o);
-        last = c2;
-    }
+    Planner pl(m, stream);
+    const int n = pl.n, P = pl.P;
+    m->sp_xpad = pl.tensor(m->desc.num_bins, hp, wp).p;          // planar [n,B,hp,wp]
+    m->sp_xorg = pl.tensor(3, hp, wp).p;                         // planar [n,3,hp,wp]
+    m->sp_xorg_half = pl.tensor(3, hp / 2, wp / 2).p;
+    const DevTensor head = pl.head(32);
+    Pair hs[3];      // hidden states of rec0..2: the decoders' skips
+    Pair x = head;
+    const int rec_out[3] = {64, 128, 256}, rec_stride[3] = {1, 2, 2};
+    for (int i = 0; i < 3; ++i) x = hs[i] = pl.conv_lstm("rec" + std::to_string(i), i, x, rec_out[i], rec_stride[i]);
+    for (int i = 0; i < 2; ++i) x = pl.res_block("res" + std::to_string(i), "res" + std::to_string(i), x);
     // up0(x + x2, x_org): the skip sum rides on res1.conv2's epilogue (model_util-style fusion)
-    for (int p = 0; p < 2; ++p) { m->convs[last].args[p].post_add = hs[2][p].p; m->convs[last].args[p].padd_packed = P; }
+    pl.fold_skip(hs[2]);
     m->sp_seg.clear();
     for (int i = 0; i < 2; ++i) {
         const std::string un = "up" + std::to_string(i);
-        const int C = (i == 0) ? 128 : 64;
-        DevTensor xn, actv, gb, u;
-        if ((rc = alloc(m, &xn, n, 2 * h, 2 * w, C, stream))) return rc;                   // PLAIN: read by spade_apply
-        ConvIO a{};
-        a.in_packed = P; a.out_packed = false;
-        for (int p = 0; p < 2; ++p) { a.in0[p] = x[p]; a.out[p] = xn.p; }
-        const int ci = conv_index(m, un + ".conv");
-        plan_conv(m, ci, n, h, w, a, C); push_conv(m, ci);
-        h *= 2; w *= 2;
+        const int C = (i == 0) ? 128 : 64, h = 2 * x[0].h, w = 2 * x[0].w;
+        const DevTensor xn = pl.tensor(h, w, C);                   // PLAIN: read by spade_apply
+        pl.conv(un + ".conv", x, xn);
         const float* seg = m->sp_xorg;
         if (h != hp) {
-            EVR_REQUIRE(2 * h == hp && 2 * w == wp, "SPADE-E2VID: unexpected decoder resolution");
-            Step s; s.kind = ST_SP_NEAREST; m->steps.push_back(s);
+            pl.require(2 * h == hp && 2 * w == wp, "SPADE-E2VID: unexpected decoder resolution");
+            pl.step(ST_SP_NEAREST);
             seg = m->sp_xorg_half;
         }
-        if ((rc = alloc(m, &actv, n, h, w, 64, stream, P))) return rc;
+        const DevTensor actv = pl.tensor(h, w, 64, P);
         HeadArgs ha; memset(&ha, 0, sizeof(ha));
         ha.vox = seg; ha.n = n; ha.B = 3; ha.H = h; ha.W = w; ha.hp = h; ha.wp = w; ha.k = 3; ha.cout = 64;
-        ha.wgt = m->sp_seg_dw[i]; ha.bias = m->sp_seg_db[i]; ha.out = actv.p; ha.relu = 1; ha.out_packed = P;
+        ha.wgt = m->sp_seg_dw[i]; ha.bias = m->sp_seg_db[i]; ha.out = actv.p; ha.relu = 1; ha.out_packed = actv.fmt;
         m->sp_seg.push_back(ha);
-        { Step s; s.kind = ST_SP_SEG; s.conv = i; m->steps.push_back(s); }
-        if ((rc = alloc(m, &gb, n, h, w, 2 * C, stream))) return rc;
-        ConvIO g{};
-        g.in_packed = P; g.out_packed = false;
-        for (int p = 0; p < 2; ++p) { g.in0[p] = actv.p; g.out[p] = gb.p; }
-        const int gi = conv_index(m, un + ".gb");
-        plan_conv(m, gi, n, h, w, g, 2 * C); push_conv(m, gi);
-        if ((rc = alloc(m, &u, n, h, w, C, stream, P))) return rc;
-        { Step s; s.kind = ST_SP_APPLY; s.a[0] = s.a[1] = xn.p; s.b[0] = s.b[1] = gb.p; s.out = u.p; s.h = h; s.w = w; s.c = C;
-          s.out_packed = P; s.a_packed = P;          // a_packed: format of the fused skip operand
-          s.conv = i;                                // skip = hidden state of rec(1 - i)
-          m->steps.push_back(s); }
+        pl.step(ST_SP_SEG, Pair(), Pair(), DevTensor(), i);
+        const DevTensor gb = pl.tensor(h, w, 2 * C);
+        pl.conv(un + ".gb", actv, gb);
+        const DevTensor u = pl.tensor(h, w, C, P);
+        // the skip fused into spade_apply is the hidden state of rec(1 - i) (up0 output + x1, up1 output + x0): parity-dependent, kept in
+        // the model and looked up by the step's index; the step's a_packed carries ITS format
+        const Pair& skip = hs[1 - i];
+        pl.step(ST_SP_APPLY, xn, gb, u, i).a_packed = skip[0].fmt;
+        m->sp_skip[i][0] = skip[0].p; m->sp_skip[i][1] = skip[1].p;
         m->flops += 2.0 * n * h * w * 9.0 * 3 * 64;
-        x[0] = x[1] = u.p;
-        name2(m, un, u, u);
+        pl.name(un, u);
+        x = u;
     }
-    // skip operands of the two spade_apply steps (parity-dependent hidden states): kept in the model, looked up by step
-    m->sp_skip[0][0] = hs[1][0].p; m->sp_skip[0][1] = hs[1][1].p;     // up0 output + x1
-    m->sp_skip[1][0] = hs[0][0].p; m->sp_skip[1][1] = hs[0][1].p;     // up1 output + x0
-    {   // up2: RecurrentConvLayer(64 -> 32, stride 1)
-        DevTensor cv;
-        if ((rc = alloc(m, &cv, n, h, w, 32, stream, P))) return rc;
-        ConvIO io{};
-        io.in_packed = P; io.out_packed = P;
-        io.in0[0] = x[0]; io.in0[1] = x[1]; io.in1[0] = io.in1[1] = nullptr; io.out[0] = io.out[1] = cv.p;
-        const int ci = conv_index(m, "up2.conv");
-        plan_conv(m, ci, n, h, w, io, 32); push_conv(m, ci);
-        DevTensor hb[2], cb;
-        if ((rc = alloc(m, &hb[0], n, h, w, 32, stream, P))) return rc;
-        if ((rc = alloc(m, &hb[1], n, h, w, 32, stream, P))) return rc;
-        if ((rc = alloc(m, &cb, n, h, w, 32, stream))) return rc;
-        ConvIO q{};
-        q.in_packed = P; q.out_packed = P;
-        for (int p = 0; p < 2; ++p) { q.in0[p] = cv.p; q.in1[p] = hb[p].p; q.out[p] = hb[1 - p].p; q.state[p] = cb.p; }
-        const int ri = conv_index(m, "up2.rec");
-        plan_conv(m, ri, n, h, w, q, 32); push_conv(m, ri);
-        name2(m, "h3", hb[1], hb[0]); name2(m, "c3", cb, cb);
-        m->pred_x[0] = hb[1].p; m->pred_x[1] = hb[0].p;
-    }
+    // up2: RecurrentConvLayer(64 -> 32, stride 1)
+    x = pl.conv_lstm("up2", 3, x, 32, 1);
+    pl.pred(x, DevTensor());
     memset(&m->sp_pred, 0, sizeof(m->sp_pred));
-    m->sp_pred.head = head.p; m->sp_pred.x_packed = P; m->sp_pred.head_packed = P;
+    m->sp_pred.head = head.p; m->sp_pred.x_packed = x[0].fmt; m->sp_pred.head_packed = head.fmt;
     m->sp_pred.n = n; m->sp_pred.hp = hp; m->sp_pred.wp = wp; m->sp_pred.wgt = m->d_sp_pred_w;
     for (int k = 0; k < 3; ++k) m->sp_pred.bias[k] = m->sp_pred_b[k];
     m->sp_pred.prev = m->sp_xorg; m->sp_pred.H = m->H; m->sp_pred.W = m->W; m->sp_pred.iy0 = m->iy0; m->sp_pred.ix0 = m->ix0;
-    m->pred_c = 32; m->pred_fused_conv = -1;
+    m->pred_fused_conv = -1;
     m->flops += 2.0 * n * hp * wp * 32.0 * 2;     // conv_img has 3 outputs (the generic account adds one)
-    return EVR_OK;
+    return pl.rc;
 }
 
 int plan_etnet(evr_model* m, hipStream_t stream) {
-    const int n = m->n_seq, hp = m->hp, wp = m->wp;
-    const int P = m->packed ? m->fmt : 0;
-    int rc;
+    const int hp = m->hp, wp = m->wp;
     EVR_REQUIRE(hp % 8 == 0 && wp % 8 == 0, "ET-Net: padded size %dx%d not a multiple of 8", wp, hp);
-    DevTensor head;
-    if ((rc = alloc(m, &head, n, hp, wp, 32, stream, P))) return rc;
-    name2(m, "head", head, head);
-    m->head.out = head.p; m->head.out_packed = P;
-    m->head.wfrag = P ? m->d_head_wfrag : nullptr;
-    const float* x[2] = {head.p, head.p};
-    int h = hp, w = wp;
-    DevTensor blk[3][2];
-    for (int i = 0; i < 3; ++i) {       // DownsampleConv: conv k5 s2 + ConvLSTM (as the UNet encoders)
-        const int cout = 64 << i;
-        const std::string en = "enc" + std::to_string(i);
-        DevTensor cv;
-        if ((rc = alloc(m, &cv, n, h / 2, w / 2, cout, stream, P))) return rc;
-        ConvIO io{};
-        io.in_packed = P; io.out_packed = P;
-        io.in0[0] = x[0]; io.in0[1] = x[1]; io.in1[0] = io.in1[1] = nullptr; io.out[0] = io.out[1] = cv.p;
-        const int ci = conv_index(m, en + ".conv");
-        plan_conv(m, ci, n, h, w, io, cout); push_conv(m, ci);
-        h /= 2; w /= 2;
-        DevTensor hb[2], cb;
-        if ((rc = alloc(m, &hb[0], n, h, w, cout, stream, P))) return rc;
-        if ((rc = alloc(m, &hb[1], n, h, w, cout, stream, P))) return rc;
-        if ((rc = alloc(m, &cb, n, h, w, cout, stream))) return rc;
-        ConvIO r{};
-        r.in_packed = P; r.out_packed = P;
-        for (int p = 0; p < 2; ++p) { r.in0[p] = cv.p; r.in1[p] = hb[p].p; r.out[p] = hb[1 - p].p; r.state[p] = cb.p; }
-        const int ri = conv_index(m, en + ".rec");
-        plan_conv(m, ri, n, h, w, r, cout); push_conv(m, ri);
-        x[0] = hb[1].p; x[1] = hb[0].p;
-        blk[i][0] = hb[1]; blk[i][1] = hb[0];
-        name2(m, "h" + std::to_string(i), hb[1], hb[0]);
-        name2(m, "c" + std::to_string(i), cb, cb);
-    }
+    Planner pl(m, stream);
+    const int n = pl.n, P = pl.P;
+    const DevTensor head = pl.head(32);
+    Pair x = head;
+    Pair blk[3];
+    for (int i = 0; i < 3; ++i)       // DownsampleConv: conv k5 s2 + ConvLSTM (as the UNet encoders)
+        x = blk[i] = pl.conv_lstm("enc" + std::to_string(i), i, x, 64 << i, 2);
     const int th = hp / 8, tw = wp / 8, L = th * tw;
 
     // sine position table (position_encoding.py:14-23: float64 numpy, cast to float32)
@@ -1392,7 +1300,7 @@ int plan_etnet(evr_model* m, hipStream_t stream) {
                 const double ang = (double)l / std::pow(10000.0, 2.0 * (j / 2) / 256.0);
                 pos[(size_t)l * 256 + j] = (float)((j & 1) ? std::cos(ang) : std::sin(ang));
             }
-        // (its own allocation, NOT alloc(): the same-shape path of evr_model_reset_states zeroes every entry of m->allocs,
+        // (its own allocation, NOT a planner tensor: the same-shape path of evr_model_reset_states zeroes every entry of m->allocs,
         // and a zeroed table would silently drop the position term from the second sequence of a dataset on)
         float* pt = nullptr;
         EVR_HIP(hipMalloc((void**)&pt, pos.size() * sizeof(float)));
@@ -1401,123 +1309,87 @@ int plan_etnet(evr_model* m, hipStream_t stream) {
         EVR_HIP(hipStreamSynchronize(stream));       // `pos` is a local
         m->et_pos = pt;
     }
-    auto tok = [&](DevTensor* t, int c, bool packed) { return alloc(m, t, n, L, 1, c, stream, packed); };
-    DevTensor Wd[3], HS[3], HC[3], Ta, Tb, Tm, Tm2, XA, MEMN, QKV, CQ, CKV, AO, FF, SP;
-    for (int s2 = 0; s2 < 3; ++s2) { if ((rc = tok(&Wd[s2], 256, false))) return rc; if ((rc = tok(&HS[s2], 256, false))) return rc; if ((rc = tok(&HC[s2], 256, false))) return rc; }
-    if ((rc = tok(&Ta, 256, false))) return rc; if ((rc = tok(&Tb, 256, false))) return rc;
-    if ((rc = tok(&Tm, 256, false))) return rc; if ((rc = tok(&Tm2, 256, false))) return rc;
-    if ((rc = tok(&XA, 256, P))) return rc; if ((rc = tok(&MEMN, 256, P))) return rc;
-    if ((rc = tok(&QKV, 768, false))) return rc; if ((rc = tok(&CQ, 256, false))) return rc; if ((rc = tok(&CKV, 512, false))) return rc;
-    if ((rc = tok(&AO, 256, P))) return rc; if ((rc = tok(&FF, 1024, P))) return rc; if ((rc = tok(&SP, 256, false))) return rc;
+    // token tensors [n, L, 1, c]: PLAIN where a VALU kernel reads them, the conv operand format where a linear layer does
+    auto tok = [&](int c, int fmt) { return pl.tensor(L, 1, c, fmt); };
+    DevTensor Wd[3], HS[3], HC[3];
+    for (int s = 0; s < 3; ++s) { Wd[s] = tok(256, 0); HS[s] = tok(256, 0); HC[s] = tok(256, 0); }
+    const DevTensor Ta = tok(256, 0), Tb = tok(256, 0), Tm = tok(256, 0), Tm2 = tok(256, 0), XA = tok(256, P), MEMN = tok(256, P);
+    const DevTensor QKV = tok(768, 0), CQ = tok(256, 0), CKV = tok(512, 0), AO = tok(256, P), FF = tok(1024, P), SP = tok(256, 0);
 
-    auto ln = [&](int idx, const float* in, float* out, int out_packed) {
-        Step s; s.kind = ST_LN; s.conv = idx; s.a[0] = s.a[1] = in; s.out = out; s.out_packed = out_packed; m->steps.push_back(s);
+    auto ln = [&](int idx, const DevTensor& in, const DevTensor& out) { pl.step(ST_LN, in, Pair(), out, idx); };
+    // linear layer = 1x1 conv over [n, L, 1, C]: in -> out [+ add]
+    auto lin = [&](const std::string& nm, const DevTensor& in, const DevTensor& out, const DevTensor& add = DevTensor()) {
+        ConvOpts o; o.post_add = add;
+        pl.conv(nm, in, out, o);
     };
-    // linear layer = 1x1 conv over [n, L, 1, C]: in (PACKED when P) -> out [+ post_add]
-    auto lin = [&](const std::string& nm, const float* in, float* out, int cout_total, bool out_packed, const float* add) {
-        const int ci = conv_index(m, nm);
-        ConvIO io{};
-        io.in_packed = P; io.out_packed = out_packed;
-        for (int p = 0; p < 2; ++p) { io.in0[p] = in; io.in1[p] = nullptr; io.out[p] = out; io.post_add[p] = add; }
-        io.padd_packed = false;
-        plan_conv(m, ci, n, L, 1, io, cout_total); push_conv(m, ci);
-    };
-    auto attn = [&](const float* q, int ldq, int qo, const float* k, int ldk, int ko, const float* v, int ldv, int vo, float* out) {
+    // 8-head attention; q / k / v are 256-channel slices of their tensors from channel qo / ko / vo on
+    auto attn = [&](const DevTensor& q, int qo, const DevTensor& k, int ko, const DevTensor& v, int vo, const DevTensor& out) {
         AttnArgs a; memset(&a, 0, sizeof(a));
-        a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.qo = qo; a.ko = ko; a.vo = vo;
-        a.n = n; a.Lq = L; a.Lk = L; a.heads = 8; a.out = out; a.out_packed = P;
-        Step s; s.kind = ST_ATTN; s.conv = (int)m->et_attn.size(); m->et_attn.push_back(a); m->steps.push_back(s);
+        a.q = q.p; a.k = k.p; a.v = v.p; a.ldq = q.c; a.ldk = k.c; a.ldv = v.c; a.qo = qo; a.ko = ko; a.vo = vo;
+        a.n = n; a.Lq = L; a.Lk = L; a.heads = 8; a.out = out.p; a.out_packed = out.fmt;
+        pl.step(ST_ATTN, Pair(), Pair(), DevTensor(), (int)m->et_attn.size());
+        m->et_attn.push_back(a);
         m->flops += 2.0 * 2.0 * n * (double)L * L * 256;
     };
     for (int sc = 0; sc < 3; ++sc) {
         // ---- words + position embedding (u_trans.py:93-104) ----
         if (sc == 0) {
-            Step s; s.kind = ST_ADDPOS; s.a[0] = blk[2][0].p; s.a[1] = blk[2][1].p; s.a_packed = P; s.out = Wd[0].p; m->steps.push_back(s);
+            pl.step(ST_ADDPOS, blk[2], Pair(), Wd[0]);
         } else {
-            const std::string nm = sc == 1 ? "split1" : "split2";
-            const int src = 2 - sc, ks = sc == 1 ? 2 : 4;
-            const int ci = conv_index(m, nm);
-            ConvIO io{};
-            io.in_packed = P; io.out_packed = false;
-            for (int p = 0; p < 2; ++p) { io.in0[p] = blk[src][p].p; io.in1[p] = nullptr; io.out[p] = SP.p; }
-            plan_conv(m, ci, n, th * ks, tw * ks, io, 256); push_conv(m, ci);
-            Step s; s.kind = ST_ADDPOS; s.a[0] = s.a[1] = SP.p; s.a_packed = 0; s.out = Wd[sc].p; m->steps.push_back(s);
+            pl.conv(sc == 1 ? "split1" : "split2", blk[2 - sc], SP);      // patch embedding: k x k stride-k conv, k = 2 / 4
+            pl.step(ST_ADDPOS, SP, Pair(), Wd[sc]);
         }
         // ---- encoder: 3 pre-norm layers (transformer_encoder.py:64-76) ----
-        const float* cur = Wd[sc].p;
+        DevTensor cur = Wd[sc];
         for (int l = 0; l < 3; ++l) {
             const std::string nm = "te" + std::to_string(sc) + "." + std::to_string(l);
             const int lb = sc * 14 + l * 2;
-            float* outp = (l == 2) ? HS[sc].p : ((l & 1) ? Tb.p : Ta.p);
-            ln(lb + 0, cur, XA.p, P);
-            lin(nm + ".qkv", XA.p, QKV.p, 768, false, nullptr);
-            attn(QKV.p, 768, 0, QKV.p, 768, 256, QKV.p, 768, 512, AO.p);
-            lin(nm + ".out", AO.p, Tm.p, 256, false, cur);
-            ln(lb + 1, Tm.p, XA.p, P);
-            lin(nm + ".ff1", XA.p, FF.p, 1024, P, nullptr);
-            lin(nm + ".ff2", FF.p, outp, 256, false, Tm.p);
+            const DevTensor& outp = (l == 2) ? HS[sc] : ((l & 1) ? Tb : Ta);
+            ln(lb + 0, cur, XA);
+            lin(nm + ".qkv", XA, QKV);
+            attn(QKV, 0, QKV, 256, QKV, 512, AO);
+            lin(nm + ".out", AO, Tm, cur);
+            ln(lb + 1, Tm, XA);
+            lin(nm + ".ff1", XA, FF);
+            lin(nm + ".ff2", FF, outp, Tm);
             cur = outp;
         }
     }
     for (int sc = 0; sc < 3; ++sc) {
         // ---- decoder: tgt = hs[sc], memory = hs[0], hs[0], hs[1] (u_trans.py:106-108; transformer_decoder.py:66-84) ----
-        const float* mem = HS[sc == 2 ? 1 : 0].p;
-        const float* cur = HS[sc].p;
+        const DevTensor& mem = HS[sc == 2 ? 1 : 0];
+        DevTensor cur = HS[sc];
         for (int l = 0; l < 2; ++l) {
             const std::string nm = "td" + std::to_string(sc) + "." + std::to_string(l);
             const int lb = sc * 14 + 6 + l * 4;
-            float* outp = (l == 1) ? HC[sc].p : Ta.p;
-            ln(lb + 0, cur, XA.p, P);
-            lin(nm + ".qkv", XA.p, QKV.p, 768, false, nullptr);
-            attn(QKV.p, 768, 0, QKV.p, 768, 256, QKV.p, 768, 512, AO.p);
-            lin(nm + ".out", AO.p, Tm.p, 256, false, cur);                 // tgt2
-            ln(lb + 1, Tm.p, XA.p, P);
-            ln(lb + 2, mem, MEMN.p, P);
-            lin(nm + ".cq", XA.p, CQ.p, 256, false, nullptr);
-            lin(nm + ".ckv", MEMN.p, CKV.p, 512, false, nullptr);
-            attn(CQ.p, 256, 0, CKV.p, 512, 0, CKV.p, 512, 256, AO.p);
-            lin(nm + ".cout", AO.p, Tm2.p, 256, false, Tm.p);              // tgt4
-            ln(lb + 3, Tm2.p, XA.p, P);
-            lin(nm + ".ff1", XA.p, FF.p, 1024, P, nullptr);
-            lin(nm + ".ff2", FF.p, outp, 256, false, Tm2.p);
+            const DevTensor& outp = (l == 1) ? HC[sc] : Ta;
+            ln(lb + 0, cur, XA);
+            lin(nm + ".qkv", XA, QKV);
+            attn(QKV, 0, QKV, 256, QKV, 512, AO);
+            lin(nm + ".out", AO, Tm, cur);                  // tgt2
+            ln(lb + 1, Tm, XA);
+            ln(lb + 2, mem, MEMN);
+            lin(nm + ".cq", XA, CQ);
+            lin(nm + ".ckv", MEMN, CKV);
+            attn(CQ, 0, CKV, 0, CKV, 256, AO);
+            lin(nm + ".cout", AO, Tm2, Tm);                 // tgt4
+            ln(lb + 3, Tm2, XA);
+            lin(nm + ".ff1", XA, FF);
+            lin(nm + ".ff2", FF, outp, Tm2);
             cur = outp;
         }
     }
     // ---- hs_trans = mean of the six token sets -> [n, h/8, w/8, 256] (u_trans.py:112-113) ----
-    DevTensor hm;
-    if ((rc = alloc(m, &hm, n, th, tw, 256, stream, P))) return rc;
-    m->et_mean_in[0] = HS[0].p; m->et_mean_in[1] = HS[1].p; m->et_mean_in[2] = HS[2].p;
-    m->et_mean_in[3] = HC[0].p; m->et_mean_in[4] = HC[1].p; m->et_mean_in[5] = HC[2].p;
-    { Step s; s.kind = ST_MEAN6; s.out = hm.p; s.out_packed = P; s.h = L; m->steps.push_back(s); }
-    name2(m, "hs_trans", hm, hm);
+    const DevTensor hm = pl.tensor(th, tw, 256, P);
+    for (int s = 0; s < 3; ++s) { m->et_mean_in[s] = HS[s].p; m->et_mean_in[3 + s] = HC[s].p; }
+    pl.step(ST_MEAN6, HS[0], Pair(), hm);      // (a: the shape of the six inputs; the kernel reads them from et_mean_in)
+    pl.name("hs_trans", hm);
     // ---- UpsampleConv decoders with skip sums (u_trans.py:116-117) ----
-    const float* y[2] = {hm.p, hm.p};
-    int ypk = P;
-    h = th; w = tw;
-    for (int i = 0; i < 3; ++i) {
-        const int cin = 256 >> i, cout = 128 >> i;
-        DevTensor up, o;
-        if ((rc = alloc(m, &up, n, 2 * h, 2 * w, cin, stream, P))) return rc;
-        Step s; s.kind = ST_UPSAMPLE; s.out = up.p; s.h = h; s.w = w; s.c = cin; s.a_packed = ypk; s.b_packed = P; s.out_packed = P;
-        for (int p = 0; p < 2; ++p) { s.a[p] = y[p]; s.b[p] = blk[2 - i][p].p; }
-        m->steps.push_back(s);
-        h *= 2; w *= 2;
-        if ((rc = alloc(m, &o, n, h, w, cout, stream, P))) return rc;
-        ConvIO a{};
-        a.in_packed = P; a.out_packed = P;
-        for (int p = 0; p < 2; ++p) { a.in0[p] = up.p; a.out[p] = o.p; }
-        const int di = conv_index(m, "dec" + std::to_string(i));
-        plan_conv(m, di, n, h, w, a, cout); push_conv(m, di);
-        y[0] = y[1] = o.p; ypk = P;
-        name2(m, "dec" + std::to_string(i), o, o);
-    }
-    m->pred_x[0] = y[0]; m->pred_x[1] = y[1];
-    m->pred_skip[0] = m->pred_skip[1] = head.p;
-    m->pred_c = 32; m->pred_x_packed = P; m->pred_skip_packed = P;
-    DevTensor hdot;
-    if ((rc = alloc(m, &hdot, n, m->hp, m->wp, 1, stream))) return rc;
-    try_fuse_pred(m, conv_index(m, "dec2"), head.p, P, hdot.p);
-    return EVR_OK;
+    x = hm;
+    for (int i = 0; i < 3; ++i) x = pl.upsample_conv("dec" + std::to_string(i), x, blk[2 - i], 128 >> i);
+    pl.pred(x, head);
+    pl.fuse_pred("dec2", head, true);
+    return pl.rc;
 }
 
 }  // namespace
@@ -1787,7 +1659,7 @@ extern "C" int evr_model_read_tensor(evr_model* m, const char* name, float* dst,
     if (n_out) *n_out = numel;
     if (!dst) return EVR_OK;
     EVR_REQUIRE(dst_elems >= numel, "evr_model_read_tensor: destination holds %lld elements, need %lld", (long long)dst_elems, (long long)numel);
-    return launch_nhwc_to_nchw(t.p, dst, t.n, t.h, t.w, cv, t.packed ? m->fmt : 0, (hipStream_t)stream, t.c);
+    return launch_nhwc_to_nchw(t.p, dst, t.n, t.h, t.w, cv, t.fmt, (hipStream_t)stream, t.c);
 }
 
 extern "C" int evr_model_set_gate(evr_model* m, const char* layer, evr_event_t ev) {
