@@ -8,10 +8,11 @@ Frames arrive in batches; gating (start/end time, |ref_ts-img_ts| <= ts_tol_ms, 
 Metric plug-ins keep the reference's contract (utils/eval_metrics.py:18-75): a `BaseMetric` subclass with `name`,
 `no_ref`, `calculate(img, ref) -> float | list`, `finish_queue()`, `reset()`.  Three kinds live side by side:
   * the GPU metrics of `_SCORERS` below run batched, one launch set per scorer: 'mse', 'ssim' and 'lpips' are booked frame by
-    frame; the others ('lpips-vgg', 'dists', 'psnr', 'ms_ssim', 'gmsd', 'niqe', 'brisque', 'piqe') through the four-frame queue of the
+    frame; the others ('lpips-vgg', 'dists', 'psnr', 'ms_ssim', 'gmsd', 'vifp', 'niqe', 'brisque', 'piqe') through the four-frame queue of the
     reference's pyiqa metrics, so their files hold the same lines.  'lpips', 'lpips-vgg', 'dists', 'niqe' and 'brisque' need a weights or
-    model file; 'psnr' / 'ms_ssim', 'piqe' and 'gmsd' need none and have a switch (EVREAL_GPU_FR_METRICS, EVREAL_GPU_PIQE,
-    EVREAL_GPU_GMSD: '0' sends the name to pyiqa instead);
+    model file; 'psnr' / 'ms_ssim', 'piqe', 'gmsd' and 'vifp' need none and have a switch (EVREAL_GPU_FR_METRICS,
+    EVREAL_GPU_PIQE, EVREAL_GPU_GMSD, EVREAL_GPU_VIFP: '0' sends the name to pyiqa instead -- which knows no 'vifp': its 'vif' is
+    the wavelet-domain form, another number, and stays pyiqa's);
   * anything registered with `register_metric(name, factory)` runs per frame on host arrays, exactly like the reference's
     MseMetric / SsimMetric (clipped float32 [H,W] images in, a float or a list of floats out);
   * any other name is looked up in pyiqa.list_models() when pyiqa is importable (queued in batches of 4 as
@@ -32,7 +33,7 @@ import numpy as np
 import torch
 
 from .lpips import DISTS, LPIPS, LPIPSVGG
-from .prepost import GMSD, FullRefMetrics, Metrics, histogram_equalization
+from .prepost import GMSD, VIFP, FullRefMetrics, Metrics, histogram_equalization
 
 DEFAULT_METRICS = ('mse', 'ssim', 'lpips')      # the reference's default (eval.py:413-445, utils/eval_metrics.py:171)
 GPU_METRICS = ('mse', 'ssim')
@@ -40,6 +41,7 @@ FR_METRICS = ('psnr', 'ms_ssim')                # full-reference, closed form, q
 FR_METRICS_ENV = 'EVREAL_GPU_FR_METRICS'        # '0': psnr / ms_ssim go to pyiqa (or are unknown without it)
 PIQE_ENV = 'EVREAL_GPU_PIQE'                    # '0': piqe goes to pyiqa (or is unknown without it)
 GMSD_ENV = 'EVREAL_GPU_GMSD'                    # '0': gmsd goes to pyiqa (or is unknown without it)
+VIFP_ENV = 'EVREAL_GPU_VIFP'                    # '0': vifp goes to pyiqa (or is unknown without it)
 LPIPS_WEIGHTS_ENV = 'EVREAL_LPIPS_WEIGHTS'      # path to a pyiqa/lpips AlexNet-v0.1 state_dict (torch.save'd)
 LPIPS_VGG_WEIGHTS_ENV = 'EVREAL_LPIPS_VGG_WEIGHTS'      # path to a pyiqa lpips-vgg (VGG-16, v0.1) state_dict (torch.save'd)
 DISTS_WEIGHTS_ENV = 'EVREAL_DISTS_WEIGHTS'      # path to a pyiqa dists state_dict (torch.save'd)
@@ -82,6 +84,10 @@ def gpu_piqe_enabled():
 
 def gpu_gmsd_enabled():
     return os.environ.get(GMSD_ENV, '1') != '0'
+
+
+def gpu_vifp_enabled():
+    return os.environ.get(VIFP_ENV, '1') != '0'
 
 
 def niqe_model_path():
@@ -349,6 +355,9 @@ _SCORERS = (
     _GpuScorer({'gmsd': 0}, 2, lambda t: t._gmsd, enabled=gpu_gmsd_enabled,           # (column 1: the mean GMS)
                too_small=lambda name, H, W: GMSD.too_small(H, W),
                run=lambda h, img, ref, names, out: h(img, ref, clip=True, out=out)),
+    _GpuScorer({'vifp': 0}, 9, lambda t: t._vifp, enabled=gpu_vifp_enabled,           # (columns 1..8: num and den of the four scales)
+               too_small=lambda name, H, W: VIFP.too_small(H, W),
+               run=lambda h, img, ref, names, out: h(img, ref, clip=True, out=out)),
     _GpuScorer({'lpips-vgg': 0}, 1, lambda t: t._cached('_lpips_vgg_cache'), before_registry=True,
                too_small=lambda name, H, W: LPIPSVGG.too_small(H, W),
                run=lambda h, img, ref, names, out: h(img, ref, clip=True, out=out[:, 0])),
@@ -395,6 +404,7 @@ class EvalMetricsTracker:
         self._gpu = Metrics()
         self._fr = FullRefMetrics()
         self._gmsd = GMSD()
+        self._vifp = VIFP()
         self.metrics = [m for m in map(self._resolve, quan_eval_metric_names) if m is not None]
         if not self.has_reference_frames:
             self.metrics = [m for m in self.metrics if m.no_ref]
@@ -497,7 +507,7 @@ class EvalMetricsTracker:
         return [m.name for m in self.metrics if getattr(m, 'on_gpu', False)]
 
     def _shape_refused(self, m, imgs):
-        """A GPU metric that is not defined on frames of this size (ms_ssim below 161 pixels a side, gmsd below 2, lpips-vgg and dists below 16) ends like a metric that
+        """A GPU metric that is not defined on frames of this size (ms_ssim below 161 pixels a side, gmsd below 2, vifp below 41, lpips-vgg and dists below 16) ends like a metric that
         raises on every frame in the reference (utils/eval_metrics.py:233-242: the exception is printed, the metric reset): its
         file stays empty and its mean is -1.  Decided from the shape, before any launch, and printed once per sequence."""
         if m.name in self._failed:

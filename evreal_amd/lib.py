@@ -78,6 +78,9 @@ SYMBOLS = {
                                c_void_p]),
     'evr_gmsd_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'evr_gmsd': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'evr_vifp_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'evr_vifp': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'evr_vifp_taps': (c_int, [c_int, c_void_p]),
     'evr_lpips_create': (c_int, [ctypes.POINTER(Tensor), c_int, ctypes.POINTER(c_void_p)]),
     'evr_lpips_destroy': (c_int, [c_void_p]),
     'evr_lpips_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

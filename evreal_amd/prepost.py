@@ -204,6 +204,55 @@ class GMSD:
         return self.stats(img, ref, clip=clip, out_map=q), q
 
 
+class VIFP:
+    """VIFp (Sheikh & Bovik 2006, pixel domain: vifp_mscale.m, sewar.vifp) for a batch of frame pairs, in fp64 (evr_vifp): four
+    scales of Gaussian-windowed second moments of 255 * frame over the valid region, sum of the information that survives the
+    channel g*x + noise over the reference's own.  `img` is the reconstruction, `ref` the reference: the score is not symmetric.
+    Constructing one touches neither the library nor the GPU; the workspace is owned and grows on demand."""
+    MIN_SIDE = 41           # 41 -> 17 -> 7 -> 3: one 3x3 window at the fourth scale
+
+    def __init__(self):
+        self.lib = None
+        self.ws = None
+
+    @classmethod
+    def too_small(cls, H, W):
+        """The message of the exception `vifp` raises on frames of this size, or None where it is defined."""
+        if min(H, W) >= cls.MIN_SIDE:
+            return None
+        return f"vifp needs frames of at least {cls.MIN_SIDE}x{cls.MIN_SIDE} pixels (four scales, the last one 3x3 window), got {H}x{W}"
+
+    def stats(self, img, ref, clip=True, out=None):
+        """img, ref: cuda float32 [n,H,W] (or [H,W]) -> float64 [n,9] = (score, num_1..4, den_1..4).
+        out: optional contiguous float64 [n,9] to write into."""
+        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dtype == ref.dtype == torch.float32
+        img = img.contiguous(); ref = ref.contiguous()
+        v = img if img.dim() == 3 else img.reshape(-1, img.shape[-2], img.shape[-1])
+        n, H, W = v.shape
+        if self.too_small(H, W):
+            raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
+        if self.lib is None:
+            self.lib = _lib.load()
+        need = self.lib.evr_vifp_workspace_bytes(n, H, W)
+        if self.ws is None or self.ws.numel() < need or self.ws.device != img.device:
+            self.ws = torch.empty(need, dtype=torch.uint8, device=img.device)
+        if out is None:
+            out = torch.empty((n, 9), dtype=torch.float64, device=img.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n, 9)
+        _lib.check(self.lib.evr_vifp(_lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0, _lib.ptr(out), _lib.ptr(self.ws),
+                                     self.ws.numel(), _lib.stream_ptr()), 'evr_vifp')
+        return out
+
+    def __call__(self, img, ref, clip=True, out=None):
+        """-> float64 [n] scores.  out: optional float64 [n,9] to write the whole rows into; its first column is returned."""
+        return self.stats(img, ref, clip=clip, out=out)[:, 0]
+
+    def scales(self, img, ref, clip=True):
+        """-> float64 [n,4,2]: (num_s, den_s) of each scale."""
+        rows = self.stats(img, ref, clip=clip)
+        return torch.stack([rows[:, 1:5], rows[:, 5:9]], dim=2)
+
+
 HISTEQ_MODES ={'none': 0, 'global': 1, 'local': 2, 'clahe': 3}
 _histeq_ws = {}
 

@@ -38,7 +38,7 @@ enum evr_status {
 
 /* Message for the last failure on this thread ("" if none). */
 const char* evr_last_error(void);
-/* ABI version (major*1000 + minor).  1005: evr_brisque_*; evr_fr_metrics*, evr_piqe_* and evr_gmsd* joined later without a bump (tests/test_brisque_cpu.py pins this number: look the symbol up instead).  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
+/* ABI version (major*1000 + minor).  1005: evr_brisque_*; evr_fr_metrics*, evr_piqe_*, evr_gmsd* and evr_vifp* joined later without a bump (tests/test_brisque_cpu.py pins this number: look the symbol up instead).  1004: evr_niqe_*.  1003 (round 6): evr_model_release_shape, evr_png_* (native PNG writer pool).  1002 (round 5): evr_model_desc.reserved[2] (per-model arithmetic), evr_model_saturation_async.
  * 1001 (round 4): evr_percentile_normalize rejects a NULL workspace (size it with
  * evr_percentile_normalize_workspace_bytes); evr_model_arith reports the mode the convolutions actually run (FireNet's 16-channel
  * layers: h3 whatever EVR_ARITH says). */
@@ -287,6 +287,25 @@ int evr_fr_metrics(const float* img, const float* ref, int n, int H, int W, unsi
 size_t evr_gmsd_workspace_bytes(int n, int H, int W);
 int evr_gmsd(const float* img, const float* ref, int n, int H, int W, int clip, double* out, double* out_map, void* workspace,
              size_t workspace_bytes, evr_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Full-reference VIFp per frame, in fp64: the pixel-domain Visual Information Fidelity of Sheikh & Bovik (IEEE TIP 2006) as
+ * vifp_mscale.m of the LIVE release and sewar.vifp compute it.  x = 255 * (double)ref, y = 255 * (double)img (after the [0,1]
+ * clamp in fp32 with clip; nothing is quantised).  Scale s = 1..4 uses a Gaussian window of N = 17, 9, 5, 3 taps (sigma N / 5)
+ * over the valid region only, two separable passes (axis 0, then axis 1), taps added in index order; below scale 1 both planes are
+ * filtered with the scale's own window and the even indices kept.  Per window: g = s12 / (s1 + 1e-10), sv = s2 - g * s12 with the
+ * threshold rules of the release; num_s = sum log10(1 + g^2 s1 / (sv + 2)), den_s = sum log10(1 + s1 / 2);
+ * vifp = sum_s num_s / sum_s den_s (NaN for a reference that is flat everywhere).  The full statement: csrc/vifp.hip,
+ * tests/vifp_ref.py.
+ * img, ref: [n, H, W]; out: double [n, 9] = {score, num_1..4, den_1..4}.  Needs H >= 41 and W >= 41; below that, for a null
+ * pointer and for a short workspace the call returns EVR_ERR_INVALID, evr_last_error names the reason (the size as "40 x 346")
+ * and nothing is launched.  A frame's numbers do not depend on n, on its place in the batch or on earlier calls.
+ * evr_vifp_taps (host only): the N_s taps the kernels use at scale 1..4, so that an oracle can be handed the same bits.
+ */
+size_t evr_vifp_workspace_bytes(int n, int H, int W);
+int evr_vifp(const float* img, const float* ref, int n, int H, int W, int clip, double* out, void* workspace,
+             size_t workspace_bytes, evr_stream_t stream);
+int evr_vifp_taps(int scale, double* taps);
 
 /* ----------------------------------------------------------------------------------------------
  * LPIPS (AlexNet, v0.1).  Replaces PyIqaMetricFactory.get_metric('lpips') (utils/eval_metrics.py:110-156):
