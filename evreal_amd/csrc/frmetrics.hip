@@ -18,30 +18,29 @@
 // separable passes run on chip, the tile writes fp64 partial sums of its cs and s maps (and of the squared error at scale 1)
 // and -- from the same staged tile -- the pooled pixels of the next level whose lower-right source pixel it owns.  Each level
 // is read once and the next one written once.  A finishing launch adds a frame's partials in a fixed order and applies the
-// clamp, the powers and the PSNR formula, so a frame's numbers do not depend on n or on its place in the batch.
+// clamp, the powers and the PSNR formula, so a frame's numbers do not depend on n or on its place in the batch.  The moment
+// passes, the tile and frame sums, the workspace plan and the frame chunks are the family's scaffold (metric_tiles.h).
 // Algorithmic bytes per frame: 2*4*H*W read at scale 1, 2*8*h_l*w_l written then read for each of the four pooled levels.
-#include "common.h"
+#include "metric_tiles.h"
 #include <cmath>
 
 namespace {
 
+using namespace evr_tiles;
+
 constexpr int R = 5;                 // Gaussian radius (11 taps)
 constexpr int LEVELS = 5;
 constexpr int MIN_SIDE = 161;        // 161 -> 81 -> 41 -> 21 -> 11: the fifth scale still holds one 11 x 11 window
-constexpr int MAX_GRID_Z = 65535;
 
 struct Gauss { double w[2 * R + 1]; };
 
 struct Finish {
     int levels;                      // 5 with ms_ssim, 1 for psnr alone
-    int tile_off[LEVELS], tiles[LEVELS], tiles_total;
+    LevelTiles<LEVELS> t;
     double map_px[LEVELS];           // (h_l - 10) * (w_l - 10)
     double inv_px;                   // 1 / (H * W)
     double wgt[LEVELS];
 };
-
-__device__ __forceinline__ double to_f64(float v) { return (double)v; }
-__device__ __forceinline__ double to_f64(double v) { return v; }
 
 // X = reference, Y = image of one level: [n, h, w] of T.  partials: [n, tiles_total, 3] = {sum cs, sum s, sum sq err}, this
 // level's tiles starting at tile_off.  PX / PY: the next level [n, h2, w2] in fp64, or null (last scale, psnr alone).
@@ -101,21 +100,7 @@ __global__ __launch_bounds__(256) void fr_scale_kernel(const T* __restrict__ Xl,
             }
         }
         // pass 1: along axis 0, for every column of the haloed tile (rows r .. r + 10 of the staged tile centre on row r)
-        for (int i = tid; i < TH * IW; i += 256) {
-            const int r = i / IW, c = i % IW;
-            double a[5];
-            {
-                const double x = to_f64(sx[r][c]), y = to_f64(sy[r][c]);
-                a[0] = g.w[0] * x; a[1] = g.w[0] * y; a[2] = g.w[0] * (x * x); a[3] = g.w[0] * (y * y); a[4] = g.w[0] * (x * y);
-            }
-#pragma unroll
-            for (int k = 1; k <= 2 * R; ++k) {
-                const double x = to_f64(sx[r + k][c]), y = to_f64(sy[r + k][c]);
-                a[0] += g.w[k] * x; a[1] += g.w[k] * y; a[2] += g.w[k] * (x * x); a[3] += g.w[k] * (y * y); a[4] += g.w[k] * (x * y);
-            }
-#pragma unroll
-            for (int k = 0; k < 5; ++k) v[k][r][c] = a[k];
-        }
+        moments_pass1<2 * R + 1, TH, TW>(sx, sy, g.w, v);
         __syncthreads();
         // pass 2: along axis 1, and the cs / s maps over the valid region
         const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
@@ -124,13 +109,7 @@ __global__ __launch_bounds__(256) void fr_scale_kernel(const T* __restrict__ Xl,
             const int gy = y0 + r, gx = x0 + c;
             if (gy < R || gy >= h - R || gx < R || gx >= w - R) continue;
             double u[5];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                double a = g.w[0] * v[k][r][c];
-#pragma unroll
-                for (int j = 1; j <= 2 * R; ++j) a += g.w[j] * v[k][r][c + j];
-                u[k] = a;
-            }
+            moments_pass2<2 * R + 1, TH, TW>(v, g.w, r, c, u);
             const double ux = u[0], uy = u[1];
             const double vx = u[2] - ux * ux, vy = u[3] - uy * uy, vxy = u[4] - ux * uy;
             const double cs = (2.0 * vxy + C2) / (vx + vy + C2);
@@ -138,14 +117,7 @@ __global__ __launch_bounds__(256) void fr_scale_kernel(const T* __restrict__ Xl,
             scs += cs; ss += s;
         }
     }
-    se = evr_wave_sum(se); scs = evr_wave_sum(scs); ss = evr_wave_sum(ss);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) { red[0][wave] = scs; red[1][wave] = ss; red[2][wave] = se; }
-    __syncthreads();
-    if (tid < 3) {
-        const int64_t t = (int64_t)f * tiles_total + tile_off + (int64_t)ty * gridDim.x + tx;
-        partials[t * 3 + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
-    }
+    tile_partials(red, partials, [&] { return (int64_t)f * tiles_total + tile_off; }, scs, ss, se);
 }
 
 // One block per frame: the partials of every level in tile order, then the scores.
@@ -153,16 +125,11 @@ __global__ __launch_bounds__(256) void fr_finish_kernel(const double* __restrict
                                                          double* __restrict__ out_scores, double* __restrict__ out_scales, int f0) {
     __shared__ double red[4];
     __shared__ double tot[LEVELS][3];
-    const int f = blockIdx.x + f0, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = blockIdx.x + f0, tid = threadIdx.x;
     for (int l = 0; l < p.levels; ++l) {
         for (int q = 0; q < 3; ++q) {
-            double a = 0.0;
-            const double* src = partials + ((int64_t)f * p.tiles_total + p.tile_off[l]) * 3 + q;
-            for (int t = tid; t < p.tiles[l]; t += 256) a += src[(int64_t)t * 3];
-            a = evr_wave_sum(a);
-            if (lane == 0) red[wave] = a;
-            __syncthreads();
-            if (tid == 0) tot[l][q] = ((red[0] + red[1]) + red[2]) + red[3];
+            const double a = frame_total<3>(partials + ((int64_t)f * p.t.tiles_total + p.t.tile_off[l]) * 3 + q, p.t.tiles[l], red);
+            if (tid == 0) tot[l][q] = a;
             __syncthreads();
         }
     }
@@ -196,30 +163,16 @@ __global__ __launch_bounds__(256) void fr_finish_kernel(const double* __restrict
 constexpr int TH0 = 16, TW0 = 64;    // scale 1 (fp32 staging): the tile of metrics.hip, 62 KiB of LDS -> two blocks per CU
 constexpr int THP = 16, TWP = 32;    // pooled scales (fp64 staging): 44 KiB -> three blocks per CU
 
-struct Plan {
-    int levels, h[LEVELS], w[LEVELS], tx[LEVELS], ty[LEVELS], tile_off[LEVELS], tiles_total;
-    size_t level_off[LEVELS];        // bytes from the workspace start to level l's reference plane block (l >= 1)
-    size_t partial_off, bytes;
-};
+using FrPlan = Plan<LEVELS>;
 
-Plan make_plan(int n, int H, int W) {
-    Plan p{};
-    p.levels = (H < W ? H : W) >= MIN_SIDE ? LEVELS : 1;
-    size_t off = 0;
-    for (int l = 0; l < p.levels; ++l) {
-        p.h[l] = l ? (p.h[l - 1] + 1) / 2 : H;
-        p.w[l] = l ? (p.w[l - 1] + 1) / 2 : W;
+FrPlan make_plan(int n, int H, int W) {
+    FrPlan p{};
+    const int levels = (H < W ? H : W) >= MIN_SIDE ? LEVELS : 1;
+    for (int l = 0, h = H, w = W; l < levels; ++l, h = (h + 1) / 2, w = (w + 1) / 2) {
         const int th = l ? THP : TH0, tw = l ? TWP : TW0;
-        p.ty[l] = (p.h[l] + th - 1) / th; p.tx[l] = (p.w[l] + tw - 1) / tw;
-        p.tile_off[l] = p.tiles_total;
-        p.tiles_total += p.tx[l] * p.ty[l];
-        if (l) {
-            p.level_off[l] = off;
-            off += evr::align_up((size_t)2 * n * p.h[l] * p.w[l] * sizeof(double), 256);
-        }
+        p.add_level(n, h, w, (h + th - 1) / th, (w + tw - 1) / tw);
     }
-    p.partial_off = off;
-    p.bytes = off + (size_t)n * p.tiles_total * 3 * sizeof(double) + 256;
+    p.close(n, 3);
     return p;
 }
 
@@ -240,7 +193,7 @@ extern "C" int evr_fr_metrics(const float* img, const float* ref, int n, int H, 
                 MIN_SIDE, H, W);
     if (n == 0) return EVR_OK;
     EVR_REQUIRE(img && ref && out_scores, "evr_fr_metrics: null pointer");
-    const Plan p = make_plan(n, H, W);
+    const FrPlan p = make_plan(n, H, W);
     if (!workspace || workspace_bytes < p.bytes) {
         evr::set_error("evr_fr_metrics: workspace %zu B < required %zu B", workspace_bytes, p.bytes);
         return EVR_ERR_WORKSPACE;
@@ -251,41 +204,32 @@ extern "C" int evr_fr_metrics(const float* img, const float* ref, int n, int H, 
         for (int i = -R; i <= R; ++i) { g.w[i + R] = std::exp(-0.5 * (double)i * (double)i / 2.25); sum += g.w[i + R]; }
         for (int i = 0; i < 2 * R + 1; ++i) g.w[i] /= sum;
     }
-    char* base = (char*)workspace;
-    double* partials = (double*)(base + p.partial_off);
+    double* partials = p.partials(workspace);
     const int levels = (which & 2u) ? LEVELS : 1;
     Finish fin{};
     fin.levels = levels;
-    fin.tiles_total = p.tiles_total;
+    fin.t = p.t;
     fin.inv_px = 1.0 / ((double)H * W);
     const double wgt[LEVELS] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};
     for (int l = 0; l < levels; ++l) {
-        fin.tile_off[l] = p.tile_off[l]; fin.tiles[l] = p.tx[l] * p.ty[l];
         fin.map_px[l] = (double)(p.h[l] - 2 * R) * (double)(p.w[l] - 2 * R);
         fin.wgt[l] = wgt[l];
     }
-    for (int f0 = 0; f0 < n; f0 += MAX_GRID_Z) {
-        const int nf = n - f0 < MAX_GRID_Z ? n - f0 : MAX_GRID_Z;
+    return for_frame_chunks(n, [&](int f0, int nf) -> int {
         for (int l = 0; l < levels; ++l) {
-            double* nx = nullptr; double* ny = nullptr;
-            int h2 = 0, w2 = 0;
-            if (l + 1 < levels) {
-                h2 = p.h[l + 1]; w2 = p.w[l + 1];
-                nx = (double*)(base + p.level_off[l + 1]); ny = nx + (size_t)n * h2 * w2;
-            }
+            const FrPlan::Next nx = p.next(workspace, l, levels, n);
             if (l == 0) {
-                hipLaunchKernelGGL((fr_scale_kernel<float, TH0, TW0>), dim3(p.tx[0], p.ty[0], nf), dim3(256), 0, stream, ref, img, H, W,
-                                   clip, which, g, partials, p.tiles_total, p.tile_off[0], nx, ny, h2, w2, f0);
+                hipLaunchKernelGGL((fr_scale_kernel<float, TH0, TW0>), dim3(p.tx[0], p.ty[0], nf), dim3(NT), 0, stream, ref, img, H, W,
+                                   clip, which, g, partials, p.t.tiles_total, p.t.tile_off[0], nx.x, nx.y, nx.h, nx.w, f0);
             } else {
-                const double* cx = (const double*)(base + p.level_off[l]);
-                const double* cy = cx + (size_t)n * p.h[l] * p.w[l];
-                hipLaunchKernelGGL((fr_scale_kernel<double, THP, TWP>), dim3(p.tx[l], p.ty[l], nf), dim3(256), 0, stream, cx, cy, p.h[l],
-                                   p.w[l], 0, which, g, partials, p.tiles_total, p.tile_off[l], nx, ny, h2, w2, f0);
+                hipLaunchKernelGGL((fr_scale_kernel<double, THP, TWP>), dim3(p.tx[l], p.ty[l], nf), dim3(NT), 0, stream,
+                                   (const double*)p.plane(workspace, l, 0, n), (const double*)p.plane(workspace, l, 1, n), p.h[l],
+                                   p.w[l], 0, which, g, partials, p.t.tiles_total, p.t.tile_off[l], nx.x, nx.y, nx.h, nx.w, f0);
             }
             EVR_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(fr_finish_kernel, dim3(nf), dim3(256), 0, stream, partials, fin, which, out_scores, out_scales, f0);
+        hipLaunchKernelGGL(fr_finish_kernel, dim3(nf), dim3(NT), 0, stream, partials, fin, which, out_scores, out_scales, f0);
         EVR_LAUNCH_CHECK();
-    }
-    return EVR_OK;
+        return EVR_OK;
+    });
 }

@@ -30,17 +30,17 @@
 // of step 3 -- the dropped odd row or column is never read); forms both gradient magnitudes and q, writes the map if asked and
 // reduces sum d and sum d^2 to one fp64 pair per tile.  The finisher adds a frame's pairs in tile order and writes the score
 // and 1 - sum d / N.  No atomics: a frame's numbers and its map do not depend on n, on its place in the batch or on earlier
-// calls.  Algorithmic bytes per frame: 2*4*H*W read (8*h2*w2 written with the map).
-#include "common.h"
+// calls (the tile and frame sums and the frame chunks are the family's scaffold, metric_tiles.h).  Algorithmic bytes per frame: 2*4*H*W read (8*h2*w2 written with the map).
+#include "metric_tiles.h"
 #include <cmath>
 
 namespace {
 
+using namespace evr_tiles;
+
 constexpr int TH = 16, TW = 32;              // pooled pixels per tile: 512, two per thread
 constexpr int PH = TH + 2, PW = TW + 2;      // ... with the one-pixel halo
 constexpr int SH = 2 * PH, SW = 2 * PW;      // the source pixels under them (36 x 68)
-constexpr int NT = 256;
-constexpr int MAX_GRID_Z = 65535;
 
 __device__ __forceinline__ float quant(float v, int clip) {
     if (clip) v = fminf(fmaxf(v, 0.f), 1.f);
@@ -107,14 +107,7 @@ __global__ __launch_bounds__(NT) void gmsd_tile_kernel(const float* __restrict__
         const double d = 1.0 - q;
         sd += d; sd2 += d * d;
     }
-    sd = evr_wave_sum(sd); sd2 = evr_wave_sum(sd2);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) { red[0][wave] = sd; red[1][wave] = sd2; }
-    __syncthreads();
-    if (tid < 2) {
-        const int64_t t = (int64_t)f * gridDim.x * gridDim.y + (int64_t)ty * gridDim.x + tx;
-        partials[t * 2 + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
-    }
+    tile_partials(red, partials, [&] { return (int64_t)f * gridDim.x * gridDim.y; }, sd, sd2);
 }
 
 // One block per frame: its tiles' pairs in tile order, then the score and the mean GMS.
@@ -122,15 +115,10 @@ __global__ __launch_bounds__(NT) void gmsd_finish_kernel(const double* __restric
                                                          double* __restrict__ out, int f0) {
     __shared__ double red[NT / 64];
     __shared__ double tot[2];
-    const int f = blockIdx.x + f0, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = blockIdx.x + f0, tid = threadIdx.x;
     for (int q = 0; q < 2; ++q) {
-        double s = 0.0;
-        const double* src = partials + (int64_t)f * tiles * 2 + q;
-        for (int t = tid; t < tiles; t += NT) s += src[(int64_t)t * 2];
-        s = evr_wave_sum(s);
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (tid == 0) tot[q] = ((red[0] + red[1]) + red[2]) + red[3];
+        const double s = frame_total<2>(partials + (int64_t)f * tiles * 2 + q, tiles, red);
+        if (tid == 0) tot[q] = s;
         __syncthreads();
     }
     if (tid != 0) return;
@@ -167,12 +155,11 @@ extern "C" int evr_gmsd(const float* img, const float* ref, int n, int H, int W,
     const int gy = (h2 + TH - 1) / TH, gx = (w2 + TW - 1) / TW;
     EVR_REQUIRE(gy <= 65535, "evr_gmsd: frames of more than %d rows are not supported, got %d", 65535 * 2 * TH, H);
     double* partials = (double*)workspace;
-    for (int f0 = 0; f0 < n; f0 += MAX_GRID_Z) {
-        const int nf = n - f0 < MAX_GRID_Z ? n - f0 : MAX_GRID_Z;
+    return for_frame_chunks(n, [&](int f0, int nf) -> int {
         hipLaunchKernelGGL(gmsd_tile_kernel, dim3(gx, gy, nf), dim3(NT), 0, stream, img, ref, H, W, h2, w2, clip, partials, out_map, f0);
         EVR_LAUNCH_CHECK();
         hipLaunchKernelGGL(gmsd_finish_kernel, dim3(nf), dim3(NT), 0, stream, partials, gx * gy, (double)h2 * (double)w2, out, f0);
         EVR_LAUNCH_CHECK();
-    }
-    return EVR_OK;
+        return EVR_OK;
+    });
 }

@@ -13,12 +13,15 @@
 //          5-pixel border cropped.
 // One kernel reads each input pixel from HBM once (plus tile halos, served by L2): tiles of
 // 16 x 64 outputs, inputs + halo staged in LDS, both filter passes on chip, per-tile fp64 partial
-// sums; a second tiny kernel adds the partials in fixed order (deterministic).
+// sums; a second tiny kernel adds the partials in fixed order (deterministic).  The sums and the
+// chunks of at most 65535 frames per launch are the family's scaffold (metric_tiles.h).
 // Algorithmic bytes per frame: 2*4*H*W.
-#include "common.h"
+#include "metric_tiles.h"
 #include <cmath>
 
 namespace {
+
+using namespace evr_tiles;
 
 constexpr int R = 5;              // Gaussian radius: int(3.5*1.5+0.5)
 constexpr int TH = 16, TW = 64;   // output tile
@@ -37,11 +40,11 @@ __device__ __forceinline__ int reflect(int i, int n) {
 
 __global__ __launch_bounds__(256) void metrics_tile_kernel(const float* __restrict__ img, const float* __restrict__ ref,
                                                             int H, int W, int clip, unsigned which, Gauss g,
-                                                            double* __restrict__ partials, int tiles_x, int tiles_y) {
+                                                            double* __restrict__ partials, int tiles_x, int tiles_y, int f0) {
     __shared__ float sx[IH][IW + 1], sy[IH][IW + 1];
     __shared__ float v[5][TH][IW + 1];     // after the vertical pass: ux, uy, uxx, uyy, uxy
     __shared__ double red[2][4];
-    const int f = blockIdx.z, ty = blockIdx.y, tx = blockIdx.x, tid = threadIdx.x;
+    const int f = blockIdx.z + f0, ty = blockIdx.y, tx = blockIdx.x, tid = threadIdx.x;
     const float* X = ref + (int64_t)f * H * W;   // skimage argument order: (ref, img) -> im1 = ref
     const float* Y = img + (int64_t)f * H * W;
     const int y0 = ty * TH, x0 = tx * TW;
@@ -114,33 +117,19 @@ __global__ __launch_bounds__(256) void metrics_tile_kernel(const float* __restri
             ss += (double)S;
         }
     }
-    se = evr_wave_sum(se); ss = evr_wave_sum(ss);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) { red[0][wave] = se; red[1][wave] = ss; }
-    __syncthreads();
-    if (tid < 2) {
-        const int64_t t = ((int64_t)f * tiles_y + ty) * tiles_x + tx;
-        partials[t * 2 + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
-    }
+    tile_partials(red, partials, [&] { return (int64_t)f * tiles_y * tiles_x; }, se, ss);
 }
 
 __global__ __launch_bounds__(256) void metrics_reduce_kernel(const double* __restrict__ partials, double* __restrict__ out,
-                                                              int n_tiles, double inv_mse, double inv_ssim, unsigned which) {
+                                                              int n_tiles, double inv_mse, double inv_ssim, unsigned which, int f0) {
     __shared__ double red[2][4];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double a = 0, b = 0;
-    for (int t = tid; t < n_tiles; t += 256) {
-        a += partials[((int64_t)f * n_tiles + t) * 2];
-        b += partials[((int64_t)f * n_tiles + t) * 2 + 1];
-    }
-    a = evr_wave_sum(a); b = evr_wave_sum(b);
-    if (lane == 0) { red[0][wave] = a; red[1][wave] = b; }
-    __syncthreads();
-    if (tid == 0) {
-        const double sa = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        const double sb = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-        out[f * 2 + 0] = (which & 1u) ? sa * inv_mse : 0.0;
-        out[f * 2 + 1] = (which & 2u) ? sb * inv_ssim : 0.0;
+    const int f = blockIdx.x + f0;
+    const double* src = partials + (int64_t)f * n_tiles * 2;
+    const double sa = frame_total<2>(src, n_tiles, red[0]);
+    const double sb = frame_total<2>(src + 1, n_tiles, red[1]);
+    if (threadIdx.x == 0) {
+        out[(int64_t)f * 2 + 0] = (which & 1u) ? sa * inv_mse : 0.0;
+        out[(int64_t)f * 2 + 1] = (which & 2u) ? sb * inv_ssim : 0.0;
     }
 }
 
@@ -176,13 +165,15 @@ extern "C" int evr_metrics(const float* img, const float* ref, int n, int H, int
     }
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
     double* partials = (double*)workspace;
-    hipLaunchKernelGGL(metrics_tile_kernel, dim3(tiles_x, tiles_y, n), dim3(256), 0, stream, img, ref, H, W, clip, which,
-                       g, partials, tiles_x, tiles_y);
-    EVR_LAUNCH_CHECK();
     const double inv_mse = 1.0 / ((double)H * W);
     const double inv_ssim = (which & 2u) ? 1.0 / ((double)(H - 2 * R) * (W - 2 * R)) : 0.0;
-    hipLaunchKernelGGL(metrics_reduce_kernel, dim3(n), dim3(256), 0, stream, partials, out, tiles_x * tiles_y, inv_mse,
-                       inv_ssim, which);
-    EVR_LAUNCH_CHECK();
-    return EVR_OK;
+    return for_frame_chunks(n, [&](int f0, int nf) -> int {
+        hipLaunchKernelGGL(metrics_tile_kernel, dim3(tiles_x, tiles_y, nf), dim3(NT), 0, stream, img, ref, H, W, clip, which,
+                           g, partials, tiles_x, tiles_y, f0);
+        EVR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(metrics_reduce_kernel, dim3(nf), dim3(NT), 0, stream, partials, out, tiles_x * tiles_y, inv_mse,
+                           inv_ssim, which, f0);
+        EVR_LAUNCH_CHECK();
+        return EVR_OK;
+    });
 }

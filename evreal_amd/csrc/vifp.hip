@@ -28,9 +28,9 @@
 //   * runs both separable passes of the five moments on chip and reduces its num and den terms to one fp64 pair.
 // So each level is read once and the next one written once.  The next level's anchors reach further (side - N' + 1 > side - N
 // + 1): the grid covers them and the moment sums are masked to their own domain.  A finishing launch (one work-group per
-// frame) adds a frame's pairs in tile order and forms the ratio.  No atomics, and the number of work-groups depends on the
-// shape alone: a frame's nine numbers are bitwise independent of n and of its place in the batch.  Frames ride the grid's z
-// axis, chunked at 65535.
+// frame) adds a frame's pairs in tile order and forms the ratio.  The moment passes, the tile and frame sums, the workspace
+// plan and the frame chunks are the family's scaffold (metric_tiles.h): a frame's nine numbers are bitwise independent of n
+// and of its place in the batch.
 //
 // Tile: 16 x 32 anchors at every scale, 256 threads, two anchors per thread.  LDS at scale 1 (the largest): 2 staged planes of
 // 32 x 48 doubles (rows padded to 49: 25,088 B) + 5 intermediate planes of 16 x 48 (31,360 B) + 64 B = 56,512 B, so two
@@ -39,17 +39,17 @@
 // wave walk consecutive doubles of a row in both passes (ds_read_b64, 32 lanes a group: conflict-free but where a group wraps
 // to the next row in pass 1, two-way).  Algorithmic bytes per frame: 2*4*H*W read at scale 1, 2*8*h*w written then read for
 // each of the three lower levels (0.33 of a frame's pixels together).
-#include "common.h"
+#include "metric_tiles.h"
 #include <cmath>
 
 namespace {
+
+using namespace evr_tiles;
 
 constexpr int SCALES = 4;
 constexpr int MIN_SIDE = 41;         // 41 -> 17 -> 7 -> 3: the fourth scale still holds one 3 x 3 window
 constexpr int MAX_TAPS = 17;
 constexpr int TH = 16, TW = 32;      // anchors per tile (both even: a tile owns whole next-level pixels)
-constexpr int NT = 256;
-constexpr int MAX_GRID_Z = 65535;
 constexpr double EPS = 1e-10, SIGMA_NSQ = 2.0;
 
 constexpr int taps_of(int s) { return (1 << (5 - s)) + 1; }      // s = 1..4
@@ -67,8 +67,6 @@ void make_taps(int s, double* w) {
     }
     for (int k = 0; k < N; ++k) w[k] /= sum;
 }
-
-struct Finish { int tile_off[SCALES], tiles[SCALES], tiles_total; };
 
 __device__ __forceinline__ double stage(float v, int clip) {
     if (clip) v = fminf(fmaxf(v, 0.f), 1.f);
@@ -123,21 +121,7 @@ __global__ __launch_bounds__(NT) void vifp_scale_kernel(const T* __restrict__ Xl
     }
 
     // pass 1: along axis 0, for every staged column (rows r .. r + N - 1 belong to anchor row r)
-    for (int i = tid; i < TH * IW; i += NT) {
-        const int r = i / IW, c = i % IW;
-        double a[5];
-        {
-            const double x = sx[r][c], y = sy[r][c];
-            a[0] = g.w[0] * x; a[1] = g.w[0] * y; a[2] = g.w[0] * (x * x); a[3] = g.w[0] * (y * y); a[4] = g.w[0] * (x * y);
-        }
-#pragma unroll
-        for (int k = 1; k < N; ++k) {
-            const double x = sx[r + k][c], y = sy[r + k][c];
-            a[0] += g.w[k] * x; a[1] += g.w[k] * y; a[2] += g.w[k] * (x * x); a[3] += g.w[k] * (y * y); a[4] += g.w[k] * (x * y);
-        }
-#pragma unroll
-        for (int k = 0; k < 5; ++k) v[k][r][c] = a[k];
-    }
+    moments_pass1<N, TH, TW>(sx, sy, g.w, v);
     __syncthreads();
 
     // pass 2: along axis 1, and the num / den terms over this scale's own valid region
@@ -146,13 +130,7 @@ __global__ __launch_bounds__(NT) void vifp_scale_kernel(const T* __restrict__ Xl
         const int r = i / TW, c = i % TW;
         if (y0 + r > h - N || x0 + c > w - N) continue;
         double u[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            double a = g.w[0] * v[k][r][c];
-#pragma unroll
-            for (int j = 1; j < N; ++j) a += g.w[j] * v[k][r][c + j];
-            u[k] = a;
-        }
+        moments_pass2<N, TH, TW>(v, g.w, r, c, u);
         const double mu1 = u[0], mu2 = u[1];
         double s1 = u[2] - mu1 * mu1, s2 = u[3] - mu2 * mu2;
         const double s12 = u[4] - mu1 * mu2;
@@ -167,31 +145,19 @@ __global__ __launch_bounds__(NT) void vifp_scale_kernel(const T* __restrict__ Xl
         num += log10(1.0 + ((gain * gain) * s1) / (sv + SIGMA_NSQ));
         den += log10(1.0 + s1 / SIGMA_NSQ);
     }
-    num = evr_wave_sum(num); den = evr_wave_sum(den);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) { red[0][wave] = num; red[1][wave] = den; }
-    __syncthreads();
-    if (tid < 2) {
-        const int64_t t = (int64_t)f * tiles_total + tile_off + (int64_t)ty * gridDim.x + tx;
-        partials[t * 2 + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
-    }
+    tile_partials(red, partials, [&] { return (int64_t)f * tiles_total + tile_off; }, num, den);
 }
 
 // One block per frame: the pairs of every scale in tile order, then the row {score, num_1..4, den_1..4}.
-__global__ __launch_bounds__(NT) void vifp_finish_kernel(const double* __restrict__ partials, Finish p, double* __restrict__ out,
-                                                         int f0) {
+__global__ __launch_bounds__(NT) void vifp_finish_kernel(const double* __restrict__ partials, LevelTiles<SCALES> p,
+                                                         double* __restrict__ out, int f0) {
     __shared__ double red[NT / 64];
     __shared__ double tot[SCALES][2];
-    const int f = blockIdx.x + f0, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = blockIdx.x + f0, tid = threadIdx.x;
     for (int l = 0; l < SCALES; ++l) {
         for (int q = 0; q < 2; ++q) {
-            double a = 0.0;
-            const double* src = partials + ((int64_t)f * p.tiles_total + p.tile_off[l]) * 2 + q;
-            for (int t = tid; t < p.tiles[l]; t += NT) a += src[(int64_t)t * 2];
-            a = evr_wave_sum(a);
-            if (lane == 0) red[wave] = a;
-            __syncthreads();
-            if (tid == 0) tot[l][q] = ((red[0] + red[1]) + red[2]) + red[3];
+            const double a = frame_total<2>(partials + ((int64_t)f * p.tiles_total + p.tile_off[l]) * 2 + q, p.tiles[l], red);
+            if (tid == 0) tot[l][q] = a;
             __syncthreads();
         }
     }
@@ -204,50 +170,28 @@ __global__ __launch_bounds__(NT) void vifp_finish_kernel(const double* __restric
     for (int l = 0; l < SCALES; ++l) { o[1 + l] = tot[l][0]; o[5 + l] = tot[l][1]; }
 }
 
-struct Plan {
-    int h[SCALES], w[SCALES], tx[SCALES], ty[SCALES], tile_off[SCALES], tiles_total;
-    size_t level_off[SCALES];        // bytes from the workspace start to level l's reference plane block (l >= 1)
-    size_t partial_off, bytes;
-};
+using VifPlan = Plan<SCALES>;
 
-Plan make_plan(int n, int H, int W) {
-    Plan p{};
-    size_t off = 0;
-    for (int l = 0; l < SCALES; ++l) {
-        const int N = taps_of(l + 1);
-        p.h[l] = l ? (p.h[l - 1] - N + 2) / 2 : H;              // ceil((side - N + 1) / 2)
-        p.w[l] = l ? (p.w[l - 1] - N + 2) / 2 : W;
-        if (l) {
-            p.level_off[l] = off;
-            off += evr::align_up((size_t)2 * n * p.h[l] * p.w[l] * sizeof(double), 256);
-        }
-    }
-    for (int l = 0; l < SCALES; ++l) {
+VifPlan make_plan(int n, int H, int W) {
+    VifPlan p{};
+    for (int l = 0, h = H, w = W; l < SCALES; ++l) {
         // anchors: the next level's valid domain where there is one (it contains this scale's own)
         const int N = l + 1 < SCALES ? taps_of(l + 2) : taps_of(l + 1);
-        p.ty[l] = (p.h[l] - N + 1 + TH - 1) / TH; p.tx[l] = (p.w[l] - N + 1 + TW - 1) / TW;
-        p.tile_off[l] = p.tiles_total;
-        p.tiles_total += p.tx[l] * p.ty[l];
+        p.add_level(n, h, w, (h - N + 1 + TH - 1) / TH, (w - N + 1 + TW - 1) / TW);
+        h = (h - N + 2) / 2; w = (w - N + 2) / 2;               // the next level: ceil((side - N + 1) / 2)
     }
-    p.partial_off = off;
-    p.bytes = off + (size_t)n * p.tiles_total * 2 * sizeof(double) + 256;
+    p.close(n, 2);
     return p;
 }
 
 template <typename T, int N, int NN>
-void launch_scale(const T* x, const T* y, const Plan& p, int l, int n, int nf, int f0, int clip, char* base, double* partials,
-                  hipStream_t stream) {
+void launch_scale(const T* x, const T* y, const VifPlan& p, int l, int n, int nf, int f0, int clip, void* ws, hipStream_t stream) {
     Taps g{};
     make_taps(l + 1, g.w);
-    double* nx = nullptr; double* ny = nullptr;
-    int h2 = 0, w2 = 0;
-    if (l + 1 < SCALES) {
-        make_taps(l + 2, g.wn);
-        h2 = p.h[l + 1]; w2 = p.w[l + 1];
-        nx = (double*)(base + p.level_off[l + 1]); ny = nx + (size_t)n * h2 * w2;
-    }
+    if (l + 1 < SCALES) make_taps(l + 2, g.wn);
+    const VifPlan::Next nx = p.next(ws, l, SCALES, n);
     hipLaunchKernelGGL((vifp_scale_kernel<T, N, NN>), dim3(p.tx[l], p.ty[l], nf), dim3(NT), 0, stream, x, y, p.h[l], p.w[l], clip, g,
-                       partials, p.tiles_total, p.tile_off[l], nx, ny, h2, w2, f0);
+                       p.partials(ws), p.t.tiles_total, p.t.tile_off[l], nx.x, nx.y, nx.h, nx.w, f0);
 }
 
 }  // namespace
@@ -273,30 +217,21 @@ extern "C" int evr_vifp(const float* img, const float* ref, int n, int H, int W,
                 MIN_SIDE, H, W);
     if (n == 0) return EVR_OK;
     EVR_REQUIRE(img && ref && out, "evr_vifp: null pointer");
-    const Plan p = make_plan(n, H, W);
+    const VifPlan p = make_plan(n, H, W);
     EVR_REQUIRE(workspace && workspace_bytes >= p.bytes, "evr_vifp: workspace %zu B < required %zu B", workspace_bytes, p.bytes);
     EVR_REQUIRE(p.ty[0] <= 65535, "evr_vifp: frames of more than %d rows are not supported, got %d", 65535 * TH, H);
-    char* base = (char*)workspace;
-    double* partials = (double*)(base + p.partial_off);
-    Finish fin{};
-    fin.tiles_total = p.tiles_total;
-    for (int l = 0; l < SCALES; ++l) { fin.tile_off[l] = p.tile_off[l]; fin.tiles[l] = p.tx[l] * p.ty[l]; }
-    auto level = [&](int l, int which) {
-        const double* x = (const double*)(base + p.level_off[l]);
-        return which ? x + (size_t)n * p.h[l] * p.w[l] : x;
-    };
-    for (int f0 = 0; f0 < n; f0 += MAX_GRID_Z) {
-        const int nf = n - f0 < MAX_GRID_Z ? n - f0 : MAX_GRID_Z;
-        launch_scale<float, 17, 9>(ref, img, p, 0, n, nf, f0, clip, base, partials, stream);
+    auto level = [&](int l, int which) { return (const double*)p.plane(workspace, l, which, n); };
+    return for_frame_chunks(n, [&](int f0, int nf) -> int {
+        launch_scale<float, 17, 9>(ref, img, p, 0, n, nf, f0, clip, workspace, stream);
         EVR_LAUNCH_CHECK();
-        launch_scale<double, 9, 5>(level(1, 0), level(1, 1), p, 1, n, nf, f0, 0, base, partials, stream);
+        launch_scale<double, 9, 5>(level(1, 0), level(1, 1), p, 1, n, nf, f0, 0, workspace, stream);
         EVR_LAUNCH_CHECK();
-        launch_scale<double, 5, 3>(level(2, 0), level(2, 1), p, 2, n, nf, f0, 0, base, partials, stream);
+        launch_scale<double, 5, 3>(level(2, 0), level(2, 1), p, 2, n, nf, f0, 0, workspace, stream);
         EVR_LAUNCH_CHECK();
-        launch_scale<double, 3, 1>(level(3, 0), level(3, 1), p, 3, n, nf, f0, 0, base, partials, stream);
+        launch_scale<double, 3, 1>(level(3, 0), level(3, 1), p, 3, n, nf, f0, 0, workspace, stream);
         EVR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(vifp_finish_kernel, dim3(nf), dim3(NT), 0, stream, partials, fin, out, f0);
+        hipLaunchKernelGGL(vifp_finish_kernel, dim3(nf), dim3(NT), 0, stream, p.partials(workspace), p.t, out, f0);
         EVR_LAUNCH_CHECK();
-    }
-    return EVR_OK;
+        return EVR_OK;
+    });
 }

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .prepost import Workspace
 
 NUM_FEATURES = 36
 BLOCK = 96
@@ -79,9 +80,10 @@ def save_niqe_model(path, mu, cov, source):
     np.savez(path, mu=mu, cov=cov, source=np.array(source))
 
 
-class NIQE:
+class NIQE(Workspace):
     """NIQE scores of cuda fp32 frames [n,H,W] -> cuda fp64 [n] (NaN for a frame without a whole 96x96 block).
     `model`: a dict with mu / cov (load_niqe_model) or a path.  The workspace is kept between calls."""
+    _workspace_bytes = 'evr_niqe_workspace_bytes'
 
     def __init__(self, model):
         _lib.require_gpu()
@@ -95,12 +97,6 @@ class NIQE:
                                             ctypes.byref(h)), 'evr_niqe_create')
         self.handle = h
         self.ws = None
-
-    def _workspace(self, n, H, W, device):
-        need = int(self.lib.evr_niqe_workspace_bytes(n, H, W))
-        if self.ws is None or self.ws.numel() < need or self.ws.device != device:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self.ws
 
     def __call__(self, img, clip=True, out=None):
         v = _as_frames(img)
@@ -302,10 +298,11 @@ def save_brisque_model(path, sv, coef, gamma, rho, fmin, fmax, lower, upper, sou
     np.savez(path, **m, source=np.array(source))
 
 
-class BRISQUE:
+class BRISQUE(Workspace):
     """BRISQUE scores of cuda fp32 frames [n,H,W] -> cuda fp64 [n] (NaN for a frame with a NaN feature, e.g. a flat one).
     `model`: a dict as load_brisque_model returns, or a path.  A model without support vectors gives features only.  The
     workspace is kept between calls."""
+    _workspace_bytes = 'evr_brisque_workspace_bytes'
 
     def __init__(self, model):
         _lib.require_gpu()
@@ -321,12 +318,6 @@ class BRISQUE:
                                                vp(m['fmax']), m['lower'], m['upper'], ctypes.byref(h)), 'evr_brisque_create')
         self.handle = h
         self.ws = None
-
-    def _workspace(self, n, H, W, device):
-        need = int(self.lib.evr_brisque_workspace_bytes(n, H, W))
-        if self.ws is None or self.ws.numel() < need or self.ws.device != device:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self.ws
 
     def __call__(self, img, clip=True, out=None):
         v = _as_frames(img)
@@ -372,20 +363,15 @@ PIQE_BLOCK = 16
 PIQE_ACTIVE, PIQE_WHSA, PIQE_WNC = 1, 2, 4      # the bits of a block's flag byte
 
 
-class PIQE:
+class PIQE(Workspace):
     """PIQE scores of cuda fp32 frames [n,H,W] -> cuda fp64 [n] (100 for a frame without an active block, e.g. a constant
     one).  No model: the metric is training-free.  The workspace is kept between calls."""
+    _workspace_bytes = 'evr_piqe_workspace_bytes'
 
     def __init__(self):
         _lib.require_gpu()
         self.lib = _lib.load()
         self.ws = None
-
-    def _workspace(self, n, H, W, device):
-        need = int(self.lib.evr_piqe_workspace_bytes(n, H, W))
-        if self.ws is None or self.ws.numel() < need or self.ws.device != device:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self.ws
 
     def __call__(self, img, clip=True, out=None):
         v = _as_frames(img)

@@ -78,33 +78,23 @@ def color_post_process_normalization(bgr_u8, norm, out=None, return_range=False)
     return out
 
 
-class Metrics:
-    """MSE + SSIM of utils/eval_metrics.py:77-97 (with the [0,1] clip of :253-255) for a batch of frames."""
+class Workspace:
+    """A handle's device workspace `ws`, sized by the library's `_workspace_bytes`(n, H, W): kept between calls, made anew
+    when it is too small or lives on another device."""
+    _workspace_bytes = None     # the entry point's name
 
-    def __init__(self):
-        self.lib = _lib.load()
-        self.ws = None
-
-    def __call__(self, img, ref, mse=True, ssim=True, clip=True):
-        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape
-        img = img.contiguous(); ref = ref.contiguous()
-        v = img if img.dim() == 3 else img.reshape(-1, img.shape[-2], img.shape[-1])
-        n, H, W = v.shape
-        need = self.lib.evr_metrics_workspace_bytes(n, H, W)
-        if self.ws is None or self.ws.numel() < need:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=img.device)
-        out = torch.empty((n, 2), dtype=torch.float64, device=img.device)
-        which = (1 if mse else 0) | (2 if ssim else 0)
-        _lib.check(self.lib.evr_metrics(_lib.ptr(img), _lib.ptr(ref), n, H, W, which, 1 if clip else 0,
-                                        _lib.ptr(out), _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()),
-                   'evr_metrics')
-        return out
+    def _workspace(self, n, H, W, device):
+        need = int(getattr(self.lib, self._workspace_bytes)(n, H, W))
+        if self.ws is None or self.ws.numel() < need or self.ws.device != device:
+            self.ws = torch.empty(need, dtype=torch.uint8, device=device)
+        return self.ws
 
 
-class FullRefMetrics:
-    """PSNR + MS-SSIM (pyiqa's `psnr` and `ms_ssim` on [0,1] gray frames, data_range 1) for a batch of frames, in fp64
-    (evr_fr_metrics).  Constructing one touches neither the library nor the GPU; the workspace is owned and grows on demand."""
-    MIN_SIDE = 161          # ms_ssim: five scales of an 11x11 window (pytorch-msssim asserts min(H, W) > 160)
+class PairMetric(Workspace):
+    """What the closed-form full-reference handles share.  Constructing one touches neither the library nor the GPU; the
+    workspace is owned and grows on demand."""
+    MIN_SIDE = 1
+    _too_small = None           # the metric's sentence, with {m} for MIN_SIDE and {H}, {W}
 
     def __init__(self):
         self.lib = None
@@ -112,32 +102,66 @@ class FullRefMetrics:
 
     @classmethod
     def too_small(cls, H, W):
-        """The message of the exception `ms_ssim` raises on frames of this size, or None where it is defined."""
+        """The message of the exception the metric raises on frames of this size, or None where it is defined."""
         if min(H, W) >= cls.MIN_SIDE:
             return None
-        return (f"ms_ssim needs frames of at least {cls.MIN_SIDE}x{cls.MIN_SIDE} pixels (five scales of an 11x11 window), "
-                f"got {H}x{W}")
+        return cls._too_small.format(m=cls.MIN_SIDE, H=H, W=W)
+
+    def _frames(self, img, ref, sized=True):
+        """cuda float32 [n,H,W] (or [H,W], or [...,H,W]) pairs -> (img, ref, n, H, W), contiguous, the library loaded and the
+        workspace ready.  sized: frames below MIN_SIDE raise ValueError, decided from the shape: no launch is tried."""
+        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dtype == ref.dtype == torch.float32
+        img = img.contiguous(); ref = ref.contiguous()
+        v = img if img.dim() == 3 else img.reshape(-1, img.shape[-2], img.shape[-1])
+        n, H, W = v.shape
+        if sized and self.too_small(H, W):
+            raise ValueError(self.too_small(H, W))
+        if self.lib is None:
+            self.lib = _lib.load()
+        self._workspace(n, H, W, img.device)
+        return img, ref, n, H, W
+
+    @staticmethod
+    def _out(out, shape, device):
+        """`out`, or a new tensor where it is None: contiguous cuda float64 of `shape`."""
+        if out is None:
+            return torch.empty(shape, dtype=torch.float64, device=device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == tuple(shape)
+        return out
+
+
+class Metrics(PairMetric):
+    """MSE + SSIM of utils/eval_metrics.py:77-97 (with the [0,1] clip of :253-255) for a batch of frames."""
+    _workspace_bytes = 'evr_metrics_workspace_bytes'
+
+    def __init__(self):
+        super().__init__()
+        self.lib = _lib.load()
+
+    def __call__(self, img, ref, mse=True, ssim=True, clip=True):
+        img, ref, n, H, W = self._frames(img, ref, sized=False)       # (the entry point refuses SSIM below 12x12)
+        out = self._out(None, (n, 2), img.device)
+        which = (1 if mse else 0) | (2 if ssim else 0)
+        _lib.check(self.lib.evr_metrics(_lib.ptr(img), _lib.ptr(ref), n, H, W, which, 1 if clip else 0,
+                                        _lib.ptr(out), _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()),
+                   'evr_metrics')
+        return out
+
+
+class FullRefMetrics(PairMetric):
+    """PSNR + MS-SSIM (pyiqa's `psnr` and `ms_ssim` on [0,1] gray frames, data_range 1) for a batch of frames, in fp64
+    (evr_fr_metrics)."""
+    MIN_SIDE = 161          # ms_ssim: five scales of an 11x11 window (pytorch-msssim asserts min(H, W) > 160)
+    _too_small = "ms_ssim needs frames of at least {m}x{m} pixels (five scales of an 11x11 window), got {H}x{W}"
+    _workspace_bytes = 'evr_fr_metrics_workspace_bytes'
 
     def __call__(self, img, ref, psnr=True, ms_ssim=True, clip=True, out=None, out_scales=None):
         """img, ref: cuda float32 [n,H,W] (or [H,W]) -> float64 [n,2] = (psnr, ms_ssim), 0 in a column not asked for.
         out / out_scales: optional contiguous float64 [n,2] / [n,10] to write into (out_scales: CS_1..5, S_1..5)."""
-        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dtype == ref.dtype == torch.float32
-        if self.lib is None:
-            self.lib = _lib.load()
-        img = img.contiguous(); ref = ref.contiguous()
-        v = img if img.dim() == 3 else img.reshape(-1, img.shape[-2], img.shape[-1])
-        n, H, W = v.shape
-        if ms_ssim and self.too_small(H, W):
-            raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
-        need = self.lib.evr_fr_metrics_workspace_bytes(n, H, W)
-        if self.ws is None or self.ws.numel() < need or self.ws.device != img.device:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=img.device)
-        if out is None:
-            out = torch.empty((n, 2), dtype=torch.float64, device=img.device)
-        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n, 2)
+        img, ref, n, H, W = self._frames(img, ref, sized=ms_ssim)
+        out = self._out(out, (n, 2), img.device)
         if out_scales is not None:
-            assert (out_scales.is_cuda and out_scales.dtype == torch.float64 and out_scales.is_contiguous()
-                    and tuple(out_scales.shape) == (n, 10))
+            self._out(out_scales, (n, 10), img.device)
         which = (1 if psnr else 0) | (2 if ms_ssim else 0)
         _lib.check(self.lib.evr_fr_metrics(_lib.ptr(img), _lib.ptr(ref), n, H, W, which, 1 if clip else 0, _lib.ptr(out),
                                            _lib.ptr(out_scales), _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()),
@@ -151,44 +175,21 @@ class FullRefMetrics:
         return self(img, ref, psnr=psnr, ms_ssim=True, clip=clip, out_scales=scales), scales
 
 
-class GMSD:
+class GMSD(PairMetric):
     """GMSD (Xue et al. 2014; pyiqa's `gmsd`) for a batch of frame pairs, in fp64 (evr_gmsd): frames quantised to
     rint(255 * clip(v)), 2x2 mean pooling, Prewitt / 3 with zero padding, GMS with c = 170, the standard deviation over the
-    pooled pixels with N - 1.  Constructing one touches neither the library nor the GPU; the workspace is owned and grows on
-    demand."""
+    pooled pixels with N - 1."""
     MIN_SIDE = 2            # one pixel of the 2x2-pooled plane
-
-    def __init__(self):
-        self.lib = None
-        self.ws = None
-
-    @classmethod
-    def too_small(cls, H, W):
-        """The message of the exception `gmsd` raises on frames of this size, or None where it is defined."""
-        if min(H, W) >= cls.MIN_SIDE:
-            return None
-        return f"gmsd needs frames of at least {cls.MIN_SIDE}x{cls.MIN_SIDE} pixels (it pools 2x2 first), got {H}x{W}"
+    _too_small = "gmsd needs frames of at least {m}x{m} pixels (it pools 2x2 first), got {H}x{W}"
+    _workspace_bytes = 'evr_gmsd_workspace_bytes'
 
     def stats(self, img, ref, clip=True, out=None, out_map=None):
         """img, ref: cuda float32 [n,H,W] (or [H,W]) -> float64 [n,2] = (score, mean GMS).
         out / out_map: optional contiguous float64 [n,2] / [n,H//2,W//2] to write into (out_map: the GMS map q)."""
-        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dtype == ref.dtype == torch.float32
-        img = img.contiguous(); ref = ref.contiguous()
-        v = img if img.dim() == 3 else img.reshape(-1, img.shape[-2], img.shape[-1])
-        n, H, W = v.shape
-        if self.too_small(H, W):
-            raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
-        if self.lib is None:
-            self.lib = _lib.load()
-        need = self.lib.evr_gmsd_workspace_bytes(n, H, W)
-        if self.ws is None or self.ws.numel() < need or self.ws.device != img.device:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=img.device)
-        if out is None:
-            out = torch.empty((n, 2), dtype=torch.float64, device=img.device)
-        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n, 2)
+        img, ref, n, H, W = self._frames(img, ref)
+        out = self._out(out, (n, 2), img.device)
         if out_map is not None:
-            assert (out_map.is_cuda and out_map.dtype == torch.float64 and out_map.is_contiguous()
-                    and tuple(out_map.shape) == (n, H // 2, W // 2))
+            self._out(out_map, (n, H // 2, W // 2), img.device)
         _lib.check(self.lib.evr_gmsd(_lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0, _lib.ptr(out), _lib.ptr(out_map),
                                      _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()), 'evr_gmsd')
         return out
@@ -204,41 +205,19 @@ class GMSD:
         return self.stats(img, ref, clip=clip, out_map=q), q
 
 
-class VIFP:
+class VIFP(PairMetric):
     """VIFp (Sheikh & Bovik 2006, pixel domain: vifp_mscale.m, sewar.vifp) for a batch of frame pairs, in fp64 (evr_vifp): four
     scales of Gaussian-windowed second moments of 255 * frame over the valid region, sum of the information that survives the
-    channel g*x + noise over the reference's own.  `img` is the reconstruction, `ref` the reference: the score is not symmetric.
-    Constructing one touches neither the library nor the GPU; the workspace is owned and grows on demand."""
+    channel g*x + noise over the reference's own.  `img` is the reconstruction, `ref` the reference: the score is not symmetric."""
     MIN_SIDE = 41           # 41 -> 17 -> 7 -> 3: one 3x3 window at the fourth scale
-
-    def __init__(self):
-        self.lib = None
-        self.ws = None
-
-    @classmethod
-    def too_small(cls, H, W):
-        """The message of the exception `vifp` raises on frames of this size, or None where it is defined."""
-        if min(H, W) >= cls.MIN_SIDE:
-            return None
-        return f"vifp needs frames of at least {cls.MIN_SIDE}x{cls.MIN_SIDE} pixels (four scales, the last one 3x3 window), got {H}x{W}"
+    _too_small = "vifp needs frames of at least {m}x{m} pixels (four scales, the last one 3x3 window), got {H}x{W}"
+    _workspace_bytes = 'evr_vifp_workspace_bytes'
 
     def stats(self, img, ref, clip=True, out=None):
         """img, ref: cuda float32 [n,H,W] (or [H,W]) -> float64 [n,9] = (score, num_1..4, den_1..4).
         out: optional contiguous float64 [n,9] to write into."""
-        assert img.is_cuda and ref.is_cuda and img.shape == ref.shape and img.dtype == ref.dtype == torch.float32
-        img = img.contiguous(); ref = ref.contiguous()
-        v = img if img.dim() == 3 else img.reshape(-1, img.shape[-2], img.shape[-1])
-        n, H, W = v.shape
-        if self.too_small(H, W):
-            raise ValueError(self.too_small(H, W))          # decided from the shape: no launch is tried
-        if self.lib is None:
-            self.lib = _lib.load()
-        need = self.lib.evr_vifp_workspace_bytes(n, H, W)
-        if self.ws is None or self.ws.numel() < need or self.ws.device != img.device:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=img.device)
-        if out is None:
-            out = torch.empty((n, 9), dtype=torch.float64, device=img.device)
-        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n, 9)
+        img, ref, n, H, W = self._frames(img, ref)
+        out = self._out(out, (n, 9), img.device)
         _lib.check(self.lib.evr_vifp(_lib.ptr(img), _lib.ptr(ref), n, H, W, 1 if clip else 0, _lib.ptr(out), _lib.ptr(self.ws),
                                      self.ws.numel(), _lib.stream_ptr()), 'evr_vifp')
         return out

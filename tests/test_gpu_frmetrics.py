@@ -112,6 +112,24 @@ def test_bitwise_independent_of_batch_and_position(fr):
     assert np.array_equal(only[:, 1], full[:, 1]) and not only[:, 0].any()
 
 
+def test_more_frames_than_one_grid_axis_holds(fr):
+    """Frames ride the grid's z axis, chunked at 65535: 65537 pairs of 2 x 2 with PSNR alone (65537 frames of the 161 x 161
+    MS-SSIM needs do not fit; the chunk loop is the same code) against the first and the last 100 computed alone, bit for bit,
+    and the last pair against the oracle within the 1e-9 dB of test_kernels_match_the_oracle."""
+    n = 65537
+    g = torch.Generator(device='cuda').manual_seed(65537)
+    imgs = torch.rand((n, 2, 2), device='cuda', generator=g)
+    refs = torch.rand((n, 2, 2), device='cuda', generator=g)
+    bits = lambda t: np.ascontiguousarray(t.cpu().numpy()).view(np.uint64)
+    full = fr(imgs, refs, ms_ssim=False)
+    for sl in (slice(0, 100), slice(n - 100, n)):
+        assert np.array_equal(bits(fr(imgs[sl].contiguous(), refs[sl].contiguous(), ms_ssim=False)), bits(full[sl]))
+    k = n - 1
+    got, want = full[k].cpu().numpy(), FR.psnr(imgs[k].cpu().numpy(), refs[k].cpu().numpy())
+    print(f'last pair: psnr {got[0]!r} vs {want!r}')
+    assert abs(got[0] - want) <= 1e-9 and got[1] == 0.0
+
+
 def test_existing_metrics_are_untouched(fr):
     from evreal_amd.prepost import Metrics
     pairs = [_pair(260, 346, s) for s in range(5)]

@@ -75,6 +75,28 @@ def test_mse_ssim_vs_oracle(shape):
     assert out[0, 0] == 0.0 and abs(out[0, 1] - 1.0) < 1e-6
 
 
+def test_mse_ssim_more_frames_than_one_grid_axis_holds():
+    """Frames ride the grid's z axis, chunked at 65535: 65537 pairs of 12 x 12 (the smallest frame SSIM accepts) against the
+    first and the last 100 computed alone, bit for bit, and the last pair against the oracle of test_mse_ssim_vs_oracle."""
+    from evreal_amd.prepost import Metrics
+    from oracle import metrics as om
+    n = 65537
+    g = torch.Generator(device='cuda').manual_seed(65537)
+    imgs = torch.rand((n, 12, 12), device='cuda', generator=g)
+    refs = torch.rand((n, 12, 12), device='cuda', generator=g)
+    m = Metrics()
+    bits = lambda t: np.ascontiguousarray(t.cpu().numpy()).view(np.uint64)
+    full = m(imgs, refs, mse=True, ssim=True)
+    for sl in (slice(0, 100), slice(n - 100, n)):
+        assert np.array_equal(bits(m(imgs[sl].contiguous(), refs[sl].contiguous(), mse=True, ssim=True)), bits(full[sl]))
+    k = n - 1
+    out = full[k].cpu().numpy()
+    a, b = om.clip01(imgs[k].cpu().numpy()), om.clip01(refs[k].cpu().numpy())
+    print(f'last pair: mse {out[0]!r} vs {om.mse(a, b)!r}, ssim {out[1]!r} vs {om.ssim(a, b)!r}')
+    assert abs(out[0] - om.mse(a, b)) <= 1e-12 + 1e-9 * om.mse(a, b)
+    assert abs(out[1] - om.ssim(a, b)) <= 2e-6, (out[1], om.ssim(a, b))
+
+
 @pytest.mark.parametrize('shape', [(260, 346), (180, 240), (96, 128)])
 def test_lpips_vs_oracle(shape):
     """LPIPS structure (AlexNet v0.1) with deterministic synthetic weights: HIP vs the torch restatement.

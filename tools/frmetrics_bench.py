@@ -1,28 +1,26 @@
 """Full-reference metric kernel timing: evr_fr_metrics (PSNR + MS-SSIM, fp64) beside evr_metrics (MSE + SSIM) on the same 512
-frame pairs of 346x260 in the same run -- device events around `--iters` calls of each after a warm-up; prints one JSON line
-(microseconds per call and per frame, the algorithmic bytes per frame of both, and their ratios).  Under
-`rocprofv3 --kernel-trace --stats` the same run gives the per-kernel table of profiles/frmetrics_kernel_stats.md.
+frame pairs of 346x260 in the same run -- device events around `--iters` calls of each after a warm-up, in a child process under
+a time limit (tools/metric_bench.py); prints one JSON line (microseconds per call and per frame, the algorithmic bytes per frame
+of both, and their ratios).  Under `rocprofv3 --kernel-trace --stats` a `--shape 260x346` run gives the per-kernel table of
+profiles/frmetrics_kernel_stats.md.
 With --evaluate it times evaluate() instead: a synthetic dataset with frames (8 sequences x 160 windows between frames, 346x260,
 synthetic E2VID weights) with -qm mse ssim and -qm mse ssim psnr ms_ssim, alternating, three times each.
 
     python tools/frmetrics_bench.py [--frames 512] [--iters 10]
     python tools/frmetrics_bench.py --evaluate
 """
-import argparse
 import contextlib
 import io
 import json
 import os
 import shutil
-import sys
 import tempfile
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import metric_bench as mb
 
 
 def level_sizes(H, W):
@@ -40,8 +38,9 @@ def algorithmic_bytes(H, W):
     return base, base + sum(2 * 2 * 8 * h * w for h, w in level_sizes(H, W)[1:])
 
 
-def kernels(n, iters, H=260, W=346):
+def run_shape(a, H, W):
     from evreal_amd.prepost import FullRefMetrics, Metrics
+    n = a.frames
     ref = torch.rand((n, H, W), device='cuda')
     img = (ref + 0.06 * torch.randn((n, H, W), device='cuda')).contiguous()
     old, new = Metrics(), FullRefMetrics()
@@ -49,22 +48,10 @@ def kernels(n, iters, H=260, W=346):
     runs = {'evr_metrics (mse + ssim)': lambda: old(img, ref),
             'evr_fr_metrics (psnr + ms_ssim)': lambda: new(img, ref, out=out),
             'evr_fr_metrics (psnr alone)': lambda: new(img, ref, ms_ssim=False, out=out)}
-    res = {}
-    for name, fn in runs.items():
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) / iters * 1e3
-        res[name] = dict(us_per_call=round(us, 1), us_per_frame=round(us / n, 3))
+    best, res = mb.entries(mb.alternate(runs, a.iters, 1, warmup=3), n, repeats=False, digits=3)
     b_old, b_new = algorithmic_bytes(H, W)
     t_old, t_new = res['evr_metrics (mse + ssim)']['us_per_call'], res['evr_fr_metrics (psnr + ms_ssim)']['us_per_call']
-    return dict(size=f'{W}x{H}', frames=n, iters=iters, runs=res, bytes_per_frame=dict(evr_metrics=b_old, evr_fr_metrics=b_new),
+    return dict(size=f'{W}x{H}', frames=n, iters=a.iters, runs=res, bytes_per_frame=dict(evr_metrics=b_old, evr_fr_metrics=b_new),
                 bytes_ratio=round(b_new / b_old, 3), time_ratio=round(t_new / t_old, 3),
                 finite=int(torch.isfinite(out).all()))
 
@@ -118,12 +105,13 @@ def evaluate_rates(reps=3):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--frames', type=int, default=512)
-    ap.add_argument('--iters', type=int, default=10)
+    ap = mb.parser(frames=512, iters=10)
     ap.add_argument('--evaluate', action='store_true', help='time evaluate() with and without psnr / ms_ssim')
     a = ap.parse_args()
-    print(json.dumps(evaluate_rates() if a.evaluate else kernels(a.frames, a.iters)))
+    if a.evaluate:
+        print(json.dumps(evaluate_rates()))
+    else:
+        mb.run(__file__, a, run_shape, lambda res: res['346x260'], shapes=((260, 346),))
 
 
 if __name__ == '__main__':
