@@ -163,6 +163,92 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsig
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Tile idioms shared by the kernels below: ONE definition each.  They are inlined, and an edit to any of them has to leave the device
+// assembly of every kernel as it was (tools/same_isa.py <rev>, all three arithmetic objects) -- or be meant to change it.  hipcc
+// simplifies a helper on its own before it inlines it, so moving code behind one can reorder a kernel's arithmetic: where that happened
+// the kernel keeps its own copy, with a comment that says so.
+
+// XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8): every XCD (private L2) walks a contiguous range of tiles
+// (the block comes before the grid size on purpose: with (total, bid) hipcc commutes one add of the map in every kernel)
+__host__ __device__ __forceinline__ constexpr int xcd_map(int bid, int total) {
+    const int q = total >> 3, r = total & 7, xcd = bid & 7, idx = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+constexpr bool xcd_map_permutes(int total) {      // blocks 0..total-1 land on 0..total-1, each once
+    bool seen[64] = {};
+    for (int bid = 0; bid < total; ++bid) {
+        const int lin = xcd_map(bid, total);
+        if (lin < 0 || lin >= total || seen[lin]) return false;
+        seen[lin] = true;
+    }
+    return true;
+}
+constexpr bool xcd_map_check() { for (int total = 1; total <= 64; ++total) if (!xcd_map_permutes(total)) return false; return true; }
+static_assert(xcd_map_check(), "the XCD remap is no permutation of the grid for some size in 1..64 (every total % 8, and total < 8)");
+__device__ __forceinline__ int xcd_remap() { return xcd_map(blockIdx.x, gridDim.x); }
+
+// validity of the 9 neighbours of pixel m of the n x H x W grid (bit t = tap (t/3 - 1, t%3 - 1)); no bits past the end of M.
+// A pixel that is not a real neighbour (image border, neighbouring image of the batch) reads a zero row in the kernels
+__device__ __forceinline__ unsigned neighbours9(const ConvArgs& a, int m, int M, int hw, int H, int W) {
+    unsigned vm = 0;
+    if (m < M) {
+        const int img = fdiv(m, a.div_hw_mul, a.div_hw_sh), rem = m - img * hw;   // (W == a.wm: stride 1 on the input's grid)
+        const int py = fdiv(rem, a.div_w_mul, a.div_w_sh), px = rem - py * W;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
+            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) vm |= 1u << t;
+        }
+    }
+    return vm;
+}
+
+// accumulator sets f32x16[NB]: zero, and their image in memory -- one float4 per (block nb, quad q) at p[(nb * 4 + q) * 64], the 64 lanes
+// of a wave side by side (p already points at the lane's own slot): the split-K workspace.  (The loops that read this image back -- the
+// split-K sum, the LDS park of the twin kernels -- stay spelled out in their kernels: behind a helper those kernels come out changed.)
+template <int NB> __device__ __forceinline__ void acc_zero(f32x16 (&acc)[NB]) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
+}
+template <int NB> __device__ __forceinline__ void acc_store(float4* p, const f32x16 (&acc)[NB]) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) p[(nb * 4 + q) * 64] = make_float4(acc[nb][4 * q], acc[nb][4 * q + 1], acc[nb][4 * q + 2], acc[nb][4 * q + 3]);
+}
+// split-K workspace: partial accumulators in register order, [tile][run][wave][block * 4 + quad][lane] x 16 B -- the float4 index of
+// the lane's first slot (written by conv3x3_band_kernel / conv_band_prog_kernel, summed by the conv_ksplit_epi* kernels)
+template <int WM, int NB> __device__ __forceinline__ size_t ksplit_slot(int tile, int ksplit, int run, int wave, int lane) {
+    return ((((size_t)tile * ksplit + run) * WM + wave) * (NB * 4)) * 64 + lane;
+}
+
+// Counted wait + BARE s_barrier: __syncthreads() carries a fence that hipcc lowers to vmcnt(0), which would drain the weight ring and
+// the band in flight.  vmcnt(N): all but this wave's N newest requests have landed (loads complete in order); lgkmcnt(0): its fragment
+// reads have left LDS before anyone overwrites the buffers.  LDS-DMA completion is never left to hipcc's own waitcnt insertion.
+template <int N> __device__ __forceinline__ void wait_barrier() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(N) : "memory"); }
+template <int N> __device__ __forceinline__ void wait_vm_barrier() { asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(N) : "memory"); }      // (no LDS reads pending)
+__device__ __forceinline__ void wait_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
+template <int N> __device__ __forceinline__ void wait_vm_lds() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(N) : "memory"); }
+
+// The step program of the programmed band kernels (entry layout: conv.h, above BAND_PROG_MAX; written by model.cpp prep_s2d): the whole
+// program sits in two VGPRs (lane l: entries l and 64 + l) and is read back with v_readlane
+struct StepProg {
+    unsigned prog_lo, prog_hi;
+    __device__ __forceinline__ StepProg(const unsigned* prog, int lane) : prog_lo(prog[lane]), prog_hi(prog[64 + lane]) {}
+    __device__ __forceinline__ unsigned entry(int s) const {
+        return s < 64 ? (unsigned)__builtin_amdgcn_readlane((int)prog_lo, s) : (unsigned)__builtin_amdgcn_readlane((int)prog_hi, s - 64);
+    }
+    // float offset of a step's weight tile in a row of the weight matrix (nch2 K chunks per tap)
+    static __device__ __forceinline__ int kofs(unsigned e, int nch2) { return (int)(((e & 15u) * (unsigned)nch2 + ((e >> 8) & 255u)) * 32u); }
+    // the band an entry asks for: source chunk (py | px << 1 | channel chunk << 2) and dy
+    static __device__ __forceinline__ int band_src(unsigned e) { return (int)((e >> 16) & 1023u); }
+    static __device__ __forceinline__ int band_dy(unsigned e) { return (int)((e >> 26) & 3u) - 1; }
+};
+
+// ---------------------------------------------------------------------------------------------------
 // Epilogue shared by the convolution kernels.
 //
 // Accumulator layout (the MFMAs run with the WEIGHT fragment as the A operand, so acc holds C^T): lane & 31 = pixel
@@ -578,13 +664,7 @@ __global__ __launch_bounds__(64 * WM, (X3 == 0) ? ((WM == 4 && !LSTM) ? 2 : 1) :
     const int M = a.n * hw;
     const int ntiles = a.cout / (32 * NB);
 
-    // XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8)
-    int lin;
-    {
-        const int total = gridDim.x, bid = blockIdx.x;
-        const int q = total >> 3, r = total & 7, xcd = bid & 7, idx = bid >> 3;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int lin = xcd_remap();
     const int ntile = lin % ntiles;
     const int mtile = lin / ntiles;
     const ConvTaps& tp = a.tp;
@@ -713,7 +793,7 @@ __global__ __launch_bounds__(64 * WM, (X3 == 0) ? ((WM == 4 && !LSTM) ? 2 : 1) :
         const int buf = s & 1;
         // LDS-DMA completion is NOT left to hipcc's automatic waitcnt insertion: with every fragment read bit-cast
         // to bf16 (PACKED mode) it no longer sees the reads alias the DMA writes and emits no vmcnt wait at all
-        if constexpr (!REGSTAGE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (!REGSTAGE) wait_vm<0>();
         if (!(ablate & 1)) __syncthreads();    // tile s is in LDS for every wave; everyone left tile s-1
         if (s + 1 < nsteps && !(ablate & 2)) issue(buf ^ 1);   // next tile: LDS-DMA, or plain loads into registers
         int groups_now = 0;
@@ -811,12 +891,7 @@ __global__ __launch_bounds__(64 * WM, 2) void conv3x3_band_kernel(const ConvArgs
     const int hw = H * W;
     const int M = a.n * hw;
     const int ntiles = a.cout / (32 * NB);
-    int lin;
-    {   // XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8)
-        const int total = gridDim.x, bid = blockIdx.x;
-        const int q = total >> 3, rr = total & 7, xcd = bid & 7, idx = bid >> 3;
-        lin = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-    }
+    int lin = xcd_remap();
     // split K (round 4, launches with fewer tiles than resident slots: small batches, the deep layers): ksplit consecutive blocks share
     // a tile and each takes a run of the input-channel chunks; partial accumulators go to `kws`, conv_ksplit_epilogue_kernel sums them
     // in a fixed order and runs the epilogue
@@ -900,12 +975,7 @@ __global__ __launch_bounds__(64 * WM, 2) void conv3x3_band_kernel(const ConvArgs
     // (only the ConvLSTM cell state -- 16 registers -- is requested a main loop early; the 64 registers of a residual /
     // skip operand are loaded in the epilogue: the split fragments of a step already take 80)
     epi_setup<NB, LSTM, GROUPED>(a, m0 + idx - SHIFT, M, hw, n0, h, acc, pre, ec, lane_ok, LSTM);
-    if (KSPLIT && ks_i > 0) {      // the bias belongs to the first run only
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
-    }
+    if (KSPLIT && ks_i > 0) acc_zero(acc);      // the bias belongs to the first run only
 
     // ConvTranspose2d(k5, s2) as a 3x3 conv whose N is phase-major (model.cpp prep_tconv): a (tap, phase) pair the
     // transposed kernel does not connect has a zero weight block.  tap_use[t] = phases of THIS N tile that use tap t:
@@ -919,8 +989,7 @@ __global__ __launch_bounds__(64 * WM, 2) void conv3x3_band_kernel(const ConvArgs
     auto tap_use = [&](int t) -> int { return GROUPED ? (a.tp.tap_groups[t] & tile_groups) : 1; };
     auto band_use = [&](int dyi) -> bool { return !GROUPED || (tap_use(3 * dyi) | tap_use(3 * dyi + 1) | tap_use(3 * dyi + 2)) != 0; };
 
-    // validity of the 9 neighbours of this lane's pixel (bit t = tap (t/3 - 1, t%3 - 1))
-    unsigned vmask = 0;
+    unsigned vmask = 0;      // (neighbours9, kept here: through the shared helper the transposed-conv instantiations come out with other code)
     {
         const int m = m0 + idx - SHIFT;
         if (lane_ok && m < M) {
@@ -942,16 +1011,15 @@ __global__ __launch_bounds__(64 * WM, 2) void conv3x3_band_kernel(const ConvArgs
     constexpr int ablate = 0;
 #endif
     const int mx_sa = a.mx_sa, mx_sb = a.mx_sb;
-    // prologue: the zero row, band 0 and the first RING-1 weight tiles
-    // (bare s_barrier below: __syncthreads() carries a fence that hipcc lowers to vmcnt(0), which would drain the ring)
+    // prologue: the zero row, band 0 and the first RING-1 weight tiles (wait_barrier: a bare s_barrier, the ring is not drained)
     if (tid < SP) lds[ZOFF + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
     issue_band(cbeg, 0, 0, band_use(0));
     issue_w(0, cbeg, 0, tap_use(0) != 0);
     if constexpr (RING == 3) {
         issue_w(1, cbeg, 1, tap_use(1) != 0);
-        if constexpr (NBW == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        wait_barrier<NBW == 2 ? 2 : 4>();
     } else {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        wait_barrier<0>();
     }
 
     for (int c = cbeg; c < cend; ++c) {
@@ -1003,28 +1071,22 @@ __global__ __launch_bounds__(64 * WM, 2) void conv3x3_band_kernel(const ConvArgs
             if (ablate & 1) continue;
             if constexpr (RING == 3) {
                 if (t % 3 == 2) {
-                    if constexpr (NBW == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                    else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                    wait_barrier<NBW == 2 ? 2 : 4>();
                 } else {
                     static_assert(RING != 3 || NBW + NA_MIN == 6 || NBW + NA_MIN == 8, "update the counted waits");
-                    if constexpr (NBW + NA_MIN == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                    else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                    wait_barrier<NBW + NA_MIN == 6 ? 6 : 8>();
                 }
             } else {
                 // 2-slot ring: the tile requested first in THIS step is needed next; only band pieces may stay in flight
                 static_assert(NA_MIN == 4, "update the counted waits");
-                if (t % 3 == 0) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                if (t % 3 == 0) wait_barrier<4>();
+                else wait_barrier<0>();
             }
         }
     }
     if (ablate & 4) return;
-    if constexpr (KSPLIT) {      // partial accumulators, register order: [tile][run][wave][block * 4 + quad][lane] x 16 B
-        float4* o = (float4*)kws + ((((size_t)lin * ksplit + ks_i) * WM + wmi) * (NB * 4)) * 64 + lane;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[(nb * 4 + q) * 64] = make_float4(acc[nb][4 * q], acc[nb][4 * q + 1], acc[nb][4 * q + 2], acc[nb][4 * q + 3]);
+    if constexpr (KSPLIT) {      // partial accumulators for the conv_ksplit_epi* kernels
+        acc_store((float4*)kws + ksplit_slot<WM, NB>(lin, ksplit, ks_i, wmi, lane), acc);
     } else {
         if constexpr (!LSTM) epi_prefetch<NB, LSTM, GROUPED>(a, n0, h, pre, ec);
         epi_finish<NB, LSTM, GROUPED, true>(a, ec, n0, h, acc, pre, img_out);
@@ -1052,6 +1114,7 @@ __global__ __launch_bounds__(256, 2) void conv_ksplit_epilogue_kernel(const Conv
     f32x16 pre[PN];
     EpiCtx ec;
     epi_setup<NB, LSTM, GROUPED>(a, m0 + wmi * 32 + r, M, hw, n0, h, dummy, pre, ec, true, LSTM);      // (the bias sits in run 0's partials)
+    // (zero, workspace address -- ksplit_slot's layout -- and sum spelled out: behind acc_zero, ksplit_slot or a helper for the sum, any one of them, this kernel changes)
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -1090,9 +1153,9 @@ __global__ __launch_bounds__(256, (KSMAX > 4) ? 1 : 2) void conv_ksplit_epi4_ker
     const int ntile = lin % ntiles, mtile = lin / ntiles;
     const int m0 = mtile * TM, n0 = ntile * 128;
     const int r = lane & 31, h = lane >> 5;
-    // partial accumulators: [tile][run][wave][block * 4 + quad][lane] x 16 B (conv3x3_band_kernel / conv_band_prog_kernel)
-    const size_t run_stride = (size_t)WM * 16 * 64;
-    const float4* base = (const float4*)kws + (((size_t)lin * ksplit) * WM + wmi) * 16 * 64 + lane;
+    // the partial accumulators of run 0 (ksplit_slot), and the distance from one run to the next
+    const size_t run_stride = ksplit_slot<WM, 4>(0, ksplit, 1, 0, 0);
+    const float4* base = (const float4*)kws + ksplit_slot<WM, 4>(lin, ksplit, 0, wmi, lane);
     float4 v[KSMAX][4];
     if constexpr (LSTM) {
         const int q = wv;
@@ -1191,12 +1254,7 @@ __global__ __launch_bounds__(256, (NB == 4) ? 2 : 3) void conv_bandk_kernel(cons
     const int hw = H * W;
     const int M = a.n * hw;
     const int ntiles = a.cout / (32 * NB);
-    int lin;
-    {   // XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8)
-        const int total = gridDim.x, bid = blockIdx.x;
-        const int q = total >> 3, rr = total & 7, xcd = bid & 7, idx = bid >> 3;
-        lin = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-    }
+    const int lin = xcd_remap();
     const int ntile = lin % ntiles, mtile = lin / ntiles;
     const int m0 = mtile * TM, n0 = ntile * 32 * NB;       // band row 0 = source pixel m0 - 2 (+ dy*W)
     const int c0 = a.c0, c1 = a.c1;
@@ -1258,8 +1316,8 @@ __global__ __launch_bounds__(256, (NB == 4) ? 2 : 3) void conv_bandk_kernel(cons
     const int idx = wmi * 32 + r;                          // lane's row of the tile; its output pixel is m0 + idx
     epi_setup<NB, false, false>(a, m0 + idx, M, hw, n0, h, acc, pre, ec, true, false);   // operands are loaded in the epilogue
 
-    unsigned vmask = 0;      // validity of the KW x KW neighbours of this lane's pixel (bit t = tap (t/KW - HALO, t%KW - HALO))
-    {
+    unsigned vmask = 0;      // validity of the KW x KW neighbours of this lane's pixel (bit t = tap (t/KW - HALO, t%KW - HALO)): neighbours9 for KW taps
+    {                        // (kept here: as a shared helper templated on KW the KW = 5 kernels come out with other code)
         const int m = m0 + idx;
         if (m < M) {
             const int img = fdiv(m, a.div_hw_mul, a.div_hw_sh), rem = m - img * hw;
@@ -1275,7 +1333,7 @@ __global__ __launch_bounds__(256, (NB == 4) ? 2 : 3) void conv_bandk_kernel(cons
     if (tid < SP) lds[ZOFF + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
     issue_band(0, 0, 0);
     issue_w(0, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    wait_barrier<0>();
 
     for (int c = 0; c < nchunks; ++c) {
         const int pa = c & 1;        // bands per chunk and taps per chunk are both odd: band parity (c + dy) & 1, ring slot (c + t) & 1
@@ -1306,8 +1364,8 @@ __global__ __launch_bounds__(256, (NB == 4) ? 2 : 3) void conv_bandk_kernel(cons
                 acc[nb] = mma_split(acc[nb], wb, xa, mx_sb, mx_sa);
             }
             // the tile requested first in THIS step is needed next; only the band pieces requested after it may stay in flight
-            if (t % KW == 0) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (t % KW == 0) wait_barrier<4>();
+            else wait_barrier<0>();
         }
     }
     epi_prefetch<NB, false, false>(a, n0, h, pre, ec);
@@ -1428,7 +1486,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_kernel(const ConvArgs* __r
         epi_setup<NB, false, false>(a, m0 + idx, M, hw, n0, hh, acc, pre, ec, true, false);      // (its bias loads are dead: replaced below)
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) acc[nb] = bias0[nb];
-        unsigned vmask = 0;
+        unsigned vmask = 0;      // (neighbours9, kept here: through the shared helper hipcc orders this kernel's index arithmetic differently)
         {
             const int m = m0 + idx;
             if (m < M) {
@@ -1446,9 +1504,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_kernel(const ConvArgs* __r
             // else in flight -- the previous tile's stores -- only makes the wait conservative); the barrier publishes every wave's
             // pieces and tells that everyone has left the band multiplied before this one, whose slot the next request reuses
             // (the stream's tail, where fewer than DIST bands are ahead: wait for everything)
-            if (DIST == 1 || ahead < DIST) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            else if (npw == 3) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (DIST == 1 || ahead < DIST) wait_barrier<0>();
+            else if (npw == 3) wait_barrier<6>();
+            else wait_barrier<4>();
             static_assert(DIST == 1 || DIST == 3, "update the counted waits: (DIST - 1) bands of 3 | 2 requests");
             --ahead;
             // the epilogue's operands are requested BEFORE the last band's look-ahead request, so that waiting for them later does
@@ -1586,7 +1644,7 @@ __global__ __launch_bounds__(256 * RPB, (RPB == 1 ? 3 : 2)) void conv3x3_c16_row
         const int x0 = strip * TM, y0 = seg * rseg;
         const int y1 = (y0 + rseg < H) ? y0 + rseg : H;
         // (everyone has left the previous item's last rows -- and, the first time, the weights and the bias are in place)
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        wait_barrier<0>();
         issue_rows(img, y0 - 1, RPB + 2, 0, x0, y1);      // rows y0-1 .. y0+RPB: the first step's
         int slot_m1 = 0;                                  // ring slot of row ys - 1
         const int x = x0 + idx;
@@ -1604,9 +1662,9 @@ __global__ __launch_bounds__(256 * RPB, (RPB == 1 ? 3 : 2)) void conv3x3_c16_row
             else epi_prefetch<NB, false, false>(a, n0, hh, pre, ec);
         };
         setup_step(y0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         for (int ys = y0; ys < y1; ys += RPB) {
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            wait_lds_barrier();
             {   // the next step's new rows ys+RPB+1 .. ys+2 RPB into the slots of the rows the previous step has left
                 int slot = slot_m1 + RPB + 2;
                 if (slot >= NBUF) slot -= NBUF;
@@ -1655,7 +1713,7 @@ __global__ __launch_bounds__(256 * RPB, (RPB == 1 ? 3 : 2)) void conv3x3_c16_row
                 }
             }
             // the next step's rows (requested a whole multiply phase ago), this step's operands and the previous step's stores
-            if (!(ablate & 8)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (!(ablate & 8)) wait_vm<0>();
             if (!(ablate & 4)) {
                 epi_finish<NB, false, false, true, NB == 1>(a, ec, n0, hh, acc, pre, img_out);
                 if (ys + RPB < y1) setup_step(ys + RPB);
@@ -1710,12 +1768,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide_kernel(const ConvArg
     const int hw = H * W;
     const int M = a.n * hw;
     const int ntiles = a.cout / TN;
-    int lin;
-    {   // XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8)
-        const int total = gridDim.x, bid = blockIdx.x;
-        const int q = total >> 3, rr = total & 7, xcd = bid & 7, idx = bid >> 3;
-        lin = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-    }
+    const int lin = xcd_remap();
     const int ntile = lin % ntiles, mtile = lin / ntiles;
     const int m0 = mtile * TM, n0 = ntile * TN;            // band row 0 = source pixel m0 - 1 (+ dy*W)
     const int n0w = n0 + wni * 32 * NB;                    // this wave's 128 columns
@@ -1784,20 +1837,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide_kernel(const ConvArg
         for (int nb = 0; nb < NB; ++nb) tile_groups |= 1 << col_group(a.tp, n0w + nb * 32);
     }
     auto tap_use = [&](int t) -> int { return GROUPED ? (a.tp.tap_groups[t] & tile_groups) : 1; };
-    auto neighbours = [&](int m) -> unsigned {   // validity of the pixel's 9 neighbours (bit t = tap (t/3 - 1, t%3 - 1))
-        unsigned vm = 0;
-        if (m < M) {
-            const int img = fdiv(m, a.div_hw_mul, a.div_hw_sh), rem = m - img * hw;   // (W == a.wm: stride 1 on the input's grid)
-            const int py = fdiv(rem, a.div_w_mul, a.div_w_sh), px = rem - py * W;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) vm |= 1u << t;
-            }
-        }
-        return vm;
-    };
-    const unsigned vmask0 = neighbours(mA), vmask1 = neighbours(mB);
+    const unsigned vmask0 = neighbours9(a, mA, M, hw, H, W), vmask1 = neighbours9(a, mB, M, hw, H, W);
     const int mx_sa = a.mx_sa, mx_sb = a.mx_sb;
     // timing ablation (results are garbage when non-zero), COMPILE-TIME only (-DEVR_WIDE_ABLATE=mask, tools/ablate_wide.sh: a run-time
     // mask costs this kernel registers it does not have): bit 0 no waits / barriers in the loop, bit 1 no LDS-DMA requests in the
@@ -1808,11 +1848,11 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide_kernel(const ConvArg
     constexpr int ablate = 0;
 #endif
 
-    // prologue: band 0 and the first weight tile (bare s_barrier: __syncthreads() carries a fence hipcc lowers to vmcnt(0))
+    // prologue: band 0 and the first weight tile
     if (tid < SP) lds[NBUF * A_F4 + 2 * B_F4 + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
     issue_band(0, 0, 0);
     issue_w(0, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    wait_barrier<0>();
 
     for (int c = 0; c < nchunks; ++c) {
         const int pa = c & 1;        // parity of band index 3c + t/3 is (c + t/3) & 1; ring slot of step 9c + t is (c + t) & 1
@@ -1861,14 +1901,14 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide_kernel(const ConvArg
             // overwrites the buffers
             if (ablate & 1) continue;
             if constexpr (SINGLE) {
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                wait_barrier<0>();
                 if (t % 3 == 2 && !(t == 8 && c == nchunks - 1)) {   // everyone has left the band: fetch the next one into the same buffer
                     if (!(ablate & 2)) issue_band(cb, d2, 0);
-                    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                    wait_vm_barrier<0>();
                 }
             } else {
-                if (t % 3 == 0) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                if (t % 3 == 0) wait_barrier<4>();
+                else wait_barrier<0>();
             }
         }
     }
@@ -1946,6 +1986,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide_kernel(const ConvArg
         // (round 4: the operands of a pixel block's FOUR column blocks are requested together -- two exposed load latencies per tile
         // instead of eight: the timing ablation put 100 of dec1's 590 us on these loads.  Not in the fp6 build: its group conversion
         // needs the registers, hipcc spilled 5 of them.)
+        // (spelled out here and in conv_band_prog_wide_kernel, loops included: as one shared function, or with the acc_* helpers, both kernels change)
         float4* park = &lds[wv * 1024];        // 16 KB per wave
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
@@ -2148,10 +2189,8 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
         if (mt >= tm.count[xcd]) return;                       // (a place past the range's last tile: the whole block leaves)
         rows4 = mt < nf;
         m0 = tm.pix0[xcd] + (rows4 ? mt * TM : nf * TM + (mt - nf) * (TM - 64));
-    } else {   // XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8)
-        const int total = gridDim.x, bid = blockIdx.x;
-        const int q = total >> 3, rr = total & 7, xcd = bid & 7, idx = bid >> 3;
-        const int lin = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
+    } else {
+        const int lin = xcd_remap();
         ntile = lin % ntiles;
         m0 = (lin / ntiles) * TM;
     }
@@ -2221,19 +2260,9 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
         accA[f] = b4; accB[f] = b4; accC[f] = b4; accD[f] = b4;
     }
     const int mP = m0 + wmi * wstride + p;                     // the lane's pixel of block 0; block b: + 16b
-    auto neighbours = [&](int m) -> unsigned {   // validity of the pixel's 9 neighbours (bit t = tap (t/3 - 1, t%3 - 1))
-        unsigned vm = 0;
-        if constexpr (EPI_ABLATE & 1024) return 0x1ffu;
-        if (m < M) {
-            const int img = fdiv(m, a.div_hw_mul, a.div_hw_sh), rem = m - img * hw;
-            const int py = fdiv(rem, a.div_w_mul, a.div_w_sh), px = rem - py * W;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-                if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) vm |= 1u << t;
-            }
-        }
-        return vm;
+    auto neighbours = [&](int m) -> unsigned {
+        if constexpr (EPI_ABLATE & 1024) return 0x1ffu;      // (timing ablation: no neighbour decodes)
+        else return neighbours9(a, m, M, hw, H, W);
     };
     const unsigned vmA = neighbours(mP), vmB = neighbours(mP + 16), vmC = neighbours(mP + 32), vmD = haveD ? neighbours(mP + 48) : 0u;
 
@@ -2242,7 +2271,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
         issue_band(0, 0, 0);
         issue_w(0, 0, 0);
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    wait_barrier<0>();
 
     if constexpr (ALT) {
         // the skewed loop: alt16 above.  Per accumulator the same MFMAs in the same order as the loop below
@@ -2285,7 +2314,7 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
                 if constexpr (FULL) { xhD = ld(&lds[iD * SP + (hs ^ xs)]); xlD = ld(&lds[iD * SP + ((hs | 2) ^ xs)]); }
                 f16x8 wh = ld(lb + wq_h), wl = ld(lb + wq_l);
                 // the fragments are in registers before the barrier: the band may be replaced from the next segment on
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                wait_lds_barrier();
                 __builtin_amdgcn_sched_barrier(0);
                 // ---- MMA
 #pragma unroll
@@ -2299,8 +2328,8 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
                     __builtin_amdgcn_sched_barrier(0);
                     wh = whn; wl = wln;
                 }
-                if (alt16::vm_after_mma(t) == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                if (alt16::vm_after_mma(t) == 4) wait_vm_lds<4>();
+                else wait_vm_lds<0>();
                 if (alt16::barrier_after_mma(late ? 1 : 0, 9 * c + t, 9 * nchunks)) asm volatile("s_barrier" ::: "memory");
             }
         }
@@ -2350,14 +2379,14 @@ __global__ __launch_bounds__(256 * WN, 2) void conv3x3_wide16_kernel(const ConvA
                 wh = whn; wl = wln;
             }
             if constexpr (SINGLE) {
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                wait_barrier<0>();
                 if (t % 3 == 2 && !(t == 8 && c == nchunks - 1)) {
                     issue_band(cb, d2, 0);
-                    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                    wait_vm_barrier<0>();
                 }
             } else {
-                if (t % 3 == 0) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                if (t % 3 == 0) wait_barrier<4>();
+                else wait_barrier<0>();
             }
         }
     }
@@ -2462,12 +2491,7 @@ __global__ __launch_bounds__(256, 2) void conv_band_prog_kernel(const ConvArgs* 
     const int M = a.n * hw;
     const int nrows = a.n * Hb;
     const int ntiles = a.cout / (32 * NB);
-    int lin;
-    {   // XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8)
-        const int total = gridDim.x, bid = blockIdx.x;
-        const int q = total >> 3, rr = total & 7, xcd = bid & 7, idx = bid >> 3;
-        lin = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-    }
+    int lin = xcd_remap();
     // (split K as in conv3x3_band_kernel: ksplit consecutive blocks share a tile, each walks a run of whole BANDS of the step program)
     const int ksplit = KSPLIT ? ksplit_arg : 1;
     const int ks_i = KSPLIT ? lin % ksplit : 0;
@@ -2480,11 +2504,7 @@ __global__ __launch_bounds__(256, 2) void conv_band_prog_kernel(const ConvArgs* 
     const unsigned row_pitch = 2u * (unsigned)a.win * (unsigned)C, pix_pitch = 2u * (unsigned)C;   // floats
     const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(a.in0, (unsigned)a.n * a.hin * a.win * (unsigned)C * 4u);
     const __amdgpu_buffer_rsrc_t rsw = make_rsrc(a.wgt2, (unsigned)a.cout * ktot * 4u);
-    // the whole step program in two VGPRs (lane l: entries l and 64 + l), read back with v_readlane
-    const unsigned prog_lo = a.prog[lane], prog_hi = a.prog[64 + lane];
-    auto entry = [&](int s) -> unsigned {
-        return s < 64 ? (unsigned)__builtin_amdgcn_readlane((int)prog_lo, s) : (unsigned)__builtin_amdgcn_readlane((int)prog_hi, s - 64);
-    };
+    const StepProg prog(a.prog, lane);
 
     // per-lane constants of the DMA pieces this wave issues: block (row, x) of band row 8j + lane/8 for dy = 0
     int a_rho[NA_MAX]; unsigned a_xq[NA_MAX];
@@ -2534,58 +2554,40 @@ __global__ __launch_bounds__(256, 2) void conv_band_prog_kernel(const ConvArgs* 
     f32x16 pre[NB];
     EpiCtx ec;
     epi_setup<NB, false, false>(a, m0 + idx, M, hw, n0, h, acc, pre, ec, true, false);   // operands are loaded in the epilogue
-    if (KSPLIT && ks_i > 0) {      // the bias belongs to the first run only
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
-    }
+    if (KSPLIT && ks_i > 0) acc_zero(acc);      // the bias belongs to the first run only
 
-    unsigned vmask = 0;      // validity of the 9 neighbour blocks of this lane's output pixel
-    {
-        const int m = m0 + idx;
-        if (m < M) {
-            const int img = fdiv(m, a.div_hw_mul, a.div_hw_sh), rem = m - img * hw;
-            const int py = fdiv(rem, a.div_w_mul, a.div_w_sh), px = rem - py * Wb;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-                if ((unsigned)yy < (unsigned)Hb && (unsigned)xx < (unsigned)Wb) vmask |= 1u << t;
-            }
-        }
-    }
+    const unsigned vmask = neighbours9(a, m0 + idx, M, hw, Hb, Wb);      // validity of the 9 neighbour blocks of this lane's output pixel
 
     const int nsteps_all = a.prog_steps;
     const int mx_sa = a.mx_sa, mx_sb = a.mx_sb;
-    auto kofs_of = [&](unsigned e) -> int { return (int)(((e & 15u) * (unsigned)nch2 + ((e >> 8) & 255u)) * 32u); };
     // this block's steps [s_first, nsteps]: everything, or (KSPLIT) the run from the first band start at or after its share's
     // beginning up to the step before the next run's
     int s_first = 1, nsteps = nsteps_all;
     if constexpr (KSPLIT) {
-        auto band_start = [&](int s) { while (s <= nsteps_all && !(entry(s) & 16u)) ++s; return s; };
+        auto band_start = [&](int s) { while (s <= nsteps_all && !(prog.entry(s) & 16u)) ++s; return s; };
         s_first = band_start(1 + (ks_i * nsteps_all) / ksplit);
         nsteps = (ks_i + 1 == ksplit) ? nsteps_all : band_start(1 + ((ks_i + 1) * nsteps_all) / ksplit) - 1;
     }
     {
-        const unsigned e1 = entry(s_first);
+        const unsigned e1 = prog.entry(s_first);
         if (tid < SP) lds[ZOFF + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (s_first == 1) {
-            const unsigned e0 = entry(0);
-            issue_band((int)((e0 >> 16) & 1023u), (int)((e0 >> 26) & 3u) - 1, 0);
+            const unsigned e0 = prog.entry(0);
+            issue_band(StepProg::band_src(e0), StepProg::band_dy(e0), 0);
         } else {      // the run's first band, decoded from its own first step: K chunk cc = phase * (C / 32) + channel chunk, dy from the tap
             const int cc = (int)((e1 >> 8) & 255u), nch = C / 32, phase = cc / nch;
             issue_band((phase >> 1) | ((phase & 1) << 1) | ((cc - phase * nch) << 2), (int)(e1 & 15u) / 3 - 1, 0);
         }
-        issue_w(kofs_of(e1), 0);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        issue_w(StepProg::kofs(e1, nch2), 0);
+        wait_barrier<0>();
     }
     int abuf = 0;
     for (int s = s_first; s <= nsteps; ++s) {
-        const unsigned e = entry(s);
+        const unsigned e = prog.entry(s);
         const int slot = (s - s_first) & 1;
-        if (s < nsteps) issue_w(kofs_of(entry(s + 1)), slot ^ 1);
+        if (s < nsteps) issue_w(StepProg::kofs(prog.entry(s + 1), nch2), slot ^ 1);
         if ((e & 16u) && s > s_first) abuf ^= 1;
-        if (e & 32u) issue_band((int)((e >> 16) & 1023u), (int)((e >> 26) & 3u) - 1, abuf ^ 1);
+        if (e & 32u) issue_band(StepProg::band_src(e), StepProg::band_dy(e), abuf ^ 1);
         const int t = (int)(e & 15u);
         const int dxi = t - (t / 3) * 3;
         const int i = idx + dxi;
@@ -2601,15 +2603,11 @@ __global__ __launch_bounds__(256, 2) void conv_band_prog_kernel(const ConvArgs* 
         }
         // the next step's weight tile was requested first in this step: it must have landed; a band requested after it
         // may stay in flight only if this band has further steps (bit 6)
-        if (e & 64u) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (e & 64u) wait_barrier<4>();
+        else wait_barrier<0>();
     }
-    if constexpr (KSPLIT) {      // partial accumulators for conv_ksplit_epilogue_kernel (NB == 4)
-        float4* o = (float4*)kws + ((((size_t)lin * ksplit + ks_i) * WM + wmi) * (NB * 4)) * 64 + lane;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[(nb * 4 + q) * 64] = make_float4(acc[nb][4 * q], acc[nb][4 * q + 1], acc[nb][4 * q + 2], acc[nb][4 * q + 3]);
+    if constexpr (KSPLIT) {      // partial accumulators for the conv_ksplit_epi* kernels (NB == 4)
+        acc_store((float4*)kws + ksplit_slot<WM, NB>(lin, ksplit, ks_i, wmi, lane), acc);
     } else {
         epi_prefetch<NB, false, false>(a, n0, h, pre, ec);
         epi_finish<NB, false, false, true>(a, ec, n0, h, acc, pre, img_out);
@@ -2646,12 +2644,7 @@ __global__ __launch_bounds__(256, 2) void conv_band_prog_wide_kernel(const ConvA
     const int M = a.n * hw;
     const int nrows = a.n * Hb;
     const int ntiles = a.cout / (32 * NB);
-    int lin;
-    {   // XCD-aware bijective remap of the 1-D grid (block b runs on XCD b % 8)
-        const int total = gridDim.x, bid = blockIdx.x;
-        const int q = total >> 3, rr = total & 7, xcd = bid & 7, idx = bid >> 3;
-        lin = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-    }
+    const int lin = xcd_remap();
     const int ntile = lin % ntiles, mtile = lin / ntiles;
     const int m0 = mtile * TM, n0 = ntile * 32 * NB;
     const int C = a.c0;
@@ -2660,10 +2653,7 @@ __global__ __launch_bounds__(256, 2) void conv_band_prog_wide_kernel(const ConvA
     const unsigned row_pitch = 2u * (unsigned)a.win * (unsigned)C, pix_pitch = 2u * (unsigned)C;   // floats
     const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(a.in0, (unsigned)a.n * a.hin * a.win * (unsigned)C * 4u);
     const __amdgpu_buffer_rsrc_t rsw = make_rsrc(a.wgt2, (unsigned)a.cout * ktot * 4u);
-    const unsigned prog_lo = a.prog[lane], prog_hi = a.prog[64 + lane];      // the step program in two VGPRs (conv_band_prog_kernel)
-    auto entry = [&](int s) -> unsigned {
-        return s < 64 ? (unsigned)__builtin_amdgcn_readlane((int)prog_lo, s) : (unsigned)__builtin_amdgcn_readlane((int)prog_hi, s - 64);
-    };
+    const StepProg prog(a.prog, lane);
 
     // DMA pieces: piece j = wv + 4 jj covers band rows 8j .. 8j + 7 (lane -> row 8j + lane / 8, 16-B slot lane % 8).  A wave's pieces
     // are 32 rows apart: one swizzle serves all of them; their (row, x) block coordinates are decoded per request -- nine multiply-
@@ -2704,36 +2694,22 @@ __global__ __launch_bounds__(256, 2) void conv_band_prog_wide_kernel(const ConvA
     const int mA = m0 + wv * 64 + r, mB = mA + 32;
     epi_setup<NB, false, false>(a, mA, M, hw, n0, h, acc0, late, ec0, true, false);   // operands are loaded in the epilogue
     epi_setup<NB, false, false>(a, mB, M, hw, n0, h, acc1, late, ec1, true, false);
-    auto neighbours = [&](int m) -> unsigned {   // validity of the 9 neighbour blocks of the lane's output pixel
-        unsigned vm = 0;
-        if (m < M) {
-            const int img = fdiv(m, a.div_hw_mul, a.div_hw_sh), rem = m - img * hw;
-            const int py = fdiv(rem, a.div_w_mul, a.div_w_sh), px = rem - py * Wb;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int yy = py + t / 3 - 1, xx = px + t % 3 - 1;
-                if ((unsigned)yy < (unsigned)Hb && (unsigned)xx < (unsigned)Wb) vm |= 1u << t;
-            }
-        }
-        return vm;
-    };
-    const unsigned vmask0 = neighbours(mA), vmask1 = neighbours(mB);
+    const unsigned vmask0 = neighbours9(a, mA, M, hw, Hb, Wb), vmask1 = neighbours9(a, mB, M, hw, Hb, Wb);      // the 9 neighbour blocks of the lane's output pixels
     const int nsteps = a.prog_steps;
     const int mx_sa = a.mx_sa, mx_sb = a.mx_sb;
-    auto kofs_of = [&](unsigned e) -> int { return (int)(((e & 15u) * (unsigned)nch2 + ((e >> 8) & 255u)) * 32u); };
     {
-        const unsigned e0 = entry(0);
+        const unsigned e0 = prog.entry(0);
         if (tid < SP) lds[A_F4 + 2 * B_F4 + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-        issue_band((int)((e0 >> 16) & 1023u), (int)((e0 >> 26) & 3u) - 1);
-        issue_w(kofs_of(entry(1)), 0);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        issue_band(StepProg::band_src(e0), StepProg::band_dy(e0));
+        issue_w(StepProg::kofs(prog.entry(1), nch2), 0);
+        wait_barrier<0>();
     }
     unsigned next_band = 0;      // bits 16-27 of the current band's first step: the band after it
     for (int s = 1; s <= nsteps; ++s) {
-        const unsigned e = entry(s);
+        const unsigned e = prog.entry(s);
         const int slot = (s - 1) & 1;
-        const unsigned e_next = s < nsteps ? entry(s + 1) : 0u;
-        if (s < nsteps) issue_w(kofs_of(e_next), slot ^ 1);
+        const unsigned e_next = s < nsteps ? prog.entry(s + 1) : 0u;
+        if (s < nsteps) issue_w(StepProg::kofs(e_next, nch2), slot ^ 1);
         if (e & 16u) next_band = e;
         __builtin_amdgcn_sched_barrier(0);
         const int t = (int)(e & 15u);
@@ -2752,13 +2728,14 @@ __global__ __launch_bounds__(256, 2) void conv_band_prog_wide_kernel(const ConvA
             acc1[nb] = mma_split(acc1[nb], wb, xa1, mx_sb, mx_sa);
             __builtin_amdgcn_sched_barrier(0);
         }
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        wait_barrier<0>();
         if (e_next & 16u) {      // this was the band's last step and everyone has left it: fetch the next one into the same buffer
-            issue_band((int)((next_band >> 16) & 1023u), (int)((next_band >> 26) & 3u) - 1);
-            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+            issue_band(StepProg::band_src(next_band), StepProg::band_dy(next_band));
+            wait_vm_barrier<0>();
         }
     }
     // plain epilogues, one pixel block at a time; the second block's accumulators wait in LDS (idle now), as in conv3x3_wide_kernel
+    // (its copy of that block, loops included: as one shared function, or with the acc_* helpers, both kernels change)
     float4* park = &lds[wv * (NB * 4 * 64)];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
