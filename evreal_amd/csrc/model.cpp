@@ -1312,7 +1312,12 @@ int plan_etnet(evr_model* m, hipStream_t stream) {
     // token tensors [n, L, 1, c]: PLAIN where a VALU kernel reads them, the conv operand format where a linear layer does
     auto tok = [&](int c, int fmt) { return pl.tensor(L, 1, c, fmt); };
     DevTensor Wd[3], HS[3], HC[3];
-    for (int s = 0; s < 3; ++s) { Wd[s] = tok(256, 0); HS[s] = tok(256, 0); HC[s] = tok(256, 0); }
+    for (int s = 0; s < 3; ++s) {
+        Wd[s] = tok(256, 0); HS[s] = tok(256, 0); HC[s] = tok(256, 0);
+        // readable (evr_model_read_tensor): the encoder's input (words + position), the encoder's and the decoder's output of scale s
+        const std::string sn = std::to_string(s);
+        pl.name("words" + sn, Wd[s]); pl.name("hs" + sn, HS[s]); pl.name("hc" + sn, HC[s]);
+    }
     const DevTensor Ta = tok(256, 0), Tb = tok(256, 0), Tm = tok(256, 0), Tm2 = tok(256, 0), XA = tok(256, P), MEMN = tok(256, P);
     const DevTensor QKV = tok(768, 0), CQ = tok(256, 0), CKV = tok(512, 0), AO = tok(256, P), FF = tok(1024, P), SP = tok(256, 0);
 

@@ -1,4 +1,4 @@
-"""Oracle: recurrent-network forward passes on torch-CPU fp32 (UNetRecurrentOracle also in float64: dtype=).  TEST INFRASTRUCTURE ONLY.
+"""Oracle: recurrent-network forward passes on torch-CPU fp32 (UNetRecurrentOracle and ETNetOracle also in float64: dtype=).  TEST INFRASTRUCTURE ONLY.
 
 Functional restatement (state_dict in, tensors out) of the reference's nn.Modules, NCHW:
   UNetRecurrentOracle   model/unet.py:9-143 (BaseUNet/UNetRecurrent) +
@@ -346,13 +346,23 @@ def sine_position_table(n_position, d_hid=256):
     return torch.FloatTensor(ang)
 
 
+def _add_pos(words, table):
+    """words [n, L, E] + the position table's rows 0 .. L-1, the same for every sequence (u_trans.py:90-91, TransformerEncoder.with_embed)."""
+    return words + table[None]
+
+
 class ETNetOracle:
     """EITR / mls_tpa (model/eitr/eitr.py:4-16, u_trans.py:13-123)."""
 
-    def __init__(self, sd, norm=None):
-        self.sd = {k: v.detach().float() for k, v in sd.items()}
+    def __init__(self, sd, norm=None, dtype=torch.float32):
+        # dtype=torch.float64: weights, states and inputs in float64 -- the high-precision reference the token kernels are measured
+        # against (tests/test_gpu_etnet_tokens.py); the default float32 is the reference's own arithmetic.  The sine table stays the
+        # float32-ROUNDED table in either (the reference builds a FloatTensor, and the library holds the same fp32 constant).
+        self.dtype = dtype
+        self.sd = {k: v.detach().to(dtype) for k, v in sd.items()}
         self.norm = norm
         self.num_encoders = 3            # eval.py:152-153
+        self.taps = {}                   # after each call: words0..2 (encoder input: words + position), hs0..2, hc0..2, hs_trans, [n, L, 256]
         self.reset_states()
 
     def reset_states(self):
@@ -360,6 +370,7 @@ class ETNetOracle:
 
     def __call__(self, x):
         sd, norm = self.sd, self.norm
+        x = x.to(self.dtype)
         x = conv_layer(sd, 'head', x, 1, 2, 'relu', norm)
         head = x
         blocks = []
@@ -373,10 +384,12 @@ class ETNetOracle:
         words = [blocks[2].flatten(2).transpose(1, 2),                                            # nn.Unfold(1): the pixels
                  F.conv2d(blocks[1], sd['split1.weight'], sd['split1.bias'], stride=2).flatten(2).transpose(1, 2),
                  F.conv2d(blocks[0], sd['split2.weight'], sd['split2.bias'], stride=4).flatten(2).transpose(1, 2)]
-        pos = sine_position_table(words[0].shape[1])[None]
+        pos = sine_position_table(words[0].shape[1]).to(self.dtype)
+        taps = {}
         hs = []
         for s in range(3):
-            t = (words[s] + pos).transpose(0, 1)                                                 # [L, N, E]
+            t = _add_pos(words[s], pos).transpose(0, 1)                                          # [L, N, E]
+            taps[f'words{s}'] = t.transpose(0, 1)
             for l in range(3):
                 t = _enc_layer(sd, f'trans_encoder{s}.encoder.layers.{l}', t)
             hs.append(t)
@@ -387,6 +400,10 @@ class ETNetOracle:
                 t = _dec_layer(sd, f'trans_decoder{s}.decoder.layers.{l}', t, mem)
             hc.append(t)
         t = (hs[0] + hs[1] + hs[2] + hc[0] + hc[1] + hc[2]) / 6
+        for s in range(3):
+            taps[f'hs{s}'] = hs[s].transpose(0, 1); taps[f'hc{s}'] = hc[s].transpose(0, 1)
+        taps['hs_trans'] = t.transpose(0, 1)
+        self.taps = taps
         y = t.permute(1, 2, 0).reshape(n, 256, H // 8, W // 8)                                   # '(h w) n c -> n c h w'
         for i in range(3):
             y = upsample_conv_layer(sd, f'UpsampleConv.{i}', y + blocks[2 - i], 2, 'relu', norm)

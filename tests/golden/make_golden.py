@@ -671,6 +671,47 @@ def make_etnet():
                  weights_sha=np.array(weights.state_dict_digest(sd)), images=np.concatenate(imgs), **out)
 
 
+def make_etnet_ref64():
+    """The reference class EITR (norm=None) in float64 on one 24x88 sequence (33 tokens per scale), two frames: pins the float64 mode
+    of oracle.model.ETNetOracle and its taps, the high-precision reference of tests/test_gpu_etnet_tokens.py.  Forward hooks on
+    trans_encoder{s} / trans_decoder{s} record the encoder's input (src + pos) and the six token sets of the LAST frame, as
+    [n, L, 256]; their mean is formed as u_trans.py:111 does.  Images in full; tokens as a [..., ::4] and the final ConvLSTM states
+    as a [:, ::8] channel subsample (the whole fixture stays near 300 KB)."""
+    import copy
+    sd = weights.synth_state_dict(weights.etnet_schema(norm=None), seed=41)
+    net = ref_model.EITR({'num_bins': 5, 'norm': None})
+    net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+    net.eval()
+    m64 = copy.deepcopy(net).double()
+    m64.reset_states()
+    F, H, W = 2, 24, 88
+    vox = synth.sparse_voxels(411, F, 5, H, W, density=0.15)
+    tok = {}
+    hooks = []
+    for s in range(3):
+        enc, dec = getattr(m64, f'trans_encoder{s}'), getattr(m64, f'trans_decoder{s}')
+        hooks.append(enc.register_forward_hook(
+            lambda mod, args, kwargs, out, s=s: tok.update({f'words{s}': (kwargs['src'] + kwargs['pos']).transpose(0, 1), f'hs{s}': out.transpose(0, 1)}),
+            with_kwargs=True))
+        hooks.append(dec.register_forward_hook(lambda mod, args, out, s=s: tok.update({f'hc{s}': out.transpose(0, 1)})))
+    with torch.no_grad():
+        imgs = [m64(torch.from_numpy(vox[f:f + 1]).double())['image'].numpy() for f in range(F)]
+    for h in hooks:
+        h.remove()
+    tok['hs_trans'] = (tok['hs0'] + tok['hs1'] + tok['hs2'] + tok['hc0'] + tok['hc1'] + tok['hc2']) / 6
+    out = {}
+    for k, v in tok.items():
+        assert v.dtype == torch.float64 and tuple(v.shape) == (1, (H // 8) * (W // 8), 256), (k, v.dtype, v.shape)
+        out[k + '_sub'] = v.numpy()[..., ::4].copy()
+    for i, (h, c) in enumerate(m64._states):
+        assert h.dtype == torch.float64 and c.dtype == torch.float64
+        out[f'h{i}_sub'] = h.numpy()[:, ::8].copy(); out[f'c{i}_sub'] = c.numpy()[:, ::8].copy()
+    images = np.concatenate(imgs)
+    assert images.dtype == np.float64
+    save_npz('etnet_ref64.npz', voxel_sha=np.array(sha(vox)), voxel_args=np.array([411, F, 5, H, W]), seed=np.array(41),
+             weights_sha=np.array(weights.state_dict_digest(sd)), images=images, **out)
+
+
 def make_spade():
     """SPADE-E2VID (reference class Unet6, exported as SpadeE2vid) with deterministic synthetic weights: 4 frames of
     one 64x96 sequence -> images, final hidden states, and the 3-channel prev_recs of the last frame."""
@@ -692,8 +733,8 @@ def make_spade():
 
 if __name__ == '__main__':
     which = sys.argv[1:] or ['voxel', 'dataset', 'helpers', 'firenet', 'e2vid', 'e2vid_ref64', 'eval', 'eval_e2vid', 'color', 'spade', 'metrics', 'etnet',
-                             'firenetplus_ckpt']
+                             'etnet_ref64', 'firenetplus_ckpt']
     for w in which:
         {'voxel': make_voxel, 'dataset': make_dataset, 'helpers': make_helpers,
-         'firenet': make_firenet, 'e2vid': make_e2vid, 'e2vid_ref64': make_e2vid_ref64, 'eval': make_eval, 'eval_e2vid': make_eval_e2vid, 'color': make_color, 'spade': make_spade, 'metrics': make_metrics_published, 'etnet': make_etnet,
+         'firenet': make_firenet, 'e2vid': make_e2vid, 'e2vid_ref64': make_e2vid_ref64, 'eval': make_eval, 'eval_e2vid': make_eval_e2vid, 'color': make_color, 'spade': make_spade, 'metrics': make_metrics_published, 'etnet': make_etnet, 'etnet_ref64': make_etnet_ref64,
          'firenetplus_ckpt': make_firenetplus_ckpt}[w]()

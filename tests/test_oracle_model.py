@@ -181,6 +181,71 @@ def test_e2vid_bn_float64_oracle_matches_the_reference_in_float64():
     assert 0.0 < spread < 1e-5, spread
 
 
+ETNET_TAPS = [f'{k}{s}' for k in ('words', 'hs', 'hc') for s in range(3)] + ['hs_trans']
+
+
+def test_etnet_float64_oracle_and_its_taps_match_the_reference_in_float64():
+    """ETNetOracle(dtype=torch.float64) against the reference class EITR run in float64 (copy.deepcopy(net).double(),
+    tests/golden/make_golden.py make_etnet_ref64) on one 24x88 sequence (33 tokens per scale), two frames: images of every frame, the
+    final ConvLSTM states and, from the last frame, the encoder inputs, the six token sets and their mean (forward hooks on the
+    reference's trans_encoder{s} / trans_decoder{s}) to float64 level.  tests/test_gpu_etnet_tokens.py measures the token kernels
+    against this oracle without the reference."""
+    z = load_npz('etnet_ref64.npz')
+    sd = weights.synth_state_dict(weights.etnet_schema(norm=None), seed=int(z['seed']))
+    assert weights.state_dict_digest(sd) == str(z['weights_sha'])
+    tsd = {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
+    m = omod.ETNetOracle(tsd, norm=None, dtype=torch.float64)
+    seed, F, B, H, W = [int(v) for v in z['voxel_args']]
+    vox = synth.sparse_voxels(seed, F, B, H, W, density=0.15)
+    assert sha(vox) == str(z['voxel_sha'])
+    m32 = omod.ETNetOracle(tsd, norm=None)
+    spread = 0.0
+    for f in range(F):
+        x = torch.from_numpy(vox[f:f + 1])
+        img = m(x)
+        assert img.dtype == torch.float64
+        np.testing.assert_allclose(img.numpy(), z['images'][f:f + 1], rtol=0, atol=1e-12, err_msg=f'frame {f}')
+        spread = max(spread, float(np.abs(m32(x).numpy() - z['images'][f:f + 1]).max()))
+    for i, (h, c) in enumerate(m.states):
+        assert h.dtype == torch.float64 and c.dtype == torch.float64
+        np.testing.assert_allclose(h.numpy()[:, ::8], z[f'h{i}_sub'], rtol=0, atol=1e-12, err_msg=f'h{i}')
+        np.testing.assert_allclose(c.numpy()[:, ::8], z[f'c{i}_sub'], rtol=0, atol=1e-12, err_msg=f'c{i}')
+    assert sorted(m.taps) == sorted(ETNET_TAPS)
+    tok_spread = 0.0
+    for k in ETNET_TAPS:
+        t = m.taps[k]
+        assert t.dtype == torch.float64 and tuple(t.shape) == (1, (H // 8) * (W // 8), 256), (k, t.dtype, t.shape)
+        # tokens reach magnitudes near 10: 1e-12 absolute is still four decimal digits above float64's own rounding there
+        np.testing.assert_allclose(t.numpy()[..., ::4], z[k + '_sub'], rtol=0, atol=1e-12, err_msg=k)
+        tok_spread = max(tok_spread, float(np.abs(m32.taps[k].numpy()[..., ::4] - z[k + '_sub']).max()))
+    # the fixture is float64 and not a copy of an fp32 result: the fp32 oracle differs from it by its own rounding
+    assert 0.0 < spread < 1e-5, spread
+    assert 0.0 < tok_spread < 1e-4, tok_spread
+
+
+def test_etnet_float64_oracle_default_is_the_fp32_oracle():
+    """dtype defaults to float32: the ET-Net oracle every other test uses is unchanged (weights, states, taps and image fp32), and an
+    explicit dtype=torch.float32 gives the same bits."""
+    sd = weights.synth_state_dict(weights.etnet_schema(norm=None), seed=3)
+    tsd = {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
+    m = omod.ETNetOracle(tsd)
+    assert m.dtype == torch.float32 and all(v.dtype == torch.float32 for v in m.sd.values()) and m.taps == {}
+    x = torch.from_numpy(synth.sparse_voxels(4, 1, 5, 16, 24))
+    torch.set_num_threads(1)
+    out = m(x)
+    assert out.dtype == torch.float32 and m.states[0][1].dtype == torch.float32
+    assert sorted(m.taps) == sorted(ETNET_TAPS) and all(t.dtype == torch.float32 and tuple(t.shape) == (1, 6, 256) for t in m.taps.values())
+    m2 = omod.ETNetOracle(tsd, norm=None, dtype=torch.float32)
+    assert torch.equal(m2(x), out) and all(torch.equal(m2.taps[k], m.taps[k]) for k in ETNET_TAPS)
+    # the sine table stays the float32-rounded table in float64 (the library holds the same fp32 constant)
+    m64 = omod.ETNetOracle(tsd, dtype=torch.float64)
+    m64(x)
+    pos = omod.sine_position_table(6)
+    assert pos.dtype == torch.float32
+    words = m64.states[2][0].flatten(2).transpose(1, 2)
+    assert torch.equal(m64.taps['words0'], words + pos.double()[None])
+
+
 def test_float64_oracle_default_is_the_fp32_oracle():
     """dtype defaults to float32: the oracle every other test uses is unchanged (weights, zero states and prev_recs fp32)."""
     kw = weights.E2VID_KWARGS
