@@ -280,10 +280,7 @@ extern "C" int evr_color_percentile_normalize(const uint8_t* bgr_in, uint8_t* bg
     if (n == 0) return EVR_OK;
     EVR_REQUIRE(bgr_in != nullptr && bgr_out != nullptr && values256 != nullptr, "evr_color_percentile_normalize: null argument");
     const size_t need = evr_color_percentile_normalize_workspace_bytes(n);
-    if (!workspace || workspace_bytes < need) {
-        evr::set_error("evr_color_percentile_normalize: workspace %zu B < required %zu B", workspace_bytes, need);
-        return EVR_ERR_WORKSPACE;
-    }
+    EVR_REQUIRE_WORKSPACE("evr_color_percentile_normalize", workspace, workspace_bytes, need);
     EVR_REQUIRE((((uintptr_t)workspace) & 3) == 0, "evr_color_percentile_normalize: workspace must be 4-byte aligned");
     const int nbytes = 3 * H * W;
     unsigned* counts = (unsigned*)workspace;

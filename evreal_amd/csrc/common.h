@@ -25,17 +25,21 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
         }                                       \
     } while (0)
 #define EVR_LAUNCH_CHECK() EVR_HIP(hipGetLastError())
+// a call's workspace `ws` of `bytes` must exist and hold `need` bytes; `what` names the entry point (a string)
+#define EVR_REQUIRE_WORKSPACE(what, ws, bytes, need)                                                        \
+    do {                                                                                                    \
+        if (!(ws) || (size_t)(bytes) < (size_t)(need)) {                                                    \
+            evr::set_error("%s: workspace %zu B < required %zu B", what, (size_t)(bytes), (size_t)(need));  \
+            return EVR_ERR_WORKSPACE;                                                                       \
+        }                                                                                                   \
+    } while (0)
 
 namespace evr {
 // a host vector into a device allocation of its own (weights, biases, tables: made once per handle)
-inline int upload(const std::vector<float>& h, float** d) {
-    EVR_HIP(hipMalloc((void**)d, h.size() * sizeof(float) + 64));
-    EVR_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return EVR_OK;
-}
-inline int upload(const std::vector<unsigned>& h, unsigned** d) {
-    EVR_HIP(hipMalloc((void**)d, h.size() * sizeof(unsigned) + 64));
-    EVR_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+template <typename T>   // float, unsigned, double
+inline int upload(const std::vector<T>& h, T** d) {
+    EVR_HIP(hipMalloc((void**)d, h.size() * sizeof(T) + 64));
+    EVR_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     return EVR_OK;
 }
 }  // namespace evr

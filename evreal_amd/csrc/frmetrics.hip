@@ -194,10 +194,7 @@ extern "C" int evr_fr_metrics(const float* img, const float* ref, int n, int H, 
     if (n == 0) return EVR_OK;
     EVR_REQUIRE(img && ref && out_scores, "evr_fr_metrics: null pointer");
     const FrPlan p = make_plan(n, H, W);
-    if (!workspace || workspace_bytes < p.bytes) {
-        evr::set_error("evr_fr_metrics: workspace %zu B < required %zu B", workspace_bytes, p.bytes);
-        return EVR_ERR_WORKSPACE;
-    }
+    EVR_REQUIRE_WORKSPACE("evr_fr_metrics", workspace, workspace_bytes, p.bytes);
     Gauss g;
     {
         double sum = 0.0;

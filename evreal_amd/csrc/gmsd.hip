@@ -147,10 +147,7 @@ extern "C" int evr_gmsd(const float* img, const float* ref, int n, int H, int W,
     if (n == 0) return EVR_OK;
     EVR_REQUIRE(img && ref && out, "evr_gmsd: null pointer");
     const size_t need = evr_gmsd_workspace_bytes(n, H, W);
-    if (!workspace || workspace_bytes < need) {
-        evr::set_error("evr_gmsd: workspace %zu B < required %zu B", workspace_bytes, need);
-        return EVR_ERR_WORKSPACE;
-    }
+    EVR_REQUIRE_WORKSPACE("evr_gmsd", workspace, workspace_bytes, need);
     const int h2 = H / 2, w2 = W / 2;
     const int gy = (h2 + TH - 1) / TH, gx = (w2 + TW - 1) / TW;
     EVR_REQUIRE(gy <= 65535, "evr_gmsd: frames of more than %d rows are not supported, got %d", 65535 * 2 * TH, H);

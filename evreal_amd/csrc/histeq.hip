@@ -216,10 +216,7 @@ extern "C" int evr_hist_equalize(float* img, int n, int H, int W, int mode, void
     }
     EVR_REQUIRE(mode == EVR_HISTEQ_LOCAL || mode == EVR_HISTEQ_CLAHE, "evr_hist_equalize: unknown mode %d", mode);
     const size_t need = evr_hist_equalize_workspace_bytes(n, H, W, mode);
-    if (!workspace || workspace_bytes < need) {
-        evr::set_error("evr_hist_equalize: workspace %zu B < required %zu B", workspace_bytes, need);
-        return EVR_ERR_WORKSPACE;
-    }
+    EVR_REQUIRE_WORKSPACE("evr_hist_equalize", workspace, workspace_bytes, need);
     unsigned char* u8 = (unsigned char*)workspace;
     const int64_t total = (int64_t)n * HW;
     hipLaunchKernelGGL(he_to_u8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, img, u8, total);

@@ -3,7 +3,8 @@
 // Device side: 256-thread blocks of four waves.  A tile kernel owns one tile of one frame (blockIdx.x / y the tile, blockIdx.z
 // + f0 the frame), keeps Q running fp64 sums per thread and ends in tile_partials: wave sums, one LDS hand-off, the four wave
 // totals added left to right, Q doubles at the tile's slot.  A finish kernel (one block per frame) calls frame_total once per
-// sum: a thread walks the frame's slots in steps of 256, then the wave sum and the same four-term add.  No atomics, and the
+// sum: a thread walks the frame's slots in steps of 256, then the wave sum and the same four-term add (block_total; block_totals
+// is the array form that the no-reference kernels of nriqa.hip end in, see nss.h).  No atomics, and the
 // number of tiles depends on the shape alone: a frame's numbers are bitwise independent of n, of its place in the batch and of
 // earlier calls.  Windowed second moments (frmetrics.hip, vifp.hip): N taps over the VALID region as two separable passes on a
 // staged tile of (TH + N - 1) x (TW + N - 1) pixels, rows padded by one; taps added in index order (a = w0 * v0; a += wk * vk),
@@ -42,17 +43,36 @@ __device__ __forceinline__ void tile_partials(double (&red)[sizeof...(D)][NT / 6
     }
 }
 
-// The sum of src[0], src[Q], ... (`tiles` entries), one column of a frame's tile partials, in every thread of the block.  A
-// second call with the same `red` needs a __syncthreads() in between.
+// The array form (nriqa.hip): Q running sums per thread in a[], the block's totals at dst[0 .. Q), in LDS or at a slot in
+// memory, written by threads 0 .. Q - 1.
 template <int Q>
-__device__ __forceinline__ double frame_total(const double* src, int tiles, double (&red)[NT / 64]) {
+__device__ __forceinline__ void block_totals(const double (&a)[Q], double (&red)[NT / 64][Q], double* dst) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double a = 0.0;
-    for (int t = tid; t < tiles; t += NT) a += src[(int64_t)t * Q];
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+        const double s = evr_wave_sum(a[k]);
+        if (lane == 0) red[wave][k] = s;
+    }
+    __syncthreads();
+    if (tid < Q) dst[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// The block's total of one running sum per thread, in every thread of the block.  A second call with the same `red` needs a
+// __syncthreads() in between.
+__device__ __forceinline__ double block_total(double a, double (&red)[NT / 64]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     a = evr_wave_sum(a);
     if (lane == 0) red[wave] = a;
     __syncthreads();
     return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// The sum of src[0], src[Q], ... (`tiles` entries), one column of a frame's tile partials, walked in steps of 256.
+template <int Q>
+__device__ __forceinline__ double frame_total(const double* src, int tiles, double (&red)[NT / 64]) {
+    double a = 0.0;
+    for (int t = threadIdx.x; t < tiles; t += NT) a += src[(int64_t)t * Q];
+    return block_total(a, red);
 }
 
 // Pass 1, along axis 0: rows r .. r + N - 1 of the staged planes belong to output row r.

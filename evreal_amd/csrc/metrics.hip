@@ -150,10 +150,7 @@ extern "C" int evr_metrics(const float* img, const float* ref, int n, int H, int
     // 12 x 12 is the smallest frame: at 11 x 11 the crop leaves ONE pixel of the SSIM map, not a mean over a frame
     EVR_REQUIRE(!(which & 2u) || (H > 2 * R + 1 && W > 2 * R + 1), "evr_metrics: SSIM needs images larger than 11x11 (win_size)");
     const size_t need = evr_metrics_workspace_bytes(n, H, W);
-    if (!workspace || workspace_bytes < need) {
-        evr::set_error("evr_metrics: workspace %zu B < required %zu B", workspace_bytes, need);
-        return EVR_ERR_WORKSPACE;
-    }
+    EVR_REQUIRE_WORKSPACE("evr_metrics", workspace, workspace_bytes, need);
     // scipy.ndimage._gaussian_kernel1d(sigma=1.5, order=0, radius=5) in fp64
     Gauss g;
     {

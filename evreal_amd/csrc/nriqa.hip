@@ -15,33 +15,20 @@
 // Launches per batch, whatever n: resize, block kernel at scale 1, block kernel at scale 2, score (features: three).
 // Every frame's arithmetic runs in work-groups of its own, each sum in a fixed order, no atomics: the results are
 // bitwise independent of the batch size and of a frame's position in the batch.
-#include "common.h"
-#include <cmath>
+// What the three metrics share -- MSCN, the AGGD fit, the hand-offs, the workspace carve, the handles' storage and the run
+// functions' refusals -- is csrc/nss.h.  More than 65535 frames: the kernels that carry the frame on gridDim.y are launched per
+// chunk of 65535 on offset pointers (every frame owns its part of every workspace region); the finishers ride gridDim.x.
+#include "nss.h"
 #include <new>
-#include <vector>
 
 namespace {
 
+using namespace evr_nss;
+using evr_tiles::block_total, evr_tiles::block_totals, evr_tiles::for_frame_chunks;
+
 constexpr int BLK = 96;
 constexpr int NF = 36;                 // features per block: 18 per scale
-constexpr int NGRID = 9801;            // alpha = 0.2 + 0.001 k, k = 0 .. 9800
 constexpr int MAX_BLOCKS = 8192;       // blocks per frame the score kernel takes (its NaN-row flags live in LDS)
-constexpr int NT = 256;
-
-struct Taps { double g[49]; };         // the 7x7 Gaussian, row-major
-
-__device__ __forceinline__ int clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-// symmetric (half-sample) reflection, repeated for an index more than one length outside (a side shorter than 4)
-__device__ __forceinline__ int mirror(int i, int n) {
-    i %= 2 * n;
-    if (i < 0) i += 2 * n;
-    return i < n ? i : 2 * n - 1 - i;
-}
-
-__device__ __forceinline__ float quant(float v, int clip) {
-    if (clip) v = fminf(fmaxf(v, 0.f), 1.f);
-    return rintf(255.f * v);
-}
 
 // imresize(u, 0.5) of the cropped (NIQE) or whole (BRISQUE) quantised frame: out [n, ceil(Hc/2), ceil(Wc/2)]
 __global__ __launch_bounds__(NT) void niqe_resize_kernel(const float* __restrict__ img, int H, int W, int Hc, int Wc,
@@ -67,8 +54,6 @@ __global__ __launch_bounds__(NT) void niqe_resize_kernel(const float* __restrict
     }
     out[(int64_t)f * Hh * Wh + i] = acc;
 }
-
-__device__ __forceinline__ bool better(double d, int k, double bd, int bk) { return d < bd || (d == bd && k < bk); }
 
 // One work-group per (block, frame) at one scale: MSCN on chip, the 26 block sums (5 vectors x {sum x^2 | x<0, n<0,
 // sum x^2 | x>0, n>0, sum |x|} + the sigma sum), then the five AGGD fits -> feat[f][b][scale*18 .. +18].
@@ -98,19 +83,9 @@ __global__ __launch_bounds__(NT) void niqe_block_kernel(const float* __restrict_
     double ssig = 0.0;
     for (int i = tid; i < S * S; i += NT) {
         const int r = i / S, c = i % S;
-        double mu = 0.0, s2 = 0.0;
-#pragma unroll
-        for (int dy = 0; dy < 7; ++dy) {
-#pragma unroll
-            for (int dx = 0; dx < 7; ++dx) {
-                const double v = (double)tile[r + dy][c + dx], g = taps.g[dy * 7 + dx];
-                mu = mu + g * v;
-                s2 = s2 + g * (v * v);
-            }
-        }
-        const double sigma = sqrt(fabs(s2 - mu * mu));
-        m[r][c] = ((double)tile[r + 3][c + 3] - mu) / (sigma + 1.0);
-        ssig += sigma;
+        const Mscn p = mscn_at(taps, (double)tile[r + 3][c + 3], [&](int dy, int dx) { return (double)tile[r + dy][c + dx]; });
+        m[r][c] = p.m;
+        ssig += p.sigma;
     }
     __syncthreads();
 
@@ -128,21 +103,9 @@ __global__ __launch_bounds__(NT) void niqe_block_kernel(const float* __restrict_
         v[3] = x * m[(r + S - 1) % S][(c + S - 1) % S];        // (1, 1)
         v[4] = x * m[(r + S - 1) % S][(c + 1) % S];            // (1, -1)
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const double q = v[k] * v[k];
-            if (v[k] < 0.0) { a[k * 5 + 0] += q; a[k * 5 + 1] += 1.0; }
-            if (v[k] > 0.0) { a[k * 5 + 2] += q; a[k * 5 + 3] += 1.0; }
-            a[k * 5 + 4] += fabs(v[k]);
-        }
+        for (int k = 0; k < 5; ++k) aggd_add(v[k], a + 5 * k);
     }
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        const double s = evr_wave_sum(a[k]);
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-    if (tid < NS) st[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    block_totals(a, red, st);
     __syncthreads();
 
     const double* R = table;
@@ -150,29 +113,13 @@ __global__ __launch_bounds__(NT) void niqe_block_kernel(const float* __restrict_
     const double* F1 = table + 2 * NGRID;
     const double* F2 = table + 3 * NGRID;
     const double N = (double)(S * S);
+    const int lane = tid & 63, wave = tid >> 6;
     double* out = feat + ((int64_t)f * nb + b) * NF + (S == BLK ? 0 : 18);
     for (int v = wave; v < 5; v += NT / 64) {      // one wave per fit
         const double* s = st + v * 5;
-        const double ls = sqrt(s[0] / s[1]), rs = sqrt(s[2] / s[3]);     // an empty side: 0/0 = NaN
-        const double g = ls / rs;
-        const double ma = s[4] / N;
-        const double rhat = (ma * ma) / ((s[0] + s[2]) / N);
-        const double rn = (rhat * (g * g * g + 1.0) * (g + 1.0)) / ((g * g + 1.0) * (g * g + 1.0));
-        int bk = 0;
-        if (!isnan(rn)) {
-            double bd = (R[lane] - rn) * (R[lane] - rn);
-            bk = lane;
-            for (int k = lane + 64; k < NGRID; k += 64) {
-                const double d = (R[k] - rn) * (R[k] - rn);
-                if (d < bd) { bd = d; bk = k; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double od = __shfl_xor(bd, o, 64);
-                const int ok = __shfl_xor(bk, o, 64);
-                if (better(od, ok, bd, bk)) { bd = od; bk = ok; }
-            }
-        }
+        const Aggd fit = aggd_ratio(s, s[0] + s[2], N);
+        const double ls = fit.ls, rs = fit.rs;
+        const int bk = alpha_argmin(fit.rn, [&](int k) { return (R[k] - fit.rn) * (R[k] - fit.rn); });
         if (lane == 0) {
             const double bl = ls * F1[bk], br = rs * F1[bk];
             if (v == 0) {
@@ -207,14 +154,10 @@ __global__ __launch_bounds__(NT) void niqe_score_kernel(const double* __restrict
         bool full = true;
         for (int k = 0; k < NF; ++k) full = full && !isnan(F[(int64_t)r * NF + k]);
         ok[r] = full ? 1 : 0;
-        c += full ? 1 : 0;
+        c += wave_votes(full);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-    if ((tid & 63) == 0) cnt[tid >> 6] = c;
     if (tid == 0) bad = 0;
-    __syncthreads();
-    const int m = ((cnt[0] + cnt[1]) + cnt[2]) + cnt[3];
+    const int m = block_count(c, cnt);
     if (tid < NF) {
         double s = 0.0, sc = 0.0;
         int k = 0;
@@ -269,60 +212,21 @@ __global__ void niqe_nan_kernel(double* __restrict__ scores, int n) {
     if (i < n) scores[i] = (double)NAN;
 }
 
-Taps gaussian_taps() {
-    // fspecial('gaussian', 7, 7/6); tests/nriqa_ref.py gaussian_window() evaluates the same expressions in the same order
-    Taps t;
-    const double sig = 7.0 / 6.0;
-    for (int i = 0; i < 7; ++i)
-        for (int j = 0; j < 7; ++j) {
-            const int y = i - 3, x = j - 3;
-            t.g[i * 7 + j] = std::exp(-(double)(x * x + y * y) / (2.0 * sig * sig));
-        }
-    double s = 0.0;
-    for (int k = 0; k < 49; ++k) s += t.g[k];
-    for (int k = 0; k < 49; ++k) t.g[k] = t.g[k] / s;
-    return t;
-}
-
-// The alpha grid's columns, Gamma evaluated once on the host: r(alpha) = G(2/a)^2/(G(1/a)G(3/a)) (the AGGD ratio), alpha,
-// sqrt(G(1/a)/G(3/a)), G(2/a)/G(1/a), and with cols = 5 the GGD ratio G(1/a)G(3/a)/G(2/a)^2.  [cols][NGRID]
-std::vector<double> alpha_table(int cols) {
-    std::vector<double> table((size_t)cols * NGRID);
-    for (int k = 0; k < NGRID; ++k) {
-        const double a = 0.2 + 0.001 * (double)k;
-        const double g1 = std::tgamma(1.0 / a), g2 = std::tgamma(2.0 / a), g3 = std::tgamma(3.0 / a);
-        table[k] = (g2 * g2) / (g1 * g3);
-        table[NGRID + k] = a;
-        table[2 * NGRID + k] = std::sqrt(g1 / g3);
-        table[3 * NGRID + k] = g2 / g1;
-        if (cols > 4) table[4 * NGRID + k] = (g1 * g3) / (g2 * g2);
-    }
-    return table;
-}
-
-struct Dims {
-    int Hc, Wc, nb, nbx;
-    size_t half_bytes, feat_bytes, sharp_bytes;
+struct Dims {                        // the crop to whole blocks and the block counts
+    int Hc, Wc, nbx, nb;
+    Dims(int H, int W) : Hc((H / BLK) * BLK), Wc((W / BLK) * BLK), nbx(Wc / BLK), nb((Hc / BLK) * nbx) {}
 };
 
-Dims dims(int n, int H, int W) {
-    Dims d;
-    d.Hc = (H / BLK) * BLK; d.Wc = (W / BLK) * BLK;
-    d.nbx = d.Wc / BLK;
-    d.nb = (d.Hc / BLK) * d.nbx;
-    d.half_bytes = evr::align_up((size_t)n * (d.Hc / 2) * (d.Wc / 2) * sizeof(double), 256);
-    d.feat_bytes = evr::align_up((size_t)n * d.nb * NF * sizeof(double), 256);
-    d.sharp_bytes = evr::align_up((size_t)n * d.nb * sizeof(double), 256);
-    return d;
-}
+struct NiqeWs : Carve {              // the workspace: a member takes the next region, in the members' order
+    double *half, *feat, *sharp;
+    NiqeWs(void* ws, size_t n, const Dims& d)
+        : Carve(ws), half(take<double>(n * (d.Hc / 2) * (d.Wc / 2))), feat(take<double>(n * d.nb * NF)),
+          sharp(take<double>(n * d.nb)) {}
+};
 
 }  // namespace
 
-struct evr_niqe {
-    double* d_model = nullptr;   // mu [36], cov [36*36]
-    double* d_table = nullptr;   // r(alpha), alpha, sqrt(G(1/a)/G(3/a)), G(2/a)/G(1/a): [4][9801]
-    Taps taps;
-};
+struct evr_niqe : evr_nss::Model {};        // d_model: mu [36], cov [36*36]; d_table: [4][9801]
 
 extern "C" int evr_niqe_create(const double* mu, const double* cov, evr_niqe** out) {
     EVR_REQUIRE(mu && cov && out, "evr_niqe_create: null pointer");
@@ -347,54 +251,27 @@ extern "C" int evr_niqe_create(const double* mu, const double* cov, evr_niqe** o
     std::vector<double> model(NF + NF * NF);
     for (int i = 0; i < NF; ++i) model[i] = mu[i];
     for (int i = 0; i < NF * NF; ++i) model[NF + i] = cov[i];
-    const std::vector<double> table = alpha_table(4);
     evr_niqe* h = new (std::nothrow) evr_niqe();
     EVR_REQUIRE(h, "evr_niqe_create: out of host memory");
-    h->taps = gaussian_taps();
-    hipError_t e = hipMalloc((void**)&h->d_model, model.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_table, table.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(h->d_model, model.data(), model.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->d_model) (void)hipFree(h->d_model);
-        if (h->d_table) (void)hipFree(h->d_table);
-        delete h;
-        return evr::hip_fail(e, "evr_niqe_create", __FILE__, __LINE__);
-    }
-    *out = h;
-    return EVR_OK;
+    return finish_create(h, model, 4, out);
 }
 
-extern "C" int evr_niqe_destroy(evr_niqe* h) {
-    if (!h) return EVR_OK;
-    hipError_t e1 = h->d_model ? hipFree(h->d_model) : hipSuccess;
-    hipError_t e2 = h->d_table ? hipFree(h->d_table) : hipSuccess;
-    delete h;
-    EVR_HIP(e1);
-    EVR_HIP(e2);
-    return EVR_OK;
-}
+extern "C" int evr_niqe_destroy(evr_niqe* h) { return destroy(h); }
 
 extern "C" size_t evr_niqe_workspace_bytes(int n, int H, int W) {
     if (n < 0 || H < 1 || W < 1) return 0;
-    const Dims d = dims(n, H, W);
-    return d.half_bytes + d.feat_bytes + d.sharp_bytes + 256;
+    return NiqeWs(nullptr, n, Dims(H, W)).bytes();
 }
 
 static int niqe_run(evr_niqe* h, const float* img, int n, int H, int W, int clip, double* scores, double* feat,
                     double* sharp, void* ws, size_t ws_bytes, evr_stream_t stream_, const char* what) {
     hipStream_t stream = (hipStream_t)stream_;
     EVR_REQUIRE(h, "%s: null handle", what);
-    EVR_REQUIRE(n >= 0 && H >= 1 && W >= 1, "%s: bad shape", what);
-    if (n == 0) return EVR_OK;
-    EVR_REQUIRE(img && (scores || (feat && sharp)), "%s: null pointer", what);
-    const Dims d = dims(n, H, W);
+    const int rc = check_run(what, 0, n, H, W, img && (scores || (feat && sharp)));
+    if (rc != EVR_OK || n == 0) return rc;
+    const Dims d(H, W);
     EVR_REQUIRE(d.nb <= MAX_BLOCKS, "%s: %d blocks per frame > %d", what, d.nb, MAX_BLOCKS);
-    const size_t need = evr_niqe_workspace_bytes(n, H, W);
-    if (!ws || ws_bytes < need) {
-        evr::set_error("%s: workspace %zu B < required %zu B", what, ws_bytes, need);
-        return EVR_ERR_WORKSPACE;
-    }
+    EVR_REQUIRE_WORKSPACE(what, ws, ws_bytes, evr_niqe_workspace_bytes(n, H, W));
     if (d.nb == 0) {              // no whole 96 x 96 block: NaN scores, no features
         if (scores) {
             hipLaunchKernelGGL(niqe_nan_kernel, dim3((n + NT - 1) / NT), dim3(NT), 0, stream, scores, n);
@@ -402,22 +279,28 @@ static int niqe_run(evr_niqe* h, const float* img, int n, int H, int W, int clip
         }
         return EVR_OK;
     }
-    char* p = (char*)ws;
-    double* half = (double*)p; p += d.half_bytes;
-    double* wfeat = (double*)p; p += d.feat_bytes;
-    double* wsharp = (double*)p;
-    if (!feat) feat = wfeat;
-    if (!sharp) sharp = wsharp;
+    const NiqeWs w(ws, n, d);
+    if (!feat) feat = w.feat;
+    if (!sharp) sharp = w.sharp;
     const int Hh = d.Hc / 2, Wh = d.Wc / 2;
-    hipLaunchKernelGGL(niqe_resize_kernel, dim3((unsigned)(((int64_t)Hh * Wh + NT - 1) / NT), n), dim3(NT), 0, stream, img, H, W,
-                       d.Hc, d.Wc, clip, half);
-    EVR_LAUNCH_CHECK();
-    hipLaunchKernelGGL((niqe_block_kernel<BLK, float>), dim3(d.nb, n), dim3(NT), 0, stream, img, (const double*)nullptr, H, W,
-                       d.Hc, d.Wc, clip, d.nbx, h->taps, (const double*)h->d_table, feat, sharp);
-    EVR_LAUNCH_CHECK();
-    hipLaunchKernelGGL((niqe_block_kernel<BLK / 2, double>), dim3(d.nb, n), dim3(NT), 0, stream, (const float*)nullptr,
-                       (const double*)half, H, W, Hh, Wh, clip, d.nbx, h->taps, (const double*)h->d_table, feat, (double*)nullptr);
-    EVR_LAUNCH_CHECK();
+    const size_t px = (size_t)H * W, hpx = (size_t)Hh * Wh;
+    const int run = for_frame_chunks(n, [&](int f0, int nf) -> int {
+        double* half = w.half + f0 * hpx;
+        double* cfeat = feat + (size_t)f0 * d.nb * NF;
+        hipLaunchKernelGGL(niqe_resize_kernel, dim3((unsigned)((hpx + NT - 1) / NT), nf), dim3(NT), 0, stream, img + f0 * px,
+                           H, W, d.Hc, d.Wc, clip, half);
+        EVR_LAUNCH_CHECK();
+        hipLaunchKernelGGL((niqe_block_kernel<BLK, float>), dim3(d.nb, nf), dim3(NT), 0, stream, img + f0 * px,
+                           (const double*)nullptr, H, W, d.Hc, d.Wc, clip, d.nbx, h->taps, (const double*)h->d_table, cfeat,
+                           sharp + (size_t)f0 * d.nb);
+        EVR_LAUNCH_CHECK();
+        hipLaunchKernelGGL((niqe_block_kernel<BLK / 2, double>), dim3(d.nb, nf), dim3(NT), 0, stream, (const float*)nullptr,
+                           (const double*)half, H, W, Hh, Wh, clip, d.nbx, h->taps, (const double*)h->d_table, cfeat,
+                           (double*)nullptr);
+        EVR_LAUNCH_CHECK();
+        return EVR_OK;
+    });
+    if (run != EVR_OK) return run;
     if (scores) {
         hipLaunchKernelGGL(niqe_score_kernel, dim3(n), dim3(NT), 0, stream, (const double*)feat, d.nb, (const double*)h->d_model,
                            scores);
@@ -428,19 +311,13 @@ static int niqe_run(evr_niqe* h, const float* img, int n, int H, int W, int clip
 
 extern "C" int evr_niqe_score(evr_niqe* h, const float* img, int n, int H, int W, int clip, double* out_scores,
                               void* workspace, size_t workspace_bytes, evr_stream_t stream) {
-    if (!out_scores && n > 0) {
-        evr::set_error("evr_niqe_score: null pointer");
-        return EVR_ERR_INVALID;
-    }
+    EVR_REQUIRE(out_scores || n <= 0, "evr_niqe_score: null pointer");
     return niqe_run(h, img, n, H, W, clip, out_scores, nullptr, nullptr, workspace, workspace_bytes, stream, "evr_niqe_score");
 }
 
 extern "C" int evr_niqe_features(evr_niqe* h, const float* img, int n, int H, int W, int clip, double* out_feat,
                                  double* out_sharpness, void* workspace, size_t workspace_bytes, evr_stream_t stream) {
-    if ((!out_feat || !out_sharpness) && n > 0) {
-        evr::set_error("evr_niqe_features: null pointer");
-        return EVR_ERR_INVALID;
-    }
+    EVR_REQUIRE((out_feat && out_sharpness) || n <= 0, "evr_niqe_features: null pointer");
     return niqe_run(h, img, n, H, W, clip, nullptr, out_feat, out_sharpness, workspace, workspace_bytes, stream,
                     "evr_niqe_features");
 }
@@ -476,23 +353,6 @@ __device__ __forceinline__ float load_px(const float* p, int64_t i, int clip) { 
 __device__ __forceinline__ double load_px(const double* p, int64_t i, int) { return p[i]; }
 __device__ __forceinline__ int wrap(int i, int n) { i %= n; return i < 0 ? i + n : i; }
 
-// M at one pixel from its 7x7 neighbourhood get(dy, dx), taps accumulated row by row (the oracle's order)
-template <typename Get>
-__device__ __forceinline__ double mscn_at(const Taps& taps, double centre, Get get) {
-    double mu = 0.0, s2 = 0.0;
-#pragma unroll
-    for (int dy = 0; dy < 7; ++dy) {
-#pragma unroll
-        for (int dx = 0; dx < 7; ++dx) {
-            const double v = get(dy, dx), g = taps.g[dy * 7 + dx];
-            mu = mu + g * v;
-            s2 = s2 + g * (v * v);
-        }
-    }
-    const double sigma = sqrt(fabs(s2 - mu * mu));
-    return (centre - mu) / (sigma + 1.0);
-}
-
 // One work-group per (tile, frame) at one scale.  The tile's input and a 4-pixel zero-padded halo are staged in LDS; M is
 // computed on chip for the tile plus the row above, the row below and the column to the left (the pairs' neighbours).
 // Where one of those lies outside the frame it is the wrapped row or column at the other edge, whose neighbourhood is
@@ -524,7 +384,7 @@ __global__ __launch_bounds__(NT) void brisque_stats_kernel(const T* __restrict__
         double v = 0.0;
         if (gy >= 0 && gy < Hs && gx >= 0 && gx < Ws) {
             // tile[r + dy][c + dx] holds the input at (gy + dy - 3, gx + dx - 3), zero outside the frame
-            v = mscn_at(taps, (double)tile[r + 3][c + 3], [&](int dy, int dx) { return (double)tile[r + dy][c + dx]; });
+            v = mscn_at(taps, (double)tile[r + 3][c + 3], [&](int dy, int dx) { return (double)tile[r + dy][c + dx]; }).m;
         } else if (gy >= -1 && gy <= Hs && gx >= -1 && gx < Ws) {
             // a neighbour across the frame's edge: the pixel at the other side, its zero-padded neighbourhood from memory
             const int wy = wrap(gy, Hs), wx = wrap(gx, Ws);
@@ -532,7 +392,7 @@ __global__ __launch_bounds__(NT) void brisque_stats_kernel(const T* __restrict__
                 const int yy = wy + dy - 3, xx = wx + dx - 3;
                 return (yy >= 0 && yy < Hs && xx >= 0 && xx < Ws) ? (double)load_px(img, (int64_t)yy * Ws + xx, clip) : 0.0;
             };
-            v = mscn_at(taps, get(3, 3), get);
+            v = mscn_at(taps, get(3, 3), get).m;
         }
         m[r][c] = v;
     }
@@ -554,21 +414,11 @@ __global__ __launch_bounds__(NT) void brisque_stats_kernel(const T* __restrict__
         v[3] = x * m[r + 1][c - 1];                             // (-1, 1): M(y + 1, x - 1)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const double q = v[k] * v[k];
-            if (v[k] < 0.0) { a[2 + 6 * k + 0] += q; a[2 + 6 * k + 1] += 1.0; }
-            if (v[k] > 0.0) { a[2 + 6 * k + 2] += q; a[2 + 6 * k + 3] += 1.0; }
-            a[2 + 6 * k + 4] += fabs(v[k]);
-            a[2 + 6 * k + 5] += q;
+            aggd_add(v[k], a + 2 + 6 * k);
+            a[2 + 6 * k + 5] += v[k] * v[k];
         }
     }
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < BNS; ++k) {
-        const double s = evr_wave_sum(a[k]);
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-    if (tid < BNS) part[((int64_t)f * nt + t) * BNS + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    block_totals(a, red, part + ((int64_t)f * nt + t) * BNS);
 }
 
 struct SvrParams { int nsv; double gamma, rho, lower, upper; };
@@ -608,29 +458,10 @@ __global__ __launch_bounds__(NT) void brisque_finish_kernel(const double* __rest
             rn = msq / (ma * ma);
         } else {
             const double* s = S + 2 + 6 * (j - 1);
-            ls = sqrt(s[0] / s[1]);                             // an empty side: 0/0 = NaN
-            rs = sqrt(s[2] / s[3]);
-            const double g = ls / rs;
-            const double ma = s[4] / N;
-            const double rhat = (ma * ma) / (s[5] / N);
-            rn = (rhat * (g * g * g + 1.0) * (g + 1.0)) / ((g * g + 1.0) * (g * g + 1.0));
+            const Aggd fit = aggd_ratio(s, s[5], N);
+            ls = fit.ls; rs = fit.rs; rn = fit.rn;
         }
-        int bk = 0;
-        if (!isnan(rn)) {
-            auto dist = [&](int k) { return j == 0 ? fabs(rn - RG[k]) : (R[k] - rn) * (R[k] - rn); };
-            double bd = dist(lane);
-            bk = lane;
-            for (int k = lane + 64; k < NGRID; k += 64) {
-                const double d = dist(k);
-                if (d < bd) { bd = d; bk = k; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double od = __shfl_xor(bd, o, 64);
-                const int ok = __shfl_xor(bk, o, 64);
-                if (better(od, ok, bd, bk)) { bd = od; bk = ok; }
-            }
-        }
+        const int bk = alpha_argmin(rn, [&](int k) { return j == 0 ? fabs(rn - RG[k]) : (R[k] - rn) * (R[k] - rn); });
         if (lane == 0) {
             double* o = fe + 18 * sc;
             if (j == 0) {
@@ -670,41 +501,32 @@ __global__ __launch_bounds__(NT) void brisque_finish_kernel(const double* __rest
         }
         acc = acc + coef[i] * exp(-svr.gamma * d);
     }
-    acc = evr_wave_sum(acc);
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
+    acc = block_total(acc, red);
     if (tid == 0) {
         bool nan = false;
         for (int k = 0; k < NF; ++k) nan = nan || isnan(fe[k]);
-        scores[f] = nan ? (double)NAN : (((red[0] + red[1]) + red[2]) + red[3]) - svr.rho;
+        scores[f] = nan ? (double)NAN : acc - svr.rho;
     }
 }
 
-struct BDims {
+struct BDims {                       // the half-size image and the tile counts of both scales
     int Hh, Wh, ntx1, nt1, ntx2, nt2;
-    size_t half_bytes, part1_bytes, part2_bytes;
+    BDims(int H, int W)
+        : Hh((H + 1) / 2), Wh((W + 1) / 2), ntx1((W + BT - 1) / BT), nt1(((H + BT - 1) / BT) * ntx1), ntx2((Wh + BT - 1) / BT),
+          nt2(((Hh + BT - 1) / BT) * ntx2) {}
 };
 
-BDims bdims(int n, int H, int W) {
-    BDims d;
-    d.Hh = (H + 1) / 2; d.Wh = (W + 1) / 2;
-    d.ntx1 = (W + BT - 1) / BT;
-    d.nt1 = ((H + BT - 1) / BT) * d.ntx1;
-    d.ntx2 = (d.Wh + BT - 1) / BT;
-    d.nt2 = ((d.Hh + BT - 1) / BT) * d.ntx2;
-    d.half_bytes = evr::align_up((size_t)n * d.Hh * d.Wh * sizeof(double), 256);
-    d.part1_bytes = evr::align_up((size_t)n * d.nt1 * BNS * sizeof(double), 256);
-    d.part2_bytes = evr::align_up((size_t)n * d.nt2 * BNS * sizeof(double), 256);
-    return d;
-}
+struct BrisqueWs : Carve {           // the workspace: a member takes the next region, in the members' order
+    double *half, *part1, *part2;
+    BrisqueWs(void* ws, size_t n, const BDims& d)
+        : Carve(ws), half(take<double>(n * d.Hh * d.Wh)), part1(take<double>(n * d.nt1 * BNS)),
+          part2(take<double>(n * d.nt2 * BNS)) {}
+};
 
 }  // namespace
 
-struct evr_brisque {
-    double* d_model = nullptr;   // fmin [36], fmax [36], coef [nsv], sv [nsv*36]
-    double* d_table = nullptr;   // r(alpha), alpha, sqrt(G(1/a)/G(3/a)), G(2/a)/G(1/a), GGD ratio: [5][9801]
+struct evr_brisque : evr_nss::Model {   // d_model: fmin [36], fmax [36], coef [nsv], sv [nsv*36]; d_table: [5][9801]
     SvrParams svr;
-    Taps taps;
 };
 
 extern "C" int evr_brisque_create(const double* sv, const double* coef, int nsv, double gamma, double rho, const double* fmin,
@@ -729,69 +551,46 @@ extern "C" int evr_brisque_create(const double* sv, const double* coef, int nsv,
     for (int k = 0; k < NF; ++k) { model[k] = fmin[k]; model[NF + k] = fmax[k]; }
     for (int i = 0; i < nsv; ++i) model[2 * NF + i] = coef[i];
     for (size_t i = 0; i < (size_t)nsv * NF; ++i) model[2 * NF + nsv + i] = sv[i];
-    const std::vector<double> table = alpha_table(5);
     evr_brisque* h = new (std::nothrow) evr_brisque();
     EVR_REQUIRE(h, "evr_brisque_create: out of host memory");
-    h->taps = gaussian_taps();
     h->svr = SvrParams{nsv, gamma, rho, lower, upper};
-    hipError_t e = hipMalloc((void**)&h->d_model, model.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_table, table.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(h->d_model, model.data(), model.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->d_model) (void)hipFree(h->d_model);
-        if (h->d_table) (void)hipFree(h->d_table);
-        delete h;
-        return evr::hip_fail(e, "evr_brisque_create", __FILE__, __LINE__);
-    }
-    *out = h;
-    return EVR_OK;
+    return finish_create(h, model, 5, out);
 }
 
-extern "C" int evr_brisque_destroy(evr_brisque* h) {
-    if (!h) return EVR_OK;
-    hipError_t e1 = h->d_model ? hipFree(h->d_model) : hipSuccess;
-    hipError_t e2 = h->d_table ? hipFree(h->d_table) : hipSuccess;
-    delete h;
-    EVR_HIP(e1);
-    EVR_HIP(e2);
-    return EVR_OK;
-}
+extern "C" int evr_brisque_destroy(evr_brisque* h) { return destroy(h); }
 
 extern "C" size_t evr_brisque_workspace_bytes(int n, int H, int W) {
     if (n < 0 || H < 1 || W < 1) return 0;
-    const BDims d = bdims(n, H, W);
-    return d.half_bytes + d.part1_bytes + d.part2_bytes + 256;
+    return BrisqueWs(nullptr, n, BDims(H, W)).bytes();
 }
 
 static int brisque_run(evr_brisque* h, const float* img, int n, int H, int W, int clip, double* scores, double* feat, void* ws,
                        size_t ws_bytes, evr_stream_t stream_, const char* what) {
     hipStream_t stream = (hipStream_t)stream_;
     EVR_REQUIRE(h, "%s: null handle", what);
-    EVR_REQUIRE(n >= 0 && n <= 65535 && H >= 1 && W >= 1, "%s: bad shape n=%d H=%d W=%d", what, n, H, W);
     EVR_REQUIRE((int64_t)H * W <= (int64_t)1 << 30, "%s: %d x %d frame is too large", what, H, W);
-    if (n == 0) return EVR_OK;
-    EVR_REQUIRE(img, "%s: null pointer", what);
-    const size_t need = evr_brisque_workspace_bytes(n, H, W);
-    if (!ws || ws_bytes < need) {
-        evr::set_error("%s: workspace %zu B < required %zu B", what, ws_bytes, need);
-        return EVR_ERR_WORKSPACE;
-    }
-    const BDims d = bdims(n, H, W);
-    char* p = (char*)ws;
-    double* half = (double*)p; p += d.half_bytes;
-    double* part1 = (double*)p; p += d.part1_bytes;
-    double* part2 = (double*)p;
-    hipLaunchKernelGGL(niqe_resize_kernel, dim3((unsigned)(((int64_t)d.Hh * d.Wh + NT - 1) / NT), n), dim3(NT), 0, stream, img, H,
-                       W, H, W, clip, half);
-    EVR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(brisque_stats_kernel<float>, dim3(d.nt1, n), dim3(NT), 0, stream, img, H, W, clip, d.ntx1, h->taps, part1);
-    EVR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(brisque_stats_kernel<double>, dim3(d.nt2, n), dim3(NT), 0, stream, (const double*)half, d.Hh, d.Wh, clip,
-                       d.ntx2, h->taps, part2);
-    EVR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(brisque_finish_kernel, dim3(n), dim3(NT), 0, stream, (const double*)part1, d.nt1, H * W,
-                       (const double*)part2, d.nt2, d.Hh * d.Wh, (const double*)h->d_table, (const double*)h->d_model, h->svr,
+    const int rc = check_run(what, 0, n, H, W, img != nullptr);
+    if (rc != EVR_OK || n == 0) return rc;
+    EVR_REQUIRE_WORKSPACE(what, ws, ws_bytes, evr_brisque_workspace_bytes(n, H, W));
+    const BDims d(H, W);
+    const BrisqueWs w(ws, n, d);
+    const size_t px = (size_t)H * W, hpx = (size_t)d.Hh * d.Wh;
+    const int run = for_frame_chunks(n, [&](int f0, int nf) -> int {
+        double* half = w.half + f0 * hpx;
+        hipLaunchKernelGGL(niqe_resize_kernel, dim3((unsigned)((hpx + NT - 1) / NT), nf), dim3(NT), 0, stream, img + f0 * px,
+                           H, W, H, W, clip, half);
+        EVR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(brisque_stats_kernel<float>, dim3(d.nt1, nf), dim3(NT), 0, stream, img + f0 * px, H, W, clip, d.ntx1,
+                           h->taps, w.part1 + (size_t)f0 * d.nt1 * BNS);
+        EVR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(brisque_stats_kernel<double>, dim3(d.nt2, nf), dim3(NT), 0, stream, (const double*)half, d.Hh, d.Wh,
+                           clip, d.ntx2, h->taps, w.part2 + (size_t)f0 * d.nt2 * BNS);
+        EVR_LAUNCH_CHECK();
+        return EVR_OK;
+    });
+    if (run != EVR_OK) return run;
+    hipLaunchKernelGGL(brisque_finish_kernel, dim3(n), dim3(NT), 0, stream, (const double*)w.part1, d.nt1, H * W,
+                       (const double*)w.part2, d.nt2, d.Hh * d.Wh, (const double*)h->d_table, (const double*)h->d_model, h->svr,
                        feat, scores);
     EVR_LAUNCH_CHECK();
     return EVR_OK;
@@ -801,19 +600,13 @@ extern "C" int evr_brisque_score(evr_brisque* h, const float* img, int n, int H,
                                  void* workspace, size_t workspace_bytes, evr_stream_t stream) {
     EVR_REQUIRE(h, "evr_brisque_score: null handle");
     EVR_REQUIRE(h->svr.nsv > 0, "evr_brisque_score: a features-only handle (no support vectors) gives no score");
-    if (!out_scores && n > 0) {
-        evr::set_error("evr_brisque_score: null pointer");
-        return EVR_ERR_INVALID;
-    }
+    EVR_REQUIRE(out_scores || n <= 0, "evr_brisque_score: null pointer");
     return brisque_run(h, img, n, H, W, clip, out_scores, nullptr, workspace, workspace_bytes, stream, "evr_brisque_score");
 }
 
 extern "C" int evr_brisque_features(evr_brisque* h, const float* img, int n, int H, int W, int clip, double* out_feat,
                                     void* workspace, size_t workspace_bytes, evr_stream_t stream) {
-    if (!out_feat && n > 0) {
-        evr::set_error("evr_brisque_features: null pointer");
-        return EVR_ERR_INVALID;
-    }
+    EVR_REQUIRE(out_feat || n <= 0, "evr_brisque_features: null pointer");
     return brisque_run(h, img, n, H, W, clip, nullptr, out_feat, workspace, workspace_bytes, stream, "evr_brisque_features");
 }
 
@@ -898,10 +691,7 @@ __global__ __launch_bounds__(NT) void piqe_block_kernel(const float* __restrict_
             }
         }
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const double sigma = sqrt(fabs(s2[p] - mu[p] * mu[p]));
-            m[r][c + p] = (centre[p] - mu[p]) / (sigma + 1.0);
-        }
+        for (int p = 0; p < 4; ++p) m[r][c + p] = mscn_close(centre[p], mu[p], s2[p]).m;
     }
     __syncthreads();
 
@@ -975,36 +765,26 @@ __global__ __launch_bounds__(NT) void piqe_finish_kernel(const double* __restric
     int c = 0;
     for (int b = tid; b < nb; b += NT) {
         s += contribution[(int64_t)f * nb + b];
-        c += flags[(int64_t)f * nb + b] & PIQE_ACTIVE;
+        c += wave_votes(flags[(int64_t)f * nb + b] & PIQE_ACTIVE);
     }
-    s = evr_wave_sum(s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-    if ((tid & 63) == 0) { red[tid >> 6] = s; cnt[tid >> 6] = c; }
-    __syncthreads();
-    if (tid == 0) {
-        const double sum = ((red[0] + red[1]) + red[2]) + red[3];
-        const int active = ((cnt[0] + cnt[1]) + cnt[2]) + cnt[3];
-        scores[f] = 100.0 * ((sum + 1.0) / (1.0 + (double)active));
-    }
+    const double sum = block_total(s, red);
+    const int active = block_count(c, cnt);
+    if (tid == 0) scores[f] = 100.0 * ((sum + 1.0) / (1.0 + (double)active));
 }
 
-struct PDims {
+struct PDims {                       // the block and tile counts
     int nby, nbx, nb, ntx, nt;
-    size_t var_bytes, contrib_bytes, flag_bytes;
+    PDims(int H, int W)
+        : nby((H + PB - 1) / PB), nbx((W + PB - 1) / PB), nb(nby * nbx), ntx((nbx + PTB - 1) / PTB),
+          nt(((nby + PTB - 1) / PTB) * ntx) {}
 };
 
-PDims pdims(int n, int H, int W) {
-    PDims d;
-    d.nby = (H + PB - 1) / PB; d.nbx = (W + PB - 1) / PB;
-    d.nb = d.nby * d.nbx;
-    d.ntx = (d.nbx + PTB - 1) / PTB;
-    d.nt = ((d.nby + PTB - 1) / PTB) * d.ntx;
-    d.var_bytes = evr::align_up((size_t)n * d.nb * sizeof(double), 256);
-    d.contrib_bytes = d.var_bytes;
-    d.flag_bytes = evr::align_up((size_t)n * d.nb, 256);
-    return d;
-}
+struct PiqeWs : Carve {              // the workspace: a member takes the next region, in the members' order
+    double *var, *contrib;
+    unsigned char* flags;
+    PiqeWs(void* ws, size_t n, const PDims& d)
+        : Carve(ws), var(take<double>(n * d.nb)), contrib(take<double>(n * d.nb)), flags(take<unsigned char>(n * d.nb)) {}
+};
 
 const Taps& piqe_taps() {
     static const Taps t = gaussian_taps();
@@ -1015,34 +795,31 @@ const Taps& piqe_taps() {
 
 extern "C" size_t evr_piqe_workspace_bytes(int n, int H, int W) {
     if (n < 1 || H < 1 || W < 1) return 0;
-    const PDims d = pdims(n, H, W);
-    return d.var_bytes + d.contrib_bytes + d.flag_bytes + 256;
+    return PiqeWs(nullptr, n, PDims(H, W)).bytes();
 }
 
 static int piqe_run(const float* img, int n, int H, int W, int clip, double* scores, double* out_var, unsigned char* out_flags,
                     void* ws, size_t ws_bytes, evr_stream_t stream_, const char* what) {
     hipStream_t stream = (hipStream_t)stream_;
-    EVR_REQUIRE(n >= 1 && n <= 65535 && H >= 1 && W >= 1, "%s: bad shape n=%d H=%d W=%d", what, n, H, W);
     EVR_REQUIRE((int64_t)H * W <= (int64_t)1 << 30, "%s: %d x %d frame is too large", what, H, W);
-    EVR_REQUIRE(img && (scores || (out_var && out_flags)), "%s: null pointer", what);
-    const size_t need = evr_piqe_workspace_bytes(n, H, W);
-    if (!ws || ws_bytes < need) {
-        evr::set_error("%s: workspace %zu B < required %zu B", what, ws_bytes, need);
-        return EVR_ERR_WORKSPACE;
-    }
-    const PDims d = pdims(n, H, W);
-    char* p = (char*)ws;
-    double* var = (double*)p; p += d.var_bytes;
-    double* contrib = (double*)p; p += d.contrib_bytes;
-    unsigned char* flags = (unsigned char*)p;
-    if (out_var) var = out_var;
-    if (out_flags) flags = out_flags;
-    hipLaunchKernelGGL(piqe_block_kernel, dim3(d.nt, n), dim3(NT), 0, stream, img, H, W, clip, d.nby, d.nbx, d.ntx, piqe_taps(), var,
-                       contrib, flags);
-    EVR_LAUNCH_CHECK();
+    const int rc = check_run(what, 1, n, H, W, img && (scores || (out_var && out_flags)));
+    if (rc != EVR_OK) return rc;
+    EVR_REQUIRE_WORKSPACE(what, ws, ws_bytes, evr_piqe_workspace_bytes(n, H, W));
+    const PDims d(H, W);
+    const PiqeWs w(ws, n, d);
+    double* var = out_var ? out_var : w.var;
+    unsigned char* flags = out_flags ? out_flags : w.flags;
+    const int run = for_frame_chunks(n, [&](int f0, int nf) -> int {
+        const size_t o = (size_t)f0 * d.nb;
+        hipLaunchKernelGGL(piqe_block_kernel, dim3(d.nt, nf), dim3(NT), 0, stream, img + (size_t)f0 * H * W, H, W, clip, d.nby,
+                           d.nbx, d.ntx, piqe_taps(), var + o, w.contrib + o, flags + o);
+        EVR_LAUNCH_CHECK();
+        return EVR_OK;
+    });
+    if (run != EVR_OK) return run;
     if (scores) {
-        hipLaunchKernelGGL(piqe_finish_kernel, dim3(n), dim3(NT), 0, stream, (const double*)contrib, (const unsigned char*)flags,
-                           d.nb, scores);
+        hipLaunchKernelGGL(piqe_finish_kernel, dim3(n), dim3(NT), 0, stream, (const double*)w.contrib,
+                           (const unsigned char*)flags, d.nb, scores);
         EVR_LAUNCH_CHECK();
     }
     return EVR_OK;

@@ -384,10 +384,7 @@ extern "C" int evr_event_tensor_normalize(float* vox, int n, int B, int H, int W
     int n_part = 1;
     if (!stats) {
         const size_t need = (size_t)n * NRM_BLOCKS * 3 * sizeof(double);
-        if (!workspace || workspace_bytes < need) {
-            evr::set_error("evr_event_tensor_normalize: workspace %zu B < required %zu B", workspace_bytes, need);
-            return EVR_ERR_WORKSPACE;
-        }
+        EVR_REQUIRE_WORKSPACE("evr_event_tensor_normalize", workspace, workspace_bytes, need);
         hipLaunchKernelGGL(nrm_partial_kernel, dim3(NRM_BLOCKS, n), dim3(256), 0, stream, vox, (double*)workspace, vol);
         EVR_LAUNCH_CHECK();
         stats = (const double*)workspace;
@@ -415,10 +412,7 @@ extern "C" int evr_percentile_normalize(float* img, int n, int H, int W, float q
     if (n == 0) return EVR_OK;
     EVR_REQUIRE(img != nullptr, "evr_percentile_normalize: null image");
     const size_t need = evr_percentile_normalize_workspace_bytes(n, H, W);
-    if (!workspace || workspace_bytes < need) {
-        evr::set_error("evr_percentile_normalize: workspace %zu B < required %zu B", workspace_bytes, need);
-        return EVR_ERR_WORKSPACE;
-    }
+    EVR_REQUIRE_WORKSPACE("evr_percentile_normalize", workspace, workspace_bytes, need);
     const int px = H * W;
     if (do_exp) {
         const int64_t total = (int64_t)n * px;

@@ -43,6 +43,44 @@ def _as_frames(img):
     return v.contiguous()
 
 
+def _new(v, *shape, dtype=torch.float64):
+    """An output of one entry [*shape] per frame of v."""
+    return torch.empty((v.shape[0],) + shape, dtype=dtype, device=v.device)
+
+
+class NoRefMetric(Workspace):
+    """What the no-reference metrics share: the library, the handle where the metric has one (`_destroy` names the entry
+    point that frees it), the workspace kept between calls, and one checked call of a named entry point:
+    entry([handle,] frames, n, H, W, clip, *outs, workspace, bytes, stream)."""
+    _score = None               # the scoring entry point's name
+    _destroy = None
+    handle = None
+
+    def __init__(self):
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.ws = None
+
+    def _run(self, entry, v, clip, *outs):
+        n, H, W = v.shape
+        ws = self._workspace(n, H, W, v.device)
+        head = (self.handle,) if self._destroy else ()
+        _lib.check(getattr(self.lib, entry)(*head, _lib.ptr(v), n, H, W, 1 if clip else 0, *map(_lib.ptr, outs), _lib.ptr(ws),
+                                            ws.numel(), _lib.stream_ptr()), entry)
+        return outs[0] if len(outs) == 1 else outs
+
+    def __call__(self, img, clip=True, out=None):
+        v = _as_frames(img)
+        return self._run(self._score, v, clip, _new(v) if out is None else out)
+
+    def __del__(self):
+        try:
+            if self._destroy and self.handle is not None:
+                getattr(self.lib, self._destroy)(self.handle); self.handle = None
+        except Exception:
+            pass
+
+
 def check_model(mu, cov):
     """(mu [36], cov [36,36]) as fp64 arrays; raises ValueError unless cov is symmetric positive definite."""
     mu = np.asarray(mu, dtype=np.float64).reshape(-1)
@@ -80,14 +118,13 @@ def save_niqe_model(path, mu, cov, source):
     np.savez(path, mu=mu, cov=cov, source=np.array(source))
 
 
-class NIQE(Workspace):
+class NIQE(NoRefMetric):
     """NIQE scores of cuda fp32 frames [n,H,W] -> cuda fp64 [n] (NaN for a frame without a whole 96x96 block).
     `model`: a dict with mu / cov (load_niqe_model) or a path.  The workspace is kept between calls."""
-    _workspace_bytes = 'evr_niqe_workspace_bytes'
+    _workspace_bytes, _score, _destroy = 'evr_niqe_workspace_bytes', 'evr_niqe_score', 'evr_niqe_destroy'
 
     def __init__(self, model):
-        _lib.require_gpu()
-        self.lib = _lib.load()
+        super().__init__()
         if isinstance(model, (str, os.PathLike)):
             model = load_niqe_model(os.fspath(model))
         self.mu, self.cov = check_model(model['mu'], model['cov'])
@@ -96,36 +133,12 @@ class NIQE(Workspace):
         _lib.check(self.lib.evr_niqe_create(self.mu.ctypes.data_as(ctypes.c_void_p), self.cov.ctypes.data_as(ctypes.c_void_p),
                                             ctypes.byref(h)), 'evr_niqe_create')
         self.handle = h
-        self.ws = None
-
-    def __call__(self, img, clip=True, out=None):
-        v = _as_frames(img)
-        n, H, W = v.shape
-        if out is None:
-            out = torch.empty(n, dtype=torch.float64, device=v.device)
-        ws = self._workspace(n, H, W, v.device)
-        _lib.check(self.lib.evr_niqe_score(self.handle, _lib.ptr(v), n, H, W, 1 if clip else 0, _lib.ptr(out), _lib.ptr(ws),
-                                           ws.numel(), _lib.stream_ptr()), 'evr_niqe_score')
-        return out
 
     def features(self, img, clip=True):
         """-> (feat cuda fp64 [n, nb, 36], sharpness cuda fp64 [n, nb]); blocks in raster order."""
         v = _as_frames(img)
-        n, H, W = v.shape
-        nb = (H // BLOCK) * (W // BLOCK)
-        feat = torch.empty((n, nb, NUM_FEATURES), dtype=torch.float64, device=v.device)
-        sharp = torch.empty((n, nb), dtype=torch.float64, device=v.device)
-        ws = self._workspace(n, H, W, v.device)
-        _lib.check(self.lib.evr_niqe_features(self.handle, _lib.ptr(v), n, H, W, 1 if clip else 0, _lib.ptr(feat), _lib.ptr(sharp),
-                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), 'evr_niqe_features')
-        return feat, sharp
-
-    def __del__(self):
-        try:
-            if self.handle is not None:
-                self.lib.evr_niqe_destroy(self.handle); self.handle = None
-        except Exception:
-            pass
+        nb = (v.shape[1] // BLOCK) * (v.shape[2] // BLOCK)
+        return self._run('evr_niqe_features', v, clip, _new(v, nb, NUM_FEATURES), _new(v, nb))
 
 
 _feature_handle = []
@@ -298,15 +311,14 @@ def save_brisque_model(path, sv, coef, gamma, rho, fmin, fmax, lower, upper, sou
     np.savez(path, **m, source=np.array(source))
 
 
-class BRISQUE(Workspace):
+class BRISQUE(NoRefMetric):
     """BRISQUE scores of cuda fp32 frames [n,H,W] -> cuda fp64 [n] (NaN for a frame with a NaN feature, e.g. a flat one).
     `model`: a dict as load_brisque_model returns, or a path.  A model without support vectors gives features only.  The
     workspace is kept between calls."""
-    _workspace_bytes = 'evr_brisque_workspace_bytes'
+    _workspace_bytes, _score, _destroy = 'evr_brisque_workspace_bytes', 'evr_brisque_score', 'evr_brisque_destroy'
 
     def __init__(self, model):
-        _lib.require_gpu()
-        self.lib = _lib.load()
+        super().__init__()
         if isinstance(model, (str, os.PathLike)):
             model = load_brisque_model(os.fspath(model))
         self.model = check_brisque_model(*(model[k] for k in ('sv', 'coef', 'gamma', 'rho', 'fmin', 'fmax', 'lower', 'upper')))
@@ -317,34 +329,11 @@ class BRISQUE(Workspace):
         _lib.check(self.lib.evr_brisque_create(vp(m['sv']), vp(m['coef']), len(m['coef']), m['gamma'], m['rho'], vp(m['fmin']),
                                                vp(m['fmax']), m['lower'], m['upper'], ctypes.byref(h)), 'evr_brisque_create')
         self.handle = h
-        self.ws = None
-
-    def __call__(self, img, clip=True, out=None):
-        v = _as_frames(img)
-        n, H, W = v.shape
-        if out is None:
-            out = torch.empty(n, dtype=torch.float64, device=v.device)
-        ws = self._workspace(n, H, W, v.device)
-        _lib.check(self.lib.evr_brisque_score(self.handle, _lib.ptr(v), n, H, W, 1 if clip else 0, _lib.ptr(out), _lib.ptr(ws),
-                                              ws.numel(), _lib.stream_ptr()), 'evr_brisque_score')
-        return out
 
     def features(self, img, clip=True):
         """-> cuda fp64 [n, 36]: the 18 full-size features, then the 18 half-size ones (unscaled)."""
         v = _as_frames(img)
-        n, H, W = v.shape
-        feat = torch.empty((n, NUM_FEATURES), dtype=torch.float64, device=v.device)
-        ws = self._workspace(n, H, W, v.device)
-        _lib.check(self.lib.evr_brisque_features(self.handle, _lib.ptr(v), n, H, W, 1 if clip else 0, _lib.ptr(feat),
-                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), 'evr_brisque_features')
-        return feat
-
-    def __del__(self):
-        try:
-            if self.handle is not None:
-                self.lib.evr_brisque_destroy(self.handle); self.handle = None
-        except Exception:
-            pass
+        return self._run('evr_brisque_features', v, clip, _new(v, NUM_FEATURES))
 
 
 _brisque_feature_handle = []
@@ -363,38 +352,17 @@ PIQE_BLOCK = 16
 PIQE_ACTIVE, PIQE_WHSA, PIQE_WNC = 1, 2, 4      # the bits of a block's flag byte
 
 
-class PIQE(Workspace):
+class PIQE(NoRefMetric):
     """PIQE scores of cuda fp32 frames [n,H,W] -> cuda fp64 [n] (100 for a frame without an active block, e.g. a constant
-    one).  No model: the metric is training-free.  The workspace is kept between calls."""
-    _workspace_bytes = 'evr_piqe_workspace_bytes'
-
-    def __init__(self):
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.ws = None
-
-    def __call__(self, img, clip=True, out=None):
-        v = _as_frames(img)
-        n, H, W = v.shape
-        if out is None:
-            out = torch.empty(n, dtype=torch.float64, device=v.device)
-        ws = self._workspace(n, H, W, v.device)
-        _lib.check(self.lib.evr_piqe_score(_lib.ptr(v), n, H, W, 1 if clip else 0, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                           _lib.stream_ptr()), 'evr_piqe_score')
-        return out
+    one).  No model, hence no handle: the metric is training-free.  The workspace is kept between calls."""
+    _workspace_bytes, _score = 'evr_piqe_workspace_bytes', 'evr_piqe_score'
 
     def blocks(self, img, clip=True):
         """-> (var cuda fp64 [n, ceil(H/16), ceil(W/16)], flags cuda uint8 of the same shape: PIQE_ACTIVE | PIQE_WHSA |
         PIQE_WNC).  MATLAB's activityMask / noticeableArtifactsMask / noiseMask are these bits spread over 16x16 pixels."""
         v = _as_frames(img)
-        n, H, W = v.shape
-        shape = (n, -(-H // PIQE_BLOCK), -(-W // PIQE_BLOCK))
-        var = torch.empty(shape, dtype=torch.float64, device=v.device)
-        flags = torch.empty(shape, dtype=torch.uint8, device=v.device)
-        ws = self._workspace(n, H, W, v.device)
-        _lib.check(self.lib.evr_piqe_blocks(_lib.ptr(v), n, H, W, 1 if clip else 0, _lib.ptr(var), _lib.ptr(flags), _lib.ptr(ws),
-                                            ws.numel(), _lib.stream_ptr()), 'evr_piqe_blocks')
-        return var, flags
+        shape = (-(-v.shape[1] // PIQE_BLOCK), -(-v.shape[2] // PIQE_BLOCK))
+        return self._run('evr_piqe_blocks', v, clip, _new(v, *shape), _new(v, *shape, dtype=torch.uint8))
 
 
 def _sequence_frames(path, device, chunk=64):

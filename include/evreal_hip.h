@@ -381,9 +381,10 @@ int evr_dists_saturation(evr_dists* m, int64_t* count, evr_stream_t stream);
  * evr_niqe_features: img [n,H,W] fp32 -> out_feat double [n, nb, 36] (block k in raster order of the (H/96) x (W/96)
  *   blocks: its 18 full-size features, then its 18 half-size ones) and out_sharpness double [n, nb] (the block's mean
  *   full-size sigma: estimatemodelparam.m's sharpness).
- * Four launches per call whatever n (three for features), no host synchronisation; results are bitwise independent
- * of n and of a frame's position in the batch.  workspace: evr_niqe_workspace_bytes(n, H, W); at most 8192 blocks
- * per frame.  One handle may serve several streams at once (it holds no per-call state).
+ * Four launches per call (three for features) up to 65535 frames, three more per further 65535; no host
+ * synchronisation; results are bitwise independent of n and of a frame's position in the batch.  workspace:
+ * evr_niqe_workspace_bytes(n, H, W); any n; at most 8192 blocks per frame.  One handle may serve several streams at
+ * once (it holds no per-call state).
  */
 typedef struct evr_niqe evr_niqe;
 int evr_niqe_create(const double* mu, const double* cov, evr_niqe** out);
@@ -407,9 +408,9 @@ int evr_niqe_features(evr_niqe* h, const float* img, int n, int H, int W, int cl
  *   features-only handle (sv and coef may be NULL); evr_brisque_score refuses it.
  * evr_brisque_score: img [n,H,W] fp32 -> out_scores double [n].
  * evr_brisque_features: img [n,H,W] fp32 -> out_feat double [n, 36] (the 18 full-size features, then the 18 half-size).
- * Four launches per call whatever n, no host synchronisation; results are bitwise independent of n and of a frame's
- * position in the batch.  workspace: evr_brisque_workspace_bytes(n, H, W); n <= 65535.  One handle may serve several
- * streams at once.
+ * Four launches per call up to 65535 frames, three more per further 65535; no host synchronisation; results are
+ * bitwise independent of n and of a frame's position in the batch.  workspace: evr_brisque_workspace_bytes(n, H, W);
+ * any n.  One handle may serve several streams at once.
  */
 typedef struct evr_brisque evr_brisque;
 int evr_brisque_create(const double* sv, const double* coef, int nsv, double gamma, double rho, const double* fmin,
@@ -434,10 +435,10 @@ int evr_brisque_features(evr_brisque* h, const float* img, int n, int H, int W, 
  * evr_piqe_blocks: img [n,H,W] fp32 -> out_var double [n, ceil(H/16), ceil(W/16)] (the block variances) and out_flags,
  *   one byte per block: bit 0 active, bit 1 noticeable artefacts, bit 2 noise (MATLAB's activityMask,
  *   noticeableArtifactsMask and noiseMask are these bits spread over the block's pixels).
- * Two launches per call whatever n (evr_piqe_blocks: one), no host synchronisation; results are bitwise independent of n
- * and of a frame's position in the batch.  All pointers are caller-owned device memory.  Refused before any launch: a
- * null pointer, n <= 0 or n > 65535, H or W < 1, a workspace shorter than evr_piqe_workspace_bytes(n, H, W) (which is 0
- * for such a shape).
+ * Two launches per call (evr_piqe_blocks: one) up to 65535 frames, one more per further 65535; no host synchronisation;
+ * results are bitwise independent of n and of a frame's position in the batch.  All pointers are caller-owned device
+ * memory.  Refused before any launch: a null pointer, n <= 0, H or W < 1, a workspace shorter than
+ * evr_piqe_workspace_bytes(n, H, W) (which is 0 for such a shape).
  */
 size_t evr_piqe_workspace_bytes(int n, int H, int W);
 int evr_piqe_score(const float* img, int n, int H, int W, int clip, double* out_scores, void* workspace,

@@ -109,6 +109,18 @@ def test_flat_frame_is_nan_and_leaves_its_neighbours_alone(brisque):
     assert np.any(np.isnan(brisque.features(_cuda(frames[3:4])).cpu().numpy()))
 
 
+def test_more_frames_than_one_grid_axis_holds(brisque):
+    """Frames ride the grid's y axis, chunked at 65535: 65537 frames against the first and the last 100 computed alone."""
+    n = 65537
+    x = torch.rand((n, 16, 16), generator=torch.Generator(device='cuda').manual_seed(65537), device='cuda')
+    full, full_f = brisque(x), brisque.features(x)
+    for sl in (slice(0, 100), slice(n - 100, n)):
+        alone, alone_f = brisque(x[sl].contiguous()), brisque.features(x[sl].contiguous())
+        assert bool(torch.isfinite(alone).any())                    # the comparison does not pass on NaN alone
+        assert torch.equal(alone.view(torch.int64), full[sl].view(torch.int64))
+        assert torch.equal(alone_f.view(torch.int64), full_f[sl].view(torch.int64))
+
+
 def test_workspace_and_argument_refusals(brisque, model):
     from evreal_amd import lib as L
     from evreal_amd.nriqa import BRISQUE, brisque_features

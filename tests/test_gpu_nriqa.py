@@ -99,6 +99,79 @@ def test_bitwise_independent_of_batch_and_position(niqe):
     assert torch.equal(f1[0].view(torch.int64), f64[5].view(torch.int64)) and torch.equal(s1[0], s64[5])
 
 
+def test_workspace_and_argument_refusals(niqe):
+    import ctypes
+    from evreal_amd import lib as L
+    lib = L.load()
+    x = torch.from_numpy(np.stack([_frame(100, 200, s) for s in range(3)])).cuda()
+    out = torch.empty(3, dtype=torch.float64, device='cuda')
+    need = int(lib.evr_niqe_workspace_bytes(3, 100, 200))
+    assert need > 0 and lib.evr_niqe_workspace_bytes(-1, 100, 200) == 0 and lib.evr_niqe_workspace_bytes(3, 0, 200) == 0
+    ws = torch.empty(need, dtype=torch.uint8, device='cuda')
+    st = L.stream_ptr()
+    assert lib.evr_niqe_score(niqe.handle, L.ptr(x), 3, 100, 200, 1, L.ptr(out), L.ptr(ws), need - 1, st) == -3
+    assert lib.evr_niqe_score(niqe.handle, L.ptr(x), 3, 100, 200, 1, L.ptr(out), None, need, st) == -3
+    assert lib.evr_niqe_score(niqe.handle, L.ptr(x), 3, 100, 200, 1, None, L.ptr(ws), need, st) == -1
+    assert lib.evr_niqe_score(niqe.handle, L.ptr(x), 3, 0, 200, 1, L.ptr(out), L.ptr(ws), need, st) == -1
+    assert lib.evr_niqe_score(None, L.ptr(x), 3, 100, 200, 1, L.ptr(out), L.ptr(ws), need, st) == -1
+    assert lib.evr_niqe_score(niqe.handle, L.ptr(x), 3, 100, 200, 1, L.ptr(out), L.ptr(ws), need, st) == 0
+    torch.cuda.synchronize()
+    assert np.all(np.isfinite(out.cpu().numpy()))
+
+    def create(mu, cov):
+        mu, cov = np.ascontiguousarray(mu, dtype=np.float64), np.ascontiguousarray(cov, dtype=np.float64)
+        h = ctypes.c_void_p()
+        rc = lib.evr_niqe_create(mu.ctypes.data_as(ctypes.c_void_p), cov.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h))
+        if rc == 0:
+            lib.evr_niqe_destroy(h)
+        return rc
+
+    m = _model()
+    assert create(m['mu'], m['cov']) == 0
+    mu = m['mu'].copy()
+    mu[7] = np.inf
+    assert create(mu, m['cov']) == -1
+    cov = m['cov'].copy()
+    cov[2, 5] += 1e-6                                    # asymmetric
+    assert create(m['mu'], cov) == -1
+    shift = 2.0 * np.linalg.eigvalsh(m['cov'])[0]
+    assert create(m['mu'], m['cov'] - shift * np.eye(36)) == -1                  # symmetric, its smallest eigenvalue < 0
+
+
+def test_more_frames_than_one_grid_axis_holds(niqe):
+    """Frames ride the grid's y axis, chunked at 65535: 65537 frames of one block against the first and the last 100 computed
+    alone.  One block gives 36 finite features and no covariance: every score is NaN, from a score kernel of 65537 groups."""
+    n = 65537
+    x = torch.rand((n, 96, 96), generator=torch.Generator(device='cuda').manual_seed(65537), device='cuda')
+    feat, sharp = niqe.features(x)
+    assert feat.shape == (n, 1, 36) and sharp.shape == (n, 1)
+    for sl in (slice(0, 100), slice(n - 100, n)):
+        f, s = niqe.features(x[sl].contiguous())
+        assert bool(torch.isfinite(f).all()) and bool(torch.isfinite(s).all())
+        assert torch.equal(f.view(torch.int64), feat[sl].view(torch.int64))
+        assert torch.equal(s.view(torch.int64), sharp[sl].view(torch.int64))
+    assert bool(torch.isnan(niqe(x)).all())
+
+
+def test_score_counts_the_complete_rows_of_more_blocks_than_threads(niqe):
+    """17 x 16 = 272 blocks: the score kernel's 256 threads walk the rows in two steps, the second a partial one, and flat
+    blocks leave incomplete rows in both.  The score must be the oracle's from the kernel's own features: a wrong count of
+    the complete rows scales the covariance by (m' - 1)/(m - 1) and moves the score far beyond 1e-7."""
+    v = _frame(17 * 96, 16 * 96, 3)
+    # flat beyond the blocks by 20 pixels: the 7x7 window and the resize taps of the half-size scale stay inside
+    v[96 - 20:192 + 20, 96 - 20:384 + 20] = 0.3          # blocks 17 .. 19
+    v[16 * 96 - 20:, 3 * 96 - 20:5 * 96 + 20] = 0.6      # blocks 259, 260: the second step
+    x = torch.from_numpy(v[None]).cuda()
+    feat, _ = niqe.features(x)
+    rows = feat[0].cpu().numpy()
+    incomplete = np.flatnonzero(np.isnan(rows).any(axis=1))
+    assert rows.shape == (272, 36) and set(incomplete) >= {17, 18, 19, 259, 260}
+    m = _model()
+    want = R.score_features(rows, m['mu'], m['cov'])
+    assert math.isfinite(want)
+    np.testing.assert_allclose(float(niqe(x)[0]), want, rtol=1e-7)
+
+
 def test_fit_on_gpu_matches_the_oracle_fit():
     from evreal_amd.nriqa import fit_niqe_model
     frames = [_frame(288, 384, s) for s in range(6)]

@@ -94,6 +94,20 @@ def test_constant_and_nan_frames_leave_their_neighbours_alone(piqe):
     assert bad.any() and not bad.all() and not flags[0][bad].any()          # comparisons with NaN are false: inactive blocks
 
 
+def test_more_frames_than_one_grid_axis_holds(piqe):
+    """Frames ride the grid's y axis, chunked at 65535: 65537 one-block frames against the first and the last 100 computed
+    alone."""
+    n = 65537
+    x = torch.rand((n, 16, 16), generator=torch.Generator(device='cuda').manual_seed(65537), device='cuda')
+    full = piqe(x)
+    var, flags = piqe.blocks(x)
+    assert bool(torch.isfinite(full).all())
+    for sl in (slice(0, 100), slice(n - 100, n)):
+        assert torch.equal(piqe(x[sl].contiguous()).view(torch.int64), full[sl].view(torch.int64))
+        v, f = piqe.blocks(x[sl].contiguous())
+        assert torch.equal(v.view(torch.int64), var[sl].view(torch.int64)) and torch.equal(f, flags[sl])
+
+
 def test_workspace_and_argument_refusals(piqe):
     from evreal_amd import lib as L
     lib = L.load()
