@@ -14,6 +14,7 @@
 // scales 2^-12 and 2^-e are the instruction's E8M0 operands) -- 2/3 of the matrix cycles of three bf16 products.
 #pragma once
 #include "common.h"
+#include "knobs.h"
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -404,22 +405,15 @@ inline int pack_p6_weights(std::vector<float>& w) {
 //      tensors are all written as whole groups by matrix-core epilogues; evr_model_create narrows it to mode 2 for the others, LPIPS then runs mode 2;
 //   2  split f16 + MX-fp8 corrections on PACKED tensors (EVR_ARITH=mx: everywhere);
 //   0  exact fp32 MFMA on PLAIN tensors (EVR_FP32=1 or EVR_ARITH=fp32)
-inline int arith_mode() {
-    if (getenv("EVR_FP32")) return 0;
-    const char* e = getenv("EVR_ARITH");
-    if (!e || !*e || !strcmp(e, "h3")) return 3;
-    if (!strcmp(e, "mx6")) return 4;
-    if (!strcmp(e, "mx")) return 2;
-    if (!strcmp(e, "fp32")) return 0;
-    return 3;
-}
+// (the process's mode: LibKnobs::arith, read once; a model may carry its own -- evr_model_desc::reserved[2])
+inline int arith_mode() { return lib_knobs().arith; }
 inline bool use_split_mode() { return arith_mode() != 0; }
 // value of the `packed` flags for tensors of a mode: 0 PLAIN, 1 PACKED (f16 | fp8 | fp8), 2 H2, 3 P6
 inline int packed_fmt(int mode) { return mode == 3 ? 2 : (mode == 2 ? 1 : (mode == 4 ? 3 : 0)); }
 // weights (K contiguous, multiples of 16) -> the mode's split layout in place; returns the tensor exponent
 inline int pack_weights_for(int mode, std::vector<float>& w) { return mode == 3 ? pack_h2_weights(w) : (mode == 4 ? pack_p6_weights(w) : pack_split_weights(w)); }
 // (A/B switch for the whole-group PACKED stores)
-inline int use_group_store() { const char* e = getenv("EVR_GROUP_STORE"); return e ? atoi(e) : 1; }
+inline int use_group_store() { return lib_knobs().group_store; }
 // ---- what the kernels of conv.hip expect of a convolution prepared for `mode` whose weights went through pack_weights_for
 // (tensor exponent e_w): every host that prepares one -- model.cpp, the LPIPS backbones -- takes it from here.
 // Mode 3 accumulates products scaled by 2^(e_w + H2_ACT_EXP), mode 4 by 2^e_w (weights scaled, activations unscaled): the
@@ -462,7 +456,7 @@ inline void set_wino_grid(ConvArgs& a) {
     a.wino_th = (gh + 1) / 2; a.wino_tw = (gw + 1) / 2;
     fastdiv_magic((unsigned)(a.wino_th * a.wino_tw), &a.wdiv_t_mul, &a.wdiv_t_sh);
     fastdiv_magic((unsigned)a.wino_tw, &a.wdiv_tw_mul, &a.wdiv_tw_sh);
-    a.wino_order = getenv("EVR_WINO_ORDER") ? atoi(getenv("EVR_WINO_ORDER")) : 1;
+    a.wino_order = lib_knobs().wino_order;
 }
 // picks (wm, nb) for the shape: fills the 256 CUs when M is small
 void pick_conv_tile(const ConvArgs& a, int kc, int* wm, int* nb);

@@ -329,8 +329,8 @@ int launch_head_conv(const HeadArgs& a, hipStream_t stream) {
         // one box (tools/head_blocks_ab.sh, two rounds): 768 work-groups (the third per CU starts when a first one ends) 421 us, 512 or
         // 1024: 382-384 us; a 168-register build that does fit three spills the weight fragments (730 us); both row passes of a wave
         // unrolled together 390 us.  EVR_HEAD_BLOCKS overrides the grid.
-        static const int wlds = [] { const char* e = getenv("EVR_HEAD_WLDS"); return e ? atoi(e) : 0; }();      // (A/B: weights in LDS, three work-groups per CU)
-        static const int head_blocks = [] { const char* e = getenv("EVR_HEAD_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : (wlds ? 768 : 512); }();
+        const int wlds = lib_knobs().head_wlds;      // (EVR_HEAD_WLDS, A/B: weights in LDS, three work-groups per CU -- then 768)
+        const int head_blocks = lib_knobs().head_blocks;
         const dim3 g((unsigned)(ntiles < head_blocks ? ntiles : head_blocks));
         const size_t tile_b = (((size_t)a.B * 13 * 36 + 3) & ~(size_t)3) * sizeof(unsigned);
         if (wlds) hipLaunchKernelGGL(head_mfma_kernel<true>, g, dim3(256), tile_b + (size_t)20 * 64 * 16, stream, a2);

@@ -10,22 +10,24 @@ namespace evr {
 
 ConvKnobs conv_knobs_from(const char* (*get)(const char*)) {
     ConvKnobs k;
-    const auto num = [&](const char* name, int dflt) { const char* e = get(name); return e ? atoi(e) : dflt; };
-    // <first>,<second>: either part may be missing
-    const auto second = [&](const char* name, int dflt) { const char* e = get(name); const char* c = e ? strchr(e, ',') : nullptr; return c ? atoi(c + 1) : dflt; };
-    k.no_band = get("EVR_NO_BAND") != nullptr;
+    // (the parse idioms are knobs.h's)
+    const auto num = [&](const char* name, int dflt) { return knob_num(get, name, dflt); };
+    const auto second = [&](const char* name, int dflt) { return knob_second(get, name, dflt); };
+    const auto set = [&](const char* name) { return knob_set(get, name); };
+    const auto on = [&](const char* name) { return knob_on(get, name); };
+    k.no_band = set("EVR_NO_BAND");
     k.band_min = num("EVR_BAND_MIN", 1);
-    k.band5 = !(k.no_band || (get("EVR_BAND5") && atoi(get("EVR_BAND5")) == 0));
-    k.band5_min = get("EVR_BAND_MIN") ? k.band_min : num("EVR_BAND5_MIN", 1);
-    k.band_prog_all = get("EVR_BAND_PROG_ALL") ? atoi(get("EVR_BAND_PROG_ALL")) != 0 : true;
+    k.band5 = !(k.no_band || !on("EVR_BAND5"));
+    k.band5_min = set("EVR_BAND_MIN") ? k.band_min : num("EVR_BAND5_MIN", 1);
+    k.band_prog_all = on("EVR_BAND_PROG_ALL");
     k.prog_wide = num("EVR_PROG_WIDE", 1);
     k.prog_wide_min = num("EVR_PROG_WIDE_MIN", 600);
     k.ksplit = num("EVR_KSPLIT", 4);
-    k.ksplit_small = num("EVR_KSPLIT_SMALL", get("EVR_KSPLIT") ? 0 : 8);
+    k.ksplit_small = num("EVR_KSPLIT_SMALL", set("EVR_KSPLIT") ? 0 : 8);
     k.ksplit_epi4 = num("EVR_KSPLIT_EPI4", 1);
     k.wide = num("EVR_WIDE", 1);
     k.wide_min = num("EVR_WIDE_MIN", 600);
-    k.wide_min_set = get("EVR_WIDE_MIN") != nullptr;
+    k.wide_min_set = set("EVR_WIDE_MIN");
     k.wide_min_twin = k.wide_min_set ? k.wide_min : 350;
     k.wide_min_dec32 = k.wide_min_set ? k.wide_min : 350;
     k.wide_min_plain = num("EVR_WIDE_MIN_PLAIN", k.wide_min > 1024 ? k.wide_min : (k.wide_min_set ? k.wide_min : 1024));
@@ -44,8 +46,8 @@ ConvKnobs conv_knobs_from(const char* (*get)(const char*)) {
     k.c16_rows = num("EVR_C16_ROWS", 1);
     k.c16_rows1_rows = num("EVR_C16_ROWS_1", 1); k.c16_rows1_blocks = second("EVR_C16_ROWS_1", 0);
     k.c16_rows2_rows = num("EVR_C16_ROWS_2", 2); k.c16_rows2_blocks = second("EVR_C16_ROWS_2", 0);
-    k.lstm_dma = get("EVR_LSTM_DMA") != nullptr;
-    k.lstm_wm8 = get("EVR_LSTM_WM8") != nullptr;
+    k.lstm_dma = set("EVR_LSTM_DMA");
+    k.lstm_wm8 = set("EVR_LSTM_WM8");
     return k;
 }
 const ConvKnobs& conv_knobs() {

@@ -280,8 +280,7 @@ int launch_layernorm256(const float* x, const float* w, const float* b, float* o
 }
 int launch_attention(const AttnArgs& a, hipStream_t stream) {
     EVR_REQUIRE(a.heads * AT_D == 256 && a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0, "attention: 8 heads of 32 channels, 16-B aligned rows");
-    static const bool valu = getenv("EVR_ATTN_VALU") != nullptr && atoi(getenv("EVR_ATTN_VALU")) != 0;
-    if (valu) hipLaunchKernelGGL(attention_kernel, dim3((unsigned)((a.Lq + 255) / 256), a.heads, a.n), dim3(256), 0, stream, a);
+    if (lib_knobs().attn_valu) hipLaunchKernelGGL(attention_kernel, dim3((unsigned)((a.Lq + 255) / 256), a.heads, a.n), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(attention_mfma_kernel, dim3((unsigned)((a.Lq + 127) / 128), a.heads, a.n), dim3(256), 0, stream, a);
     EVR_LAUNCH_CHECK();
     return EVR_OK;

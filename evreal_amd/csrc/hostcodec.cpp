@@ -190,7 +190,7 @@ extern "C" int evr_png_pool_create(int n_threads, int level, evr_png_pool** out)
     EVR_REQUIRE(out && n_threads >= 1 && n_threads <= 256 && level >= 0 && level <= 9, "evr_png_pool_create: 1..256 threads, zlib level 0..9");
     evr_png_pool* p = new evr_png_pool();
     p->level = level;
-    if (const char* e = getenv("EVREAL_PNG_PER_DIR")) { const int v = atoi(e); if (v >= 1) p->per_dir = v; }
+    if (lib_knobs().png_per_dir >= 1) p->per_dir = lib_knobs().png_per_dir;      // (EVREAL_PNG_PER_DIR)
     for (int i = 0; i < n_threads; ++i) p->workers.emplace_back([p] { p->run(); });
     *out = p;
     return EVR_OK;

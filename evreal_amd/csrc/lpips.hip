@@ -437,8 +437,7 @@ static void lpips_fill_plan(evr_lpips* m, PlanCache<4>::Plan& pl, int n) {
         {   // conv2 (5x5) on the band kernel with 8 KB of LDS padding (two blocks per CU instead of three); EVR_LPIPS_BAND5=<KB> sets the
             // padding, EVR_LPIPS_BAND5=-1 keeps the implicit GEMM (the default until the evaluation stream moved behind the residual
             // blocks: beside the ConvLSTM layers its LDS footprint cost more than the kernel gained; now +0.7 .. 1.0 %, profiles/r03_env_ab.txt)
-            const char* e = getenv("EVR_LPIPS_BAND5");
-            const int kb = e ? atoi(e) : 8;
+            const int kb = lib_knobs().lpips_band5_kb;
             a.no_band5 = kb < 0 ? 1 : 0; a.band_lds_pad = kb < 0 ? 0 : kb * 1024;
         }
         pick_conv_tile(a, 32, &pl.wm[i], &pl.nb[i]);
@@ -470,7 +469,7 @@ extern "C" int evr_lpips_forward(evr_lpips* m, const float* img, const float* re
         EVR_HIP(hipFuncSetAttribute((const void*)lpips_conv1_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         if (dev >= 0 && dev < 64) attr_done[dev].store(1, std::memory_order_relaxed);
     }
-    static const bool conv1_valu = getenv("EVR_LPIPS_CONV1_VALU") != nullptr;      // A/B switch: the direct VALU kernel in split mode too
+    const bool conv1_valu = lib_knobs().lpips_conv1_valu;      // EVR_LPIPS_CONV1_VALU, A/B switch: the direct VALU kernel in split mode too
     if (m->d_wfrag1 && !conv1_valu) {
         const size_t lds = (size_t)(71 * 71 + 3) * sizeof(float) + (size_t)8 * 2 * 2 * 64 * 16;
         hipLaunchKernelGGL(lpips_conv1_mfma_kernel, dim3((m->w[0] + 15) / 16, (m->h[0] + 15) / 16, n2), dim3(256), lds, stream, c1);
@@ -489,7 +488,7 @@ extern "C" int evr_lpips_forward(evr_lpips* m, const float* img, const float* re
     // The layer scores read both images' features again: scored right behind the layer that wrote them (EVR_LPIPS_SCORE_SPLIT, default
     // 1) they come from the Infinity Cache -- 446 MB per 64-frame step that one launch at the end fetched from HBM (conv1's 180 MB of
     // features are long evicted by then).  Same partial sums, same final reduction: bit-identical scores.
-    static const int score_split = getenv("EVR_LPIPS_SCORE_SPLIT") ? atoi(getenv("EVR_LPIPS_SCORE_SPLIT")) : 1;
+    const int score_split = lib_knobs().lpips_score_split;
     const int C[5] = {64, 192, 384, 256, 256};
     ScoreArgs sa;
     const int sblocks = score_blocks(n);

@@ -263,8 +263,7 @@ int prep_tconv(Conv& c, const HostTensor* w, const Affine& af, int cin, int cout
     memset(&c.tp, 0, sizeof(c.tp));
     c.tp.ngroups = 4; c.tp.grp_cols = grp_cols;
     // more than 32 output channels: interleave the four phases per 128-column tile (conv.h ConvTaps::inter) -- EVR_TCONV_INTER=0: phase-major
-    static const bool inter_on = getenv("EVR_TCONV_INTER") ? atoi(getenv("EVR_TCONV_INTER")) != 0 : true;
-    const bool inter = inter_on && c.kc == 32 && cout == grp_cols && cout % 32 == 0 && cout > 32;
+    const bool inter = lib_knobs().tconv_inter && c.kc == 32 && cout == grp_cols && cout % 32 == 0 && cout > 32;
     auto row_of = [&](int g, int co) { return inter ? (co / 32) * 128 + g * 32 + co % 32 : g * grp_cols + co; };
     if (inter) { c.tp.inter = 1; c.tp.grp_cols = 32; }
     // shared taps
@@ -379,8 +378,7 @@ int finish_conv(evr_model* m, Conv& c) {
     // 16-channel 3x3 layers (FireNet): v_mfma_f32_32x32x16_f16 contracts exactly one 16-channel H2 group, so in the split modes they
     // run the three-f16-product arithmetic on UNPADDED tensors (conv.hip conv3x3_c16_kernel) whatever the mode of the 32-channel
     // layers -- fp32-grade (the goldens hold 1e-5), and no longer the 1/16-rate fp32 MFMA.  EVR_FIRENET_H3=0: the exact-fp32 path.
-    static const bool fire_h3 = getenv("EVR_FIRENET_H3") ? atoi(getenv("EVR_FIRENET_H3")) != 0 : true;
-    if (c.kc == 16 && m->arith != 0 && fire_h3 && c.k == 3 && c.stride == 1 && !c.transposed && c.cin0 == 16 && (c.cin1 == 0 || c.cin1 == 16) &&
+    if (c.kc == 16 && m->arith != 0 && lib_knobs().firenet_h3 && c.k == 3 && c.stride == 1 && !c.transposed && c.cin0 == 16 && (c.cin1 == 0 || c.cin1 == 16) &&
         (m->desc.arch == EVR_ARCH_FIRENET_LEGACY || m->desc.arch == EVR_ARCH_FIRENET) && c.n_gemm == 32)
         c.x3 = 3;
     if (c.x3 && c.k == 5 && c.stride == 2 && !c.transposed && c.cin1 == 0 && c.n_gemm % 64 == 0 && 25 * (c.cin0 / 32) < BAND_PROG_MAX - 2) {
@@ -395,15 +393,13 @@ int finish_conv(evr_model* m, Conv& c) {
     // Winograd-domain weights too -- G g G^T in fp64 -- and run F(2x2, 3x3): 2.25x fewer fp32 MFMAs (EVR_WINO=0: direct form only)
     // (round 6, later: the k5 s2 transposed decoders too -- their four phases are 3x3 convolutions on the input grid sharing one input
     // transform, 16 instead of 25 multiplies per 2x2 outputs and phase; EVR_WINO_TCONV=0: direct form)
-    static const bool wino_tconv = getenv("EVR_WINO_TCONV") ? atoi(getenv("EVR_WINO_TCONV")) != 0 : true;
     const bool wino_plain = c.k == 3 && !c.transposed && c.tp.ngroups == 1 && c.n_valid == c.n_gemm &&
         ((c.epi == EPI_LSTM && c.hidden % 16 == 0) || c.epi == EPI_BIAS || c.epi == EPI_BIAS_RELU || c.epi == EPI_RESIDUAL_RELU);
-    const bool wino_t = wino_tconv && c.transposed && c.tp.ngroups == 4 && c.tp.ntaps == 9 && c.cin1 == 0 && c.n_valid % 32 == 0 && c.n_gemm == 4 * c.n_valid &&
+    const bool wino_t = lib_knobs().wino_tconv && c.transposed && c.tp.ngroups == 4 && c.tp.ntaps == 9 && c.cin1 == 0 && c.n_valid % 32 == 0 && c.n_gemm == 4 * c.n_valid &&
         (c.epi == EPI_BIAS || c.epi == EPI_BIAS_RELU);
     // ... and the k5 stride-2 encoders: in space-to-depth form (prep_s2d's weight layout) they are 3x3 stride-1 convolutions over 2x2
     // pixel blocks with 4 cin channels, 36 (tap, phase) pairs of which 25 carry weights -- Winograd needs 16 (EVR_WINO_S2D=0: direct form)
-    static const bool wino_s2d_on = getenv("EVR_WINO_S2D") ? atoi(getenv("EVR_WINO_S2D")) != 0 : true;
-    if (c.x3 == 0 && c.kc == 32 && wino_enabled() && wino_s2d_on && c.k == 5 && c.stride == 2 && !c.transposed && c.tp.ngroups == 1 && c.tp.ntaps == 25 &&
+    if (c.x3 == 0 && c.kc == 32 && wino_enabled() && lib_knobs().wino_s2d && c.k == 5 && c.stride == 2 && !c.transposed && c.tp.ngroups == 1 && c.tp.ntaps == 25 &&
         c.cin1 == 0 && c.cin0 % 8 == 0 && ((c.cin0 / 8) & (c.cin0 / 8 - 1)) == 0 && c.n_gemm % 64 == 0 && c.n_valid == c.n_gemm &&
         (c.epi == EPI_BIAS || c.epi == EPI_BIAS_RELU)) {
         const int cin = c.cin0;
@@ -664,9 +660,8 @@ int build_firenet(evr_model* m) {
     const std::string g2 = legacy ? "net.resblocks.0.recurrent_block" : "G2";
     const std::string r2 = legacy ? "net.resblocks.1" : "R2";
     const std::string pred = legacy ? "net.pred" : "pred";
-    static const bool pad32 = getenv("EVR_FIRENET_PAD32") ? atoi(getenv("EVR_FIRENET_PAD32")) != 0 : false;
     m->fire_C = C;
-    if (C == 16 && m->arith != 0 && pad32) {
+    if (C == 16 && m->arith != 0 && lib_knobs().firenet_pad32) {      // (EVR_FIRENET_PAD32=1)
         firenet_pad_state_dict(m, head);
         C = m->fire_C = 32;
     }
@@ -933,7 +928,7 @@ int plan_conv(evr_model* m, int ci, const Pair& in0, const Pair& out, const Conv
         a.wgt_wino = c.d_wino; a.wino_s2d = c.wino_s2d; set_wino_grid(a);
         a.sat = m->d_sat ? m->d_sat + ci : nullptr;
         a.in_packed = x.fmt != 0; a.out_packed = y.fmt != 0;
-        if (const char* e = getenv("EVR_ABLATE")) a.debug_ablate = (c.epi == EPI_LSTM || getenv("EVR_ABLATE_ALL")) ? atoi(e) : 0;
+        a.debug_ablate = (c.epi == EPI_LSTM || lib_knobs().ablate_all) ? lib_knobs().ablate : 0;      // (EVR_ABLATE / EVR_ABLATE_ALL: timing only)
     }
     if (o.post_add) { if (int rc = set_post_add(c, o.post_add)) return rc; }
     pick_conv_tile(c.args[0], c.kc, &c.wm, &c.nb);
@@ -1062,7 +1057,7 @@ struct Planner {
         if (c.epi != EPI_BIAS_RELU && c.epi != EPI_RESIDUAL_RELU && c.epi != EPI_BIAS) return;
         // the skip is the head tensor and the matrix-core head kernel runs: it also writes sum_c pred_w[c] * head[c] per pixel (hdot),
         // and the decoder's epilogue adds that one float instead of loading and unpacking the 32 skip channels
-        const bool by_dot = hdot.p && m->head.wfrag && m->head.cout == 32 && getenv("EVR_NO_PRED_DOT") == nullptr;
+        const bool by_dot = hdot.p && m->head.wfrag && m->head.cout == 32 && !lib_knobs().no_pred_dot;      // (EVR_NO_PRED_DOT)
         if (by_dot) { m->head.pred_w = m->d_pred_w; m->head.pred_dot = hdot.p; }
         if (skip.p && (rc = set_post_add(c, skip))) return;
         for (int p = 0; p < 2; ++p) {

@@ -7,6 +7,7 @@
 // Both are HBM/L2-bound elementwise passes around small reductions; fp32 with one rounding per
 // operation (built with -ffp-contract=off) so the elementwise arithmetic matches numpy/torch.
 #include "common.h"
+#include "knobs.h"
 #include "pct.h"        // pct_rank, pct_lerp (shared with color.hip)
 #include <cstdlib>
 
@@ -423,10 +424,10 @@ extern "C" int evr_percentile_normalize(float* img, int n, int H, int W, float q
     }
     // two work-groups per image (one per percentile, both ranks each) instead of four (one per rank): half the image passes;
     // +0.3 .. +0.5 % on the headline in three A/B pairs on one box.  EVR_PCT_PAIR=0 restores the four-work-group form.
-    static const int pair = [] { const char* e = getenv("EVR_PCT_PAIR"); return e ? atoi(e) : 1; }();
+    const int pair = evr::lib_knobs().pct_pair;
     // round 5: the one-pass sampled-bracket select (exact: the bracket is verified, the four-pass select is its fallback);
     // EVR_PCT_FAST=0 restores the four-pass form
-    static const int fast = [] { const char* e = getenv("EVR_PCT_FAST"); return e ? atoi(e) : 1; }();
+    const int fast = evr::lib_knobs().pct_fast;
     if (fast && px % 4 == 0 && px >= 1024 && (((uintptr_t)img) & 15) == 0)
         hipLaunchKernelGGL(pct_select_fast_kernel, dim3(2, n), dim3(PCT_THREADS), 0, stream, img, px, q_lo, q_hi, (float*)workspace);
     else

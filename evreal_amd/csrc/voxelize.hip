@@ -42,6 +42,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "knobs.h"
 
 namespace {
 
@@ -496,8 +497,8 @@ struct VoxPlan {
 };
 
 int acc_kb() {
-    const char* e = getenv("EVR_VOX_ACC_KB");      // tuning knob: LDS for the cells -> rows per range -> workgroups per CU
-    const int v = e ? atoi(e) : ACC_KB_DEFAULT;
+    // EVR_VOX_ACC_KB, tuning knob: LDS for the cells -> rows per range -> workgroups per CU
+    const int v = evr::lib_knobs().vox_acc_kb_set ? evr::lib_knobs().vox_acc_kb : ACC_KB_DEFAULT;
     return v < 8 ? 8 : (v > 128 ? 128 : v);
 }
 
@@ -555,11 +556,6 @@ SideStream* side_stream(int dev) {
     return ok ? &p : nullptr;
 }
 
-int split_groups_env() {
-    const char* e = getenv("EVR_VOX_SPLIT");       // tuning knob: split workgroups per window
-    return e ? atoi(e) : 0;
-}
-
 template <bool RAW>
 int voxelize_impl(const EventSrc& src, const int64_t* win_begin, const int64_t* win_end, const int64_t* rec_base,
                   int n_windows, int64_t n_events_total,
@@ -598,7 +594,7 @@ int voxelize_impl(const EventSrc& src, const int64_t* win_begin, const int64_t* 
         if (dev >= 0 && dev < 64) attr_done[dev].fetch_or(bit, std::memory_order_relaxed);
     }
     // split workgroups per window: enough for the average window in one pass, at most 32 (longer windows loop)
-    int S = split_groups_env();
+    int S = evr::lib_knobs().vox_split;      // (EVR_VOX_SPLIT, tuning knob)
     if (S <= 0) {
         const int64_t avg = n_events_total / n_windows;
         S = (int)((avg + SEG - 1) / SEG);
@@ -620,7 +616,7 @@ int voxelize_impl(const EventSrc& src, const int64_t* win_begin, const int64_t* 
     // events per window, us per call for 1 / 2 / 4 / 8 chunks): 64 windows 66 / 88 / 93 / 140, 512 windows 279 / 289 / 291 / 333,
     // 2048 windows 1171 / 1081 / 1099 / 1090 -- the cross-stream hand-offs cost more than the overlap returns until a chunk is
     // ~1000 windows, so: two chunks from 2048 windows on, one below.  EVR_VOX_CHUNKS=<n> forces a count.
-    static const int chunks_env = getenv("EVR_VOX_CHUNKS") ? atoi(getenv("EVR_VOX_CHUNKS")) : 0;
+    const int chunks_env = evr::lib_knobs().vox_chunks;
     int C = chunks_env > 0 ? chunks_env : (n_windows >= 2048 ? 2 : 1);
     if (C > MAX_CHUNKS) C = MAX_CHUNKS;
     if (C > n_windows / 8) C = n_windows / 8 > 0 ? n_windows / 8 : 1;
@@ -636,7 +632,7 @@ int voxelize_impl(const EventSrc& src, const int64_t* win_begin, const int64_t* 
     auto launch_range = [&](int w0, int w1, int publish) {
         const int nw = w1 - w0;
         const int64_t blocks = xcd_map ? (int64_t)((nw + 7) / 8) * 8 * pl.G : (int64_t)nw * pl.G;
-        static const int scan_probe = getenv("EVR_VOX_SCANPROBE") ? atoi(getenv("EVR_VOX_SCANPROBE")) : 0;
+        const int scan_probe = evr::lib_knobs().vox_scanprobe;      // (EVR_VOX_SCANPROBE: timing experiment)
         if (RAW && scan_probe == 1)
             hipLaunchKernelGGL((vox_range_kernel<RAW, RAW ? 1 : 0>), dim3((unsigned)blocks), dim3(K2T), pl.lds2, stream, win_begin, win_end, rec_base,
                                rec, table, out, partials, hdr, w1, pl.G, pl.rows, pl.Rp, B, H, W, vec_out, xcd_map, rq_magic, w0, publish, src.xy);

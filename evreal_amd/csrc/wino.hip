@@ -57,10 +57,7 @@ void wino_pack_weights(const std::vector<float>& w, int n_gemm, int cin, int lst
             }
 }
 
-bool wino_enabled() {
-    static const bool on = getenv("EVR_WINO") ? atoi(getenv("EVR_WINO")) != 0 : true;
-    return on;
-}
+bool wino_enabled() { return lib_knobs().wino; }
 
 // host-side test of a launch plan (model.cpp sets wgt_wino only for layers that pass the shape part of this)
 bool wino_eligible(const ConvArgs& a) {
@@ -613,10 +610,10 @@ int launch_conv_wino(const ConvArgs& a, const ConvArgs* d_args, hipStream_t stre
     const int64_t total = ((Mt + 63) / 64) * (a.cout / 64);
     EVR_REQUIRE(total < (1LL << 31), "conv_wino: too many work items");
     // persistent blocks, one per CU (EVR_WINO_BLOCKS overrides the count); libm-grade gate activations with EVR_WINO_FASTACT=0
-    static const int nblocks = getenv("EVR_WINO_BLOCKS") && atoi(getenv("EVR_WINO_BLOCKS")) > 0 ? atoi(getenv("EVR_WINO_BLOCKS")) : 256;
-    static const bool fast_act = getenv("EVR_WINO_FASTACT") ? atoi(getenv("EVR_WINO_FASTACT")) != 0 : true;
+    const int nblocks = lib_knobs().wino_blocks;
+    const bool fast_act = lib_knobs().wino_fastact;
     const unsigned grid = (unsigned)(total < nblocks ? total : nblocks);
-    static const int var = getenv("EVR_WINO_VAR") ? atoi(getenv("EVR_WINO_VAR")) : 0;
+    const int var = lib_knobs().wino_var;      // (EVR_WINO_VAR: timing experiments)
     if (a.epi == EPI_LSTM) {
         if (!fast_act) hipLaunchKernelGGL((wino::wino_f32_kernel<true, false>), dim3(grid), dim3(256), 0, stream, d_args, (int)total, img);
         else if (var == 2) hipLaunchKernelGGL((wino::wino_f32_kernel<true, true, 2>), dim3(grid), dim3(256), 0, stream, d_args, (int)total, img);

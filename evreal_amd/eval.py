@@ -115,9 +115,10 @@ def _model_cache_key(model_name, checkpoint_path):
     from . import lib as _lib
     _lib.require_gpu()          # (EvrError on a machine without a GPU, before torch is asked for its current device)
     st = os.stat(checkpoint_path)
-    # EVR_ARITH / EVR_FP32 / EVR_FIRENET_* are read when a model is created, so they belong in the key.  Most other EVR_* switches
-    # (EVR_KSPLIT, EVR_C16_*, EVR_WIDE*, EVR_LPIPS_*) are function-local statics of the library, read ONCE PER PROCESS: changing
-    # them inside a process gives a new cache entry that still runs the old setting -- set them before the first call.
+    # Every native EVR_* switch -- EVR_ARITH / EVR_FP32 / EVR_FIRENET_* included -- is a field of one of the library's two tables
+    # (csrc/knobs.h LibKnobs, csrc/conv_route.h ConvKnobs), each read ONCE PER PROCESS at its first use: changing one inside a
+    # process gives a new cache entry that still runs the old setting -- set them before the first call.  (Another arithmetic
+    # inside a process is per model: exact_twin().)
     switches = tuple(sorted((k, v) for k, v in os.environ.items() if k.startswith('EVR_')))
     return (model_name, os.path.abspath(checkpoint_path), st.st_mtime_ns, st.st_size, torch.cuda.current_device(), switches)
 
